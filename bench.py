@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: Gibbs iterations/sec of LogitICARGibbs on a 100x100 ICAR lattice.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--chains-per-gpu C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--chains-per-gpu C] [--dump-outputs DIR] [--full]
 
 A "step" is ONE Gibbs iteration of every chain resident on a GPU (all seven conditional updates of
 the reference's LogitICARGibbs.step(), logit.py:254-266, for C chains batched in each kernel).
@@ -11,11 +11,18 @@ per GPU.  For N > 1 (launched by torch.distributed.run -- used as a process laun
 torch -- one rank per GPU) every rank runs its own 4 chains -- chains are the natural shard, weak scaling -- after ONE
 RCCL broadcast (ncclCommInitRank / ncclBroadcast through the engine's C ABI) of the laid-out problem arrays from rank
 0's device to the other devices; there is no per-iteration collective.  value = chain-iterations of all ranks /
-max-over-ranks wall time of exactly K timed steps.  The same line carries `split_4_chains`: SURVEY 8(e)'s split of
-the metric's 4 chains over the N GPUs (4 / 2 / 1 / <= 1 per GPU).  Without a launcher, `--gpus N` drives the N GPUs
-from this one process, a host thread each (EngineGroup).
+max-over-ranks wall time of exactly K timed steps; ms_per_step = that wall time / K.  Without a launcher, `--gpus N`
+drives the N GPUs from this one process, a host thread each (EngineGroup).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the JSON line (headline, workload, every chain's last draw).
+`--dump-outputs DIR` also writes what the last timed step computed, every chain of the job, as float64 .npy files:
+alpha (chains x q), beta (chains x p), tau (chains), and the spatial effect eta and latent occupancy z (chains x sites;
+a fixed, seeded sample of the sites when the files would pass 64 MB).  Inputs depend only on the arguments (data seed 0,
+sampler seed 10), so two builds can be compared output for output.
+
+`--full` adds what takes runs of its own, to the same line:
+  split_4_chains : (N > 1) SURVEY 8(e)'s split of the metric's 4 chains over the N GPUs (4 / 2 / 1 / <= 1 per GPU);
+  ranks        : (N > 1) every rank, reported through the communicator the broadcast ran on;
   roofline     : the dominant kernel (k_iter: tau, right-hand side, the whole MINRES solve of eta, projection
                  and beta sums of one iteration, all chains): algorithmic bytes per launch / its mean DISPATCH
                  duration -- the start / stop events of hipExtLaunchKernel on the engine's main stream, i.e. the
@@ -234,6 +241,143 @@ def timed_run(eng, comm, steps, warmup, checkpoint=False):
     return elapsed, stats_warm, (eng.stats() if eng is not None else None), last, ckpt
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def chain_state(eng, chain_ids):
+    """eta and z of this rank's chains as the last timed step left them, by global chain number."""
+    if eng is None:
+        return {}
+    return {c: {name: np.asarray(eng.get(name, i), dtype=np.float64) for name in ('eta', 'z')} for i, c in enumerate(chain_ids)}
+
+
+def dump_outputs(path, prob, draws, state):
+    """DIR/<name>.npy, float64, chains in global order: the last step's alpha / beta / tau (`draws`: chain -> its last
+    recorded row) and the state it left (`state`: chain -> eta, z).  Over DUMP_BYTES, eta and z keep a fixed, seeded
+    sample of the sites."""
+    chains = sorted(draws)
+    rows = np.array([draws[c] for c in chains], dtype=np.float64)
+    q, p = prob.q, prob.p
+    out = {'alpha': rows[:, :q], 'beta': rows[:, q:q + p], 'tau': rows[:, q + p]}
+    sites = {name: np.stack([state[c][name] for c in chains]) for name in ('eta', 'z')}
+    n = sites['eta'].shape[1]
+    small = sum(a.nbytes for a in out.values())
+    per_site = 8 * len(chains) * len(sites)
+    if small + per_site * n > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=(DUMP_BYTES - small) // per_site, replace=False))
+        sites = {name: a[:, keep] for name, a in sites.items()}
+    out.update(sites)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a))
+
+
+def roofline(eng0, prob, stats, stats_warm, ckpt0, steps_timed, elapsed, C, workload_key):
+    """--full: the dominant kernel against the HBM roofline, from a profile pass of its own after the timed region
+    (`ckpt0`: the chains' state at the start of the region, replayed when given).  `workload_key`: the workload of the
+    committed PMC passes, None when they do not apply."""
+    # the profile pass REPLAYS the first 200 launches of the timed region (the chains are put back to where the region
+    # started: same keys, same iterations, same solves), so the dispatch overhead it measures belongs to launches the
+    # timed region made -- same MINRES steps per launch -- not to later ones
+    stats_end = stats
+    replay = ckpt0 is not None
+    if replay:
+        eng0.restore(ckpt0)
+    stats_before_prof = eng0.stats()
+    prof = eng0.profile(reps=min(200, steps_timed))
+    sell = sell_entry_count(prob)
+    fused = bool(stats['persistent_solve']) and prof['iter']['launches'] > 0
+    if fused:
+        # the timed region itself: every k_iter launch is clocked from inside (first workgroup in to last chain out,
+        # constant-rate device wall clock), and its MINRES iterations are counted on the device
+        d_solves = max(1, stats['solves'] - stats_warm['solves'])
+        steps = (stats['krylov_total'] - stats_warm['krylov_total']) / d_solves + 3.0
+        kname = 'k_tiles' if stats['persistent_solve'] == 3 else 'k_iter'   # (k_tiles: the tile-looping form for large lattices, occ_tiles.hpp)
+        ka = {'avg_us': stats['iter_kernel_mean_us'], 'launches': stats['iter_kernel_launches']}
+        bytes_launch = iter_bytes_per_launch(prob, C, sell, steps)
+        per_iter = {'iter': 1, 'z_ob': 1}
+        prof['iter_in_situ_hip_events'] = prof['iter']
+        prof['iter'] = dict(ka, total_us=ka['avg_us'] * ka['launches'])
+        timing = ('every k_iter launch of the TIMED REGION clocked inside the kernel (device wall clock, first '
+                  'workgroup in to last chain out; HIP events cannot bracket a graph node without adding nodes); '
+                  'cross-checks: avg_launch_us_by_kernel.iter_in_situ_hip_events = two HIP events on the main '
+                  'stream around each of 200 further launches, launched one by one after the timed region (the '
+                  'device idles between them: slower), and the rocprofv3 kernel_stats of the same command in '
+                  'profiles/')
+    else:
+        steps = None
+        kname, ka = 'k_minres', prof['minres']
+        bytes_launch = minres_bytes_per_launch(prob, C, sell)
+        per_iter = {'eta_init': 1, 'minres': stats['krylov_cap'] + 3, 'beta_partial': 1, 'z_ob': 1}
+        timing = ('HIP events on the engine stream around 200 replays of a captured solve prefix '
+                  '(k_eta_init + k_minres launches 1..8, every launch cache-cold as in the real solve), '
+                  'k_eta_init subtracted; = kernel duration + one dependent-launch boundary')
+    achieved = bytes_launch / (ka['avg_us'] * 1e-6) / 1e9 if ka['avg_us'] > 0 else 0.0
+    # The number rocprofv3 reproduces (VERDICT r2: the in-kernel clock stops ~3 us short of what the profiler reports for
+    # the same launch -- launch ramp and end-of-kernel release are outside a kernel's own view): the DISPATCH duration
+    # of k_iter, from the start / stop events of hipExtLaunchKernel (the begin / end timestamps of the dispatch's
+    # completion signal, the profiler's own basis), over the 200 in-situ launches that follow the timed region, with the
+    # MINRES steps THOSE launches ran.  `frac` is quoted on this basis; the in-kernel clock of the timed region stays
+    # beside it.
+    in_kernel = {'achieved': round(achieved, 1), 'frac': round(achieved / HBM_PEAK_GBS, 4), 'avg_launch_us': round(ka['avg_us'], 3),
+                 'launches_timed': ka['launches'], 'bytes_per_launch': bytes_launch,
+                 'minres_steps_per_launch': round(steps, 2) if steps else None,
+                 'basis': 'device wall clock read inside k_iter, first workgroup in to last chain out, every launch of the timed region'}
+    stats_prof = eng0.stats()
+    disp_us = stats_prof.get('profile_iter_dispatch_us', 0.0)
+    dispatch = None
+    if fused and disp_us > 0:
+        # the same 200 launches by both clocks: what the dispatch adds around the kernel's own view of itself
+        n0, m0 = stats_before_prof['iter_kernel_launches'], stats_before_prof['iter_kernel_mean_us']
+        n1, m1 = stats_prof['iter_kernel_launches'], stats_prof['iter_kernel_mean_us']
+        in_kernel_prof = (n1 * m1 - n0 * m0) / max(1, n1 - n0)
+        overhead = max(0.0, disp_us - in_kernel_prof)
+        m0 = stats_end['iter_kernel_mean_us']
+        est = m0 + overhead                     # dispatch duration of the TIMED REGION's launches
+        achieved = bytes_launch / (est * 1e-6) / 1e9
+        dispatch = {'dispatch_overhead_us': round(overhead, 3), 'profile_pass_dispatch_us': round(disp_us, 3),
+                    'profile_pass_in_kernel_us': round(in_kernel_prof, 3), 'profile_pass_launches': int(n1 - n0),
+                    'profile_pass': ('a replay of the first launches of the timed region (chains restored to its start state)' if replay
+                                     else 'further launches that continue the chains after the timed region'),
+                    'profile_pass_minres_steps_per_launch': round(stats_prof['profile_minres_iterations'] + 3.0, 2)}
+        ka = {'avg_us': est, 'launches': ka['launches']}
+        timing = ('mean DISPATCH duration of the k_iter launches of the timed region = their mean by the in-kernel clock '
+                  '(every launch; roofline.in_kernel_clock) + the dispatch overhead measured live on a REPLAY of the '
+                  'region\'s first launches (chains restored to the region\'s start state: the same solves): '
+                  'hipExtLaunchKernel start / stop events (the begin / end timestamps of the dispatch\'s completion signal = '
+                  'what rocprofv3 --kernel-trace reports; launch ramp and end-of-kernel release included) minus the '
+                  'in-kernel clock of the same launches (roofline.dispatch_basis).  HIP events cannot bracket a node of a '
+                  'replayed graph without adding nodes.  Check: profiles/r04_bench_trace_region.json = the rocprofv3 kernel '
+                  'trace of this command averaged over the timed region\'s launches')
+    traffic, traffic_file = pmc_traffic('occ::' + kname, workload_key) if workload_key else (None, None)
+    total_us = sum(prof[k]['avg_us'] * per_iter[k] for k in per_iter)
+    # SURVEY 8(d)'s whole-iteration accounting beside the dominant kernel's: B_iter(measured K, R_e = R, n_no = 0.4 n)
+    kmean = stats['krylov_mean']
+    whole = whole_iteration_bytes(prob, kmean) * C
+    return {
+        'bound': 'hbm', 'kernel': kname,
+        'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+        'frac': round(achieved / HBM_PEAK_GBS, 4),
+        'traffic': traffic,
+        'traffic_source': (traffic_file or 'none for this workload') + ' (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, bytes per launch)',
+        'bytes_per_launch': bytes_launch, 'avg_launch_us': round(ka['avg_us'], 3),
+        'launches_timed': ka['launches'],
+        'timing': timing,
+        'minres_steps_per_launch': round(steps, 2) if steps else None,
+        'in_kernel_clock': in_kernel,
+        'dispatch_basis': dispatch,
+        'algorithmic_bytes_per_minres_step': minres_bytes_per_launch(prob, C, sell),
+        'share_of_critical_path_launch_time': round(ka['avg_us'] * per_iter['iter' if fused else 'minres'] / total_us, 3) if total_us else None,
+        'avg_launch_us_by_kernel': {k: round(v['avg_us'], 3) for k, v in prof.items()},
+        'whole_iteration': {
+            'note': 'SURVEY 8(d) accounting of ONE WHOLE Gibbs iteration (all seven conditionals, 15 vector passes per '
+                    'MINRES iteration at the measured K) x chains per GPU / measured time per iteration on one GPU',
+            'bytes_per_iteration': whole, 'krylov_iterations_mean': round(kmean, 2),
+            'achieved': round(whole / (elapsed / steps_timed) / 1e9, 1), 'unit': 'GB/s',
+            'frac': round(whole / (elapsed / steps_timed) / 1e9 / HBM_PEAK_GBS, 4)},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -242,9 +386,12 @@ def main():
     ap.add_argument('--chains-per-gpu', type=int, default=4)
     ap.add_argument('--lattice', type=int, nargs=2, default=[100, 100])
     ap.add_argument('--visits', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy (float64)')
+    ap.add_argument('--full', action='store_true', help='also the roofline pass, the CPU baseline (N = 1), the 4-chain split '
+                                                        'and the ranks seen (N > 1)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-baseline-mode', choices=['auto', 'dense_eigen', 'edge'], default='auto')
-    ap.add_argument('--no-split', action='store_true', help='skip the second measurement of N > 1 (the metric\'s 4 chains split over the GPUs)')
+    ap.add_argument('--no-split', action='store_true', help='with --full: skip the second measurement of N > 1 (the metric\'s 4 chains split over the GPUs)')
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -328,6 +475,9 @@ def main():
     eng, mine = make_engine(mine_ids, gens, prob)
     start_engine(eng, mine, mine_ids, gens, starts)
     transport = eng.transport
+    # the snapshot of the chains before the timed region is taken on every run, although only --full's roofline replay
+    # reads it: the headline has always been timed right after it, and without it the same timed steps measured about 6 %
+    # slower on one MI355X (0.066 against 0.062 ms per step, four alternating runs each; cause not yet known)
     elapsed, stats_warm, stats, last_rows, ckpt0 = timed_run(eng, comm, args.steps, args.warmup, checkpoint=(rank == 0 and not in_process))
     # every chain's last recorded draw, by global chain number: the draws do not depend on how the chains are spread over
     # GPUs (chain c owns the generator the reference gives its c-th copy), so a multi-GPU line can be checked against a
@@ -335,10 +485,16 @@ def main():
     last_draws = {}
     for part in comm.allgather_obj(dict(zip(mine_ids, last_rows))):
         last_draws.update(part)
+    if args.dump_outputs:
+        state = {}
+        for part in comm.allgather_obj(chain_state(eng, mine_ids)):
+            state.update(part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, prob, last_draws, state)
 
     # ---- N > 1: SURVEY 8(e)'s split of the metric's 4 chains (4 / 2 / 1 / <= 1 per GPU), same steps ---------------
     split = None
-    if n_dev > 1 and not args.no_split:
+    if args.full and n_dev > 1 and not args.no_split:
         gens4 = chain_generators(10, 4)
         if world > 1:
             ids4 = [c for c in range(4) if c % world == rank]
@@ -369,95 +525,16 @@ def main():
     # ---- who took part (N > 1): every rank reports itself THROUGH the communicator the broadcast ran on -- with RCCL that
     # is ncclBroadcast between the ranks' devices, so a rank that RCCL does not reach cannot appear
     ranks_info = None
-    if n_dev > 1:
+    if args.full and n_dev > 1:
         seen = comm.allgather_obj({'rank': rank, 'local_rank': local_rank, 'device': local_rank, 'chains': len(mine_ids), 'pid': os.getpid()})
         ranks_info = {'ranks_seen_by_rccl' if 'rccl' in comm_note.split(' ')[0] else 'ranks_seen_by_file_rendezvous': len(seen),
                       'distinct_devices': len({(r['device']) for r in seen}) if world > 1 else n_dev,
                       'communicator': comm_note, 'members': seen}
 
     if rank == 0:
-        # ---- roofline of the dominant kernel, live, HIP events on the engine's stream --------------
         eng0 = eng.engines[0] if in_process else eng
         if in_process:
             stats, stats_warm = stats['per_device'][0], stats_warm['per_device'][0]
-        # the profile pass REPLAYS the first 200 launches of the timed region (the chains are put back to where the region
-        # started: same keys, same iterations, same solves), so the dispatch overhead it measures belongs to launches the
-        # timed region made -- same MINRES steps per launch -- not to later ones
-        stats_end = stats
-        replay = ckpt0 is not None
-        if replay:
-            eng0.restore(ckpt0)
-        stats_before_prof = eng0.stats()
-        prof = eng0.profile(reps=min(200, args.steps))
-        sell = sell_entry_count(prob)
-        fused = bool(stats['persistent_solve']) and prof['iter']['launches'] > 0
-        if fused:
-            # the timed region itself: every k_iter launch is clocked from inside (first workgroup in to last chain out,
-            # constant-rate device wall clock), and its MINRES iterations are counted on the device
-            d_solves = max(1, stats['solves'] - stats_warm['solves'])
-            steps = (stats['krylov_total'] - stats_warm['krylov_total']) / d_solves + 3.0
-            kname = 'k_tiles' if stats['persistent_solve'] == 3 else 'k_iter'   # (k_tiles: the tile-looping form for large lattices, occ_tiles.hpp)
-            ka = {'avg_us': stats['iter_kernel_mean_us'], 'launches': stats['iter_kernel_launches']}
-            bytes_launch = iter_bytes_per_launch(prob, C, sell, steps)
-            per_iter = {'iter': 1, 'z_ob': 1}
-            prof['iter_in_situ_hip_events'] = prof['iter']
-            prof['iter'] = dict(ka, total_us=ka['avg_us'] * ka['launches'])
-            timing = ('every k_iter launch of the TIMED REGION clocked inside the kernel (device wall clock, first '
-                      'workgroup in to last chain out; HIP events cannot bracket a graph node without adding nodes); '
-                      'cross-checks: avg_launch_us_by_kernel.iter_in_situ_hip_events = two HIP events on the main '
-                      'stream around each of 200 further launches, launched one by one after the timed region (the '
-                      'device idles between them: slower), and the rocprofv3 kernel_stats of the same command in '
-                      'profiles/')
-        else:
-            steps = None
-            kname, ka = 'k_minres', prof['minres']
-            bytes_launch = minres_bytes_per_launch(prob, C, sell)
-            per_iter = {'eta_init': 1, 'minres': stats['krylov_cap'] + 3, 'beta_partial': 1, 'z_ob': 1}
-            timing = ('HIP events on the engine stream around 200 replays of a captured solve prefix '
-                      '(k_eta_init + k_minres launches 1..8, every launch cache-cold as in the real solve), '
-                      'k_eta_init subtracted; = kernel duration + one dependent-launch boundary')
-        achieved = bytes_launch / (ka['avg_us'] * 1e-6) / 1e9 if ka['avg_us'] > 0 else 0.0
-        # The number rocprofv3 reproduces (the in-kernel clock stops ~3 us short of what the profiler reports for
-        # the same launch -- launch ramp and end-of-kernel release are outside a kernel's own view): the DISPATCH duration
-        # of k_iter, from the start / stop events of hipExtLaunchKernel (the begin / end timestamps of the dispatch's
-        # completion signal, the profiler's own basis), over the 200 in-situ launches that follow the timed region, with the
-        # MINRES steps THOSE launches ran.  `frac` is quoted on this basis; the in-kernel clock of the timed region stays
-        # beside it.
-        in_kernel = {'achieved': round(achieved, 1), 'frac': round(achieved / HBM_PEAK_GBS, 4), 'avg_launch_us': round(ka['avg_us'], 3),
-                     'launches_timed': ka['launches'], 'bytes_per_launch': bytes_launch,
-                     'minres_steps_per_launch': round(steps, 2) if steps else None,
-                     'basis': 'device wall clock read inside k_iter, first workgroup in to last chain out, every launch of the timed region'}
-        stats_prof = eng0.stats()
-        disp_us = stats_prof.get('profile_iter_dispatch_us', 0.0)
-        dispatch = None
-        if fused and disp_us > 0:
-            # the same 200 launches by both clocks: what the dispatch adds around the kernel's own view of itself
-            n0, m0 = stats_before_prof['iter_kernel_launches'], stats_before_prof['iter_kernel_mean_us']
-            n1, m1 = stats_prof['iter_kernel_launches'], stats_prof['iter_kernel_mean_us']
-            in_kernel_prof = (n1 * m1 - n0 * m0) / max(1, n1 - n0)
-            overhead = max(0.0, disp_us - in_kernel_prof)
-            m0 = stats_end['iter_kernel_mean_us']
-            est = m0 + overhead                     # dispatch duration of the TIMED REGION's launches
-            achieved = bytes_launch / (est * 1e-6) / 1e9
-            dispatch = {'dispatch_overhead_us': round(overhead, 3), 'profile_pass_dispatch_us': round(disp_us, 3),
-                        'profile_pass_in_kernel_us': round(in_kernel_prof, 3), 'profile_pass_launches': int(n1 - n0),
-                        'profile_pass': ('a replay of the first launches of the timed region (chains restored to its start state)' if replay
-                                         else 'further launches that continue the chains after the timed region'),
-                        'profile_pass_minres_steps_per_launch': round(stats_prof['profile_minres_iterations'] + 3.0, 2)}
-            ka = {'avg_us': est, 'launches': ka['launches']}
-            timing = ('mean DISPATCH duration of the k_iter launches of the timed region = their mean by the in-kernel clock '
-                      '(every launch; roofline.in_kernel_clock) + the dispatch overhead measured live on a REPLAY of the '
-                      'region\'s first launches (chains restored to the region\'s start state: the same solves): '
-                      'hipExtLaunchKernel start / stop events (the begin / end timestamps of the dispatch\'s completion signal = '
-                      'what rocprofv3 --kernel-trace reports; launch ramp and end-of-kernel release included) minus the '
-                      'in-kernel clock of the same launches (roofline.dispatch_basis).  HIP events cannot bracket a node of a '
-                      'replayed graph without adding nodes.  Check: profiles/r04_bench_trace_region.json = the rocprofv3 kernel '
-                      'trace of this command averaged over the timed region\'s launches')
-        traffic, traffic_file = pmc_traffic('occ::' + kname, f'{rows}x{cols} queen lattice, {C} chains') if args.visits == 5 else (None, None)
-        total_us = sum(prof[k]['avg_us'] * per_iter[k] for k in per_iter)
-        # SURVEY 8(d)'s whole-iteration accounting beside the dominant kernel's: B_iter(measured K, R_e = R, n_no = 0.4 n)
-        kmean = stats['krylov_mean']
-        whole = whole_iteration_bytes(prob, kmean) * C
         out = {
             'metric': 'Gibbs iterations/sec on 100x100 ICAR lattice, 4 chains; 1/2/4/8 GPUs',
             'value': total_chains * args.steps / elapsed,
@@ -488,29 +565,11 @@ def main():
                 'threads_per_block': stats['threads_per_block'],
                 'device_ms_last_run': round(stats['last_run_ms'], 3),
             },
-            'roofline': {
-                'bound': 'hbm', 'kernel': kname,
-                'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                'frac': round(achieved / HBM_PEAK_GBS, 4),
-                'traffic': traffic,
-                'traffic_source': (traffic_file or 'none for this workload') + ' (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, bytes per launch)',
-                'bytes_per_launch': bytes_launch, 'avg_launch_us': round(ka['avg_us'], 3),
-                'launches_timed': ka['launches'],
-                'timing': timing,
-                'minres_steps_per_launch': round(steps, 2) if steps else None,
-                'in_kernel_clock': in_kernel,
-                'dispatch_basis': dispatch,
-                'algorithmic_bytes_per_minres_step': minres_bytes_per_launch(prob, C, sell),
-                'share_of_critical_path_launch_time': round(ka['avg_us'] * per_iter['iter' if fused else 'minres'] / total_us, 3) if total_us else None,
-                'avg_launch_us_by_kernel': {k: round(v['avg_us'], 3) for k, v in prof.items()},
-                'whole_iteration': {
-                    'note': 'SURVEY 8(d) accounting of ONE WHOLE Gibbs iteration (all seven conditionals, 15 vector passes per '
-                            'MINRES iteration at the measured K) x chains per GPU / measured time per iteration on one GPU',
-                    'bytes_per_iteration': whole, 'krylov_iterations_mean': round(kmean, 2),
-                    'achieved': round(whole / (elapsed / args.steps) / 1e9, 1), 'unit': 'GB/s',
-                    'frac': round(whole / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4)},
-            },
         }
+        if args.full:
+            # ---- roofline of the dominant kernel, live, HIP events on the engine's stream --------------
+            workload_key = f'{rows}x{cols} queen lattice, {C} chains' if args.visits == 5 else None
+            out['roofline'] = roofline(eng0, prob, stats, stats_warm, ckpt0, args.steps, elapsed, C, workload_key)
         if n_dev > 1:
             # how to read a SCALE curve from these lines: `value` is WEAK scaling -- every GPU runs the metric's
             # 4 chains -- so value / n_gpus is what compares with the N = 1 line (BENCH); split_4_chains is the metric's
@@ -519,10 +578,11 @@ def main():
             out['n1_equivalent'] = {'value': out['value'] / n_dev, 'unit': 'iterations/s',
                                     'note': 'value / n_gpus: each GPU runs the N = 1 workload (4 chains); compare with the N = 1 line'}
             out['scale_curve'] = 'read `value` (weak: 4 chains per GPU); efficiency = value(N) / (N * value(1))'
-            out['ranks'] = ranks_info
+            if ranks_info is not None:
+                out['ranks'] = ranks_info
         if split is not None:
             out['split_4_chains'] = split
-        if n_dev == 1 and not args.no_cpu_baseline:
+        if args.full and n_dev == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(prob, args.cpu_baseline_mode)
         print(json.dumps(out), flush=True)
     eng.close()

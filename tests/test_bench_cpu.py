@@ -34,9 +34,9 @@ def _launch(world, port, extra=()):
     return outs
 
 
-def _single_process_last_draws(n_chains, warmup=3, steps=7):
+def _single_process_last_draws(n_chains, warmup=3, steps=7, state=None):
     """The same chains in ONE batch of one process: bench.py's seeding rule (chain c owns the c-th generator of seed 10:
-    start values first, then its Philox key)."""
+    start values first, then its Philox key).  `state`: a dict that receives eta and z of every chain after the run."""
     from occuspytial_amd._engine import Engine
     from occuspytial_amd._problem import FlatProblem, chain_generators, default_start
     from occuspytial_amd.utils import make_lattice_problem
@@ -49,12 +49,25 @@ def _single_process_last_draws(n_chains, warmup=3, steps=7):
         eng.set_start(c, st['alpha'], st['beta'], st['tau'], st['eta'])
     eng.run(warmup, warmup - 1)
     a, b, t = eng.run(steps, 0)
+    if state is not None:
+        for name in ('eta', 'z'):
+            state[name] = np.stack([eng.get(name, c) for c in range(n_chains)])
     eng.close()
     return [np.concatenate([a[c, -1], b[c, -1], t[c, -1:]]) for c in range(n_chains)]
 
 
-def test_eight_ranks_run_bench_py_and_agree_with_one_process(cpu_abi):  # noqa: F811
-    outs = _launch(8, 29671)
+def _check_dump(path, draws, state):
+    """bench.py --dump-outputs: float64 files, chains in global order, equal to the same chains run in one process."""
+    got = {name: np.load(os.path.join(path, name + '.npy')) for name in ('alpha', 'beta', 'tau', 'eta', 'z')}
+    assert all(a.dtype == np.float64 for a in got.values())
+    rows = np.array(draws)
+    assert np.array_equal(got['alpha'], rows[:, :2]) and np.array_equal(got['beta'], rows[:, 2:4]) and np.array_equal(got['tau'], rows[:, 4])
+    assert np.array_equal(got['eta'], state['eta']) and np.array_equal(got['z'], state['z'])
+    assert got['eta'].shape == (len(draws), 90)
+
+
+def test_eight_ranks_run_bench_py_and_agree_with_one_process(cpu_abi, tmp_path):  # noqa: F811
+    outs = _launch(8, 29671, ['--full', '--dump-outputs', str(tmp_path)])
     lines = [ln for ln in outs[0].splitlines() if ln.strip()]
     assert len(lines) == 1, outs[0][-2000:]                       # ONE line, on rank 0 ...
     assert all(not o.strip() for o in outs[1:])                   # ... and nothing on the other ranks' stdout
@@ -69,7 +82,9 @@ def test_eight_ranks_run_bench_py_and_agree_with_one_process(cpu_abi):  # noqa: 
     assert sorted(m['rank'] for m in r['members']) == list(range(8)) and all(m['chains'] == 4 for m in r['members'])
     assert 'file rendezvous' in r['communicator']
     # the weak line: 32 chains, chain c on rank c // 4 -- the draws of a single process running all 32
-    want = _single_process_last_draws(32)
+    state = {}
+    want = _single_process_last_draws(32, state=state)
+    _check_dump(tmp_path, want, state)
     assert len(d['last_draws']) == 32
     for c in range(32):
         assert np.array_equal(np.asarray(d['last_draws'][c]), want[c]), c
@@ -82,17 +97,38 @@ def test_eight_ranks_run_bench_py_and_agree_with_one_process(cpu_abi):  # noqa: 
         assert np.array_equal(np.asarray(s['last_draws'][c]), want4[c]), c
 
 
-def test_one_rank_line_has_the_same_chains(cpu_abi):  # noqa: F811
-    """The N = 1 line of the same workload carries the draws the 8-rank line's first four chains carry (same seed rule)."""
+def test_one_rank_line_has_the_same_chains(cpu_abi, tmp_path):  # noqa: F811
+    """The N = 1 line of the same workload carries the draws the 8-rank line's first four chains carry (same seed rule).
+    A plain run is lean: no roofline pass, no CPU baseline; --dump-outputs writes the last step's outputs."""
     env = dict(os.environ, PYTHONPATH=ROOT)
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', '_bench_worker.py')] + ARGS, env=env, capture_output=True, text=True, timeout=600)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', '_bench_worker.py')] + ARGS + ['--dump-outputs', str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d['n_gpus'] == 1 and 'ranks' not in d and 'split_4_chains' not in d and d['vs_baseline'] is None
+    assert 'roofline' not in d and 'cpu_baseline' not in d
+    assert d['steps'] == 7 and abs(d['value'] - 4 * 7 / (d['ms_per_step'] * 7e-3)) < 1e-6 * d['value']
+    state = {}
+    want = _single_process_last_draws(4, state=state)
+    for c in range(4):
+        assert np.array_equal(np.asarray(d['last_draws'][c]), want[c])
+    _check_dump(tmp_path, want, state)
+
+
+def test_one_rank_full_line_adds_the_roofline(cpu_abi):  # noqa: F811
+    """--full on one rank: the roofline pass runs after the timed region and the timed chains are unchanged by it."""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        env.pop(k, None)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', '_bench_worker.py')] + ARGS + ['--full'], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['roofline']['bound'] == 'hbm' and d['roofline']['peak'] > 0 and 'cpu_baseline' not in d
     want = _single_process_last_draws(4)
     for c in range(4):
         assert np.array_equal(np.asarray(d['last_draws'][c]), want[c])

@@ -19,7 +19,7 @@ def per_kernel(root, counter):
 
 fetch, write = per_kernel(sys.argv[1], 'FETCH_SIZE'), per_kernel(sys.argv[2], 'WRITE_SIZE')
 out = {'note': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `OCC_EAGER_ONLY=1 python bench.py '
-               '--steps 40 --warmup 10 --no-cpu-baseline` (eager launches of the same kernels: counter collection '
+               '--full --steps 40 --warmup 10 --no-cpu-baseline` (eager launches of the same kernels: counter collection '
                'crashes on hipGraph launches in ROCm 7.2). Values are medians per launch in KB as reported; hbm_bytes '
                '= (2*FETCH_SIZE + WRITE_SIZE)*1024 with the gfx950 FETCH_SIZE correction of MI355X_MICROARCH.md '
                '(x2 for wide coalesced reads).',

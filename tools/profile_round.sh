@@ -17,33 +17,33 @@ has() { case " $parts " in *" $1 "*) return 0;; *) return 1;; esac; }
 if has bench; then
 # 1. per-kernel time of the default bench run (headline: 100x100, 4 chains); the k_iter dispatches of the TIMED REGION from
 #    the same trace (what roofline.frac's dispatch-duration basis is checked against)
-run rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/stats.log
+run rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/stats.log
 cp "$(ls -t $out/stats/*/*kernel_stats.csv | head -n 1)" profiles/${tag}_bench_kernel_stats.csv
 cp "$(ls -t $out/stats/*/*domain_stats.csv | head -n 1)" profiles/${tag}_bench_domain_stats.csv || true
 tail -n 1 $out/bench_under_rocprof.json > profiles/${tag}_bench_under_rocprof.json
 python3 tools/trace_region.py "$(ls -t $out/stats/*/*kernel_trace.csv | head -n 1)" 200 2000 profiles/${tag}_bench_trace_region.json > $out/trace_region.log
 # ... and of the driver's own short call
-run rocprofv3 --kernel-trace --output-format csv -d $out/stats20 -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench20_under_rocprof.json 2> $out/stats20.log
+run rocprofv3 --kernel-trace --output-format csv -d $out/stats20 -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench20_under_rocprof.json 2> $out/stats20.log
 python3 tools/trace_region.py "$(ls -t $out/stats20/*/*kernel_trace.csv | head -n 1)" 5 20 profiles/${tag}_bench_20_steps_trace_region.json > $out/trace_region20.log
 fi
 if has pmc; then
 # 2. HBM traffic per kernel: separate counter passes, eager launches
 echo "OCC_EAGER_ONLY=1" >> $out/commands.log
-OCC_EAGER_ONLY=1 run rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -- python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline > $out/fetch.json 2> $out/fetch.log
-OCC_EAGER_ONLY=1 run rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -- python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline > $out/write.json 2> $out/write.log
+OCC_EAGER_ONLY=1 run rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -- python3 bench.py --full --steps 40 --warmup 10 --no-cpu-baseline > $out/fetch.json 2> $out/fetch.log
+OCC_EAGER_ONLY=1 run rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -- python3 bench.py --full --steps 40 --warmup 10 --no-cpu-baseline > $out/write.json 2> $out/write.log
 python3 tools/pmc_traffic.py $out/fetch $out/write profiles/${tag}_pmc_hbm_traffic.json "100x100 queen lattice, 4 chains" > $out/pmc.log
 fi
 if has c4; then
 # 3. BASELINE config 4 (500x500, one chain; k_tiles): bench line, kernel stats + timed region, HBM traffic
 C4="--lattice 500 500 --chains-per-gpu 1 --steps 300 --warmup 60 --no-cpu-baseline"
-run rocprofv3 --kernel-trace --stats --output-format csv -d $out/c4_stats -- python3 bench.py $C4 > $out/c4_under_rocprof.json 2> $out/c4_stats.log
+run rocprofv3 --kernel-trace --stats --output-format csv -d $out/c4_stats -- python3 bench.py --full $C4 > $out/c4_under_rocprof.json 2> $out/c4_stats.log
 cp "$(ls -t $out/c4_stats/*/*kernel_stats.csv | head -n 1)" profiles/${tag}_c4_kernel_stats.csv
 python3 tools/trace_region.py "$(ls -t $out/c4_stats/*/*kernel_trace.csv | head -n 1)" 60 300 profiles/${tag}_c4_trace_region.json k_tiles > $out/c4_trace_region.log
-OCC_EAGER_ONLY=1 run rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/c4_fetch -- python3 bench.py --lattice 500 500 --chains-per-gpu 1 --steps 12 --warmup 4 --no-cpu-baseline > $out/c4_fetch.json 2> $out/c4_fetch.log
-OCC_EAGER_ONLY=1 run rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/c4_write -- python3 bench.py --lattice 500 500 --chains-per-gpu 1 --steps 12 --warmup 4 --no-cpu-baseline > $out/c4_write.json 2> $out/c4_write.log
+OCC_EAGER_ONLY=1 run rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/c4_fetch -- python3 bench.py --full --lattice 500 500 --chains-per-gpu 1 --steps 12 --warmup 4 --no-cpu-baseline > $out/c4_fetch.json 2> $out/c4_fetch.log
+OCC_EAGER_ONLY=1 run rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/c4_write -- python3 bench.py --full --lattice 500 500 --chains-per-gpu 1 --steps 12 --warmup 4 --no-cpu-baseline > $out/c4_write.json 2> $out/c4_write.log
 python3 tools/pmc_traffic.py $out/c4_fetch $out/c4_write profiles/${tag}_c4_pmc_hbm_traffic.json "500x500 queen lattice, 1 chains" > $out/c4_pmc.log
-python3 bench.py $C4 2> $out/c4_bench.err | tail -n 1 > profiles/${tag}_c4_bench.json
-OCC_NO_TILES=1 python3 bench.py $C4 2> $out/c4_lps.err | tail -n 1 > profiles/${tag}_c4_bench_launch_per_step.json
+python3 bench.py --full $C4 2> $out/c4_bench.err | tail -n 1 > profiles/${tag}_c4_bench.json
+OCC_NO_TILES=1 python3 bench.py --full $C4 2> $out/c4_lps.err | tail -n 1 > profiles/${tag}_c4_bench_launch_per_step.json
 fi
 if has valu; then
 # 3b. the Polya-Gamma kernels, SQ counters, BEFORE (round 3's build, tools/libocc_gibbs_r3.so: built by hand from commit c4e04c1,
@@ -84,8 +84,8 @@ if has sizes; then
 fi
 if has line; then
 # 6. the plain bench lines (not profiled): default (cpu_baseline included) and the driver's short call
-python3 bench.py 2> $out/bench.err | tail -n 1 > profiles/${tag}_bench.json
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2> $out/bench20.err | tail -n 1 > profiles/${tag}_bench_20_steps.json
+python3 bench.py --full 2> $out/bench.err | tail -n 1 > profiles/${tag}_bench.json
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2> $out/bench20.err | tail -n 1 > profiles/${tag}_bench_20_steps.json
 cat profiles/${tag}_bench.json
 fi
 cp $out/commands.log profiles/${tag}_commands.log
