@@ -111,6 +111,13 @@ struct Cursor {
 //     itself below Z = 1/t (its tilt exp(-Z^2 x/2) goes into the acceptance test) and the untruncated IG(1/Z, 1) from
 //     1/t on (a proposal beyond t is a rejected round), so cosh Z cancels and no erfc is needed (rounds 1-3: two erfc and
 //     three exp per draw, and a rejection loop of its own for the truncated inverse Gaussian).
+//   * From |z| = 96.831... on (Z > 48.4), k f exp(f t - Z) overflows and the denominator of that probability is +inf.  The
+//     right piece then has probability 0 (its mass is below 2^-1024 of the left piece's): ptail = 0 and rq = 1 exactly, as
+//     1 / (1 + inf) = 0 gives on the oracle.  pg_rcp alone does not: v_rcp_f64(inf) = 0, but its Newton step
+//     fma(-inf, 0, 1) is NaN, and a NaN ptail never picks the right piece nor flips the Michael-Schucany-Haas root (the
+//     draws came out finite, positive and biased low, ~10 % at |z| = 97).  pg_prep takes fmax(pg_rcp(den), 0), which is
+//     the reciprocal itself wherever it is positive -- below the overflow, bit for bit -- and 0 for the NaN (IEEE
+//     maxNum); one v_max_f64 per draw, no register or spill more in any kernel that inlines the draw.
 //   * The alternating series is tested in ratio form, U <= E (1 - r_1 + r_2 - ...), r_n = a_n / a_0 = (2n+1) exp(...):
 //     a_0 is never formed, and the first test -- one exp -- decides 99.4 % of the proposals.
 //   * A wave executes every branch some lane takes, so the round is written WITHOUT branches: both proposals, both
@@ -177,7 +184,8 @@ __device__ __forceinline__ PgPrep pg_prep(double Z)
     const double fz = 0.125 * kPi * kPi + 0.5 * Z * Z;
     const bool below = Z < 1.0 / kPgT;
     P.below = below ? 1 : 0;
-    P.ptail = pg_rcp(1.0 + (below ? kPgKBelow : kPgKAbove) * fz * exp(fz * kPgT - (below ? 0.0 : Z)));
+    const double den = 1.0 + (below ? kPgKBelow : kPgKAbove) * fz * exp(fz * kPgT - (below ? 0.0 : Z));
+    P.ptail = fmax(pg_rcp(den), 0.0);  // (past |z| = 96.83 pg_rcp(inf) is NaN and this 0: see above; rq = pg_rcp(1) = 1)
     P.rfz = pg_rcp(fz);
     P.mu = pg_rcp(below ? 1.0 : Z);
     P.hzz = below ? 0.5 * Z * Z : 0.0;

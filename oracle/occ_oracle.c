@@ -122,7 +122,10 @@ static double cur_norm(cursor_t *c)
  *   x <= t, Z >= 1/t  cosh Z exp(-Z^2 x/2) l(x) = 2 cosh Z e^-Z IG(x; 1/Z, 1), proposed on ALL x > 0,
  *                     a proposal beyond t rejected                 mass 2 cosh Z e^-Z
  * so the right piece is proposed with probability 1 / (1 + k f exp(f t - s)), (k, s) = (2 q0 / pi, 0) below 1/t
- * and (4 / pi, Z) from 1/t on -- cosh Z cancels: one exp, no erfc.  Round r of a draw takes Philox block r of the
+ * and (4 / pi, Z) from 1/t on -- cosh Z cancels: one exp, no erfc.  From |z| = 96.831... on (Z > 48.4) k f exp(f t - Z)
+ * overflows to +inf: the right piece's probability is then exactly 0 and 1 / (1 - ptail) exactly 1, and the draw is the
+ * left piece's alone (what 1 / (1 + inf) gives in IEEE arithmetic; written out below, and on the device, whose
+ * Newton-refined reciprocal would turn inf into NaN).  Round r of a draw takes Philox block r of the
  * sub-stream, its four 32-bit words (x0, x1, x2, x3): Ux = u01 of the 64-bit word x1:x0 (52 bits: the proposal's variate),
  * Um = (x2 + 1/2) 2^-32 (which piece), Us = (x3 + 1/2) 2^-32 (the acceptance test) -- probabilities to within 2^-33 --
  * and U2 = (Um - ptail) / (1 - ptail), which is uniform given that the left piece was picked.
@@ -189,7 +192,8 @@ static double pg1_draw_at(uint64_t key, uint32_t index, uint32_t iter, uint32_t 
     if (!(Z < 1.0e100)) return (z - z) * NAN;  /* (the device returns NaN for these too: occ_rng.hpp) */
     const double fz = 0.125 * M_PI * M_PI + 0.5 * Z * Z;
     const int below = Z < 1.0 / PG_T;
-    const double ptail = 1.0 / (1.0 + (below ? PG_K_BELOW : PG_K_ABOVE) * fz * exp(fz * PG_T - (below ? 0.0 : Z)));
+    const double den = 1.0 + (below ? PG_K_BELOW : PG_K_ABOVE) * fz * exp(fz * PG_T - (below ? 0.0 : Z));
+    const double ptail = isinf(den) ? 0.0 : 1.0 / den;  /* (past |z| = 96.83: see the header) */
     const double rfz = 1.0 / fz, mu = 1.0 / (below ? 1.0 : Z), hm = 0.5 * mu, hzz = below ? 0.5 * Z * Z : 0.0;
     const double rq = 1.0 / (1.0 - ptail);
     for (uint32_t r = 0;; ++r) {

@@ -456,13 +456,17 @@ def test_eta_solve_at_baseline_size_equals_the_reference_solver_call():
     eng.close()
 
 
-def _lockstep(oracle, prob, start, n_iter, key=KEY):
+def _lockstep(oracle, prob, start, n_iter, key=KEY, reseat=None):
+    """``reseat(it)``: a dict of state to set on both sides before iteration ``it``."""
     from occuspytial_amd._engine import Engine
     eng = Engine(prob, [key])
     orc = oracle.OracleSampler(prob, key)
     eng.set_start(0, **start)
     orc.set_start(**start)
-    for _ in range(n_iter):
+    for it in range(n_iter):
+        for name, v in (reseat(it) if reseat else {}).items():
+            eng.set(name, v)
+            orc.set(name, v)
         x0 = orc.get('xz')
         eng.step()
         orc.step()
@@ -515,6 +519,39 @@ def test_irregular_adjacency_with_long_rows_and_unsurveyed_sites(oracle, solve_m
     prob = FlatProblem(Q, W, X, y)
     assert len(prob.not_surveyed) == 35
     _lockstep(oracle, prob, _random_start(prob, 4), 4)
+
+
+def _large_predictors(prob, seed, scale=150.0):
+    """reseat(it) for _lockstep: beta and alpha drawn afresh before every iteration so that x'beta + eta and w'alpha spread
+    about 0 with standard deviation scale -- PG(1, z) arguments past |z| = 96.83, where the right piece's mass
+    1 / (1 + k f exp(f t - Z)) has an infinite denominator (occ_rng.hpp pg_prep), for a sizeable share of the sites and
+    visit rows, beside moderate ones."""
+    rng = np.random.default_rng(seed)
+    X, W = np.asarray(prob.X), np.asarray(prob.W)
+
+    def coef(M):                                      # (no intercept: centred on 0)
+        c = rng.standard_normal(M.shape[1])
+        c[0] = 0.0
+        return c * scale / (M @ c).std()
+
+    def reseat(it):
+        beta, alpha = coef(X), coef(W)
+        for lin in (X @ beta, W @ alpha):
+            assert (np.abs(lin) > 100).mean() > 0.25 and (np.abs(lin) < 50).mean() > 0.1
+        return dict(beta=beta, alpha=alpha)
+    return reseat
+
+
+@pytest.mark.parametrize('pq', [2, 12])
+def test_large_linear_predictors_lockstep(oracle, pq, solve_mode):
+    """Whole iterations in lock step with the oracle at linear predictors |x'beta + eta|, |w'alpha| of a few hundred
+    (unscaled covariates; a small tau in burn-in), the omega_b and omega_a draws held to 1e-10: p = q = 2 (fused omega_a
+    rows, q <= 8) and p = q = 12 (the generic omega_a path), both forms of the eta solve."""
+    from occuspytial_amd._problem import FlatProblem
+    from occuspytial_amd.utils import make_lattice_problem
+    Q, W, X, y, *_ = make_lattice_problem(23, 29, visits=4, p=pq, q=pq, random_state=40 + pq)
+    prob = FlatProblem(Q, W, X, y)
+    _lockstep(oracle, prob, _random_start(prob, 40 + pq), 4, reseat=_large_predictors(prob, pq))
 
 
 def test_one_covariate_and_eight_covariates(oracle):
@@ -618,6 +655,33 @@ def test_reduced_rank_lockstep_iterations_match_oracle(oracle, case):
         orc.step()
         for name, tol in (('omega_b', 1e-10), ('tau', 1e-11), ('theta', 1e-9), ('eta', 1e-9), ('beta', 1e-9), ('alpha', 1e-9)):
             assert _rel(eng.get(name), orc.get(name)) < tol, (it, name, _rel(eng.get(name), orc.get(name)))
+        assert np.array_equal(eng.get('z'), orc.get('z'))
+        for name in ('alpha', 'beta', 'tau', 'theta', 'z'):
+            eng.set(name, orc.get(name))
+    eng.close()
+
+
+def test_reduced_rank_lockstep_at_large_linear_predictors(oracle):
+    """LogitRSRGibbs on ref_rsr150_r05 with beta and alpha re-seated before every iteration so that x'beta + eta and w'alpha
+    reach a few hundred (PG(1, z) past the overflow of the right piece's mass at |z| = 96.83): omega_b and omega_a to 1e-10
+    and the rest of the iteration to the tolerances of the lock-step test above."""
+    from occuspytial_amd._engine import Engine
+    prob, start = _rsr_problem('ref_rsr150_r05')
+    reseat = _large_predictors(prob, 5)
+    eng = Engine(prob, [KEY])
+    orc = oracle.OracleSampler(prob, KEY)
+    eng.set_start(0, **start)
+    orc.set_start(**start)
+    for it in range(4):
+        for name, v in reseat(it).items():
+            eng.set(name, v)
+            orc.set(name, v)
+        eng.step()
+        orc.step()
+        for name, tol in (('omega_b', 1e-10), ('tau', 1e-11), ('theta', 1e-9), ('eta', 1e-9), ('beta', 1e-9), ('alpha', 1e-9)):
+            assert _rel(eng.get(name), orc.get(name)) < tol, (it, name, _rel(eng.get(name), orc.get(name)))
+        rows = _existing_rows(prob, orc.get('exists').astype(bool))
+        assert _rel(eng.get('omega_a')[rows], orc.get('omega_a')[rows]) < TOL['omega_a']
         assert np.array_equal(eng.get('z'), orc.get('z'))
         for name in ('alpha', 'beta', 'tau', 'theta', 'z'):
             eng.set(name, orc.get(name))

@@ -4,39 +4,47 @@ The Polya-Gamma sampler stands where the reference calls the third-party ``polya
 (``logit.py:191-193, 202-204``), which is absent from the reference tree and from the image, and the
 reference holds no known-answer test at that boundary: PG parity is UNPINNED by the reference.  What pins the
 device sampler instead: (1) the closed-form mean, variance and Laplace transform of PG(1, z) (Polson, Scott &
-Windle 2013) on a million device draws per z; (2) a KS test against the defining infinite series; (3) agreement
-with the CPU oracle's independent implementation of the same stream specification, draw by draw; (4) the draws the
-sampler's own omega_b kernel makes equal ``occ_draw``'s, so (1)-(3) speak for the kernels of the iteration.
+Windle 2013) on a million device draws per z; (2) KS tests against the defining infinite series and against the exact
+CDF (tests/_pg_theory.py); (3) agreement with the CPU oracle's independent implementation of the same stream
+specification, draw by draw; (4) the draws the sampler's own omega_b kernel makes equal ``occ_draw``'s, so (1)-(3) speak
+for the kernels of the iteration.
 """
 import numpy as np
 import pytest
 from scipy import stats
+
+from ._pg_theory import PG_BRANCH, PG_OVERFLOW, PG_SUBNORMAL, pg_cdf, pg_laplace, pg_mean, pg_var
 
 pytestmark = pytest.mark.gpu
 
 STREAM_OMEGA_B, STREAM_TAU, STREAM_ETA_SITE, STREAM_Z = 1, 2, 3, 8
 
 
-def _pg_mean(z):
-    return 0.25 if abs(z) < 1e-8 else np.tanh(z / 2) / (2 * z)
+def _ulps_around(x, k):
+    """x and its k floating-point neighbours on each side."""
+    out = [x]
+    lo = hi = x
+    for _ in range(k):
+        lo, hi = np.nextafter(lo, -np.inf), np.nextafter(hi, np.inf)
+        out += [lo, hi]
+    return np.array(sorted(out))
 
 
-def _pg_var(z):
-    return 1 / 24 if abs(z) < 1e-3 else (np.sinh(z) - z) / (4 * z ** 3 * np.cosh(z / 2) ** 2)
-
-
-@pytest.mark.parametrize('z', [0.0, 0.3, 1.0, 1.5, 1.5625, 2.5, 5.0, 12.0, -3.0, 40.0])
+@pytest.mark.parametrize('z', [0.0, 0.3, 1.0, 1.5, 1.5625, 2.5, 5.0, 12.0, -3.0, 40.0,
+                               3.125, 60.0, 96.8, 96.84, 98.0, 120.0, 300.0, 1e3, 1e4, 1e6])
 def test_device_pg1_moments_and_laplace_transform(z):
-    """tests/test_oracle_rng.py's theory checks on a million DEVICE draws (5x the oracle's sample: tighter)."""
+    """tests/test_oracle_rng.py's theory checks on a million DEVICE draws (5x the oracle's sample: tighter), over the
+    whole range of arguments: both sides of the branch at |z| = 3.125 and both sides of the overflow of the right piece's
+    mass at |z| = 96.83 (tests/_pg_theory.py: forms that stay finite at any z)."""
     from occuspytial_amd._engine import device_draw
     N = 1_000_000
     x = device_draw('pg1', np.full(N, z), key=1234 + int(abs(z) * 16), it=7, stream=STREAM_OMEGA_B)
     assert np.all(x > 0) and np.all(np.isfinite(x))
-    m, v = _pg_mean(z), _pg_var(z)
-    assert abs(x.mean() - m) < 5 * np.sqrt(v / N)
-    assert abs(x.var() - v) < 0.015 * v
+    m, v = pg_mean(z), pg_var(z)
+    assert abs(x.mean() - m) < 5 * np.sqrt(v / N), (x.mean() / m - 1)
+    assert abs(x.var() - v) < 0.015 * v, (x.var() / v - 1)
     for t in (0.5, 2.0, 10.0):
-        lt = np.cosh(z / 2) / np.cosh(np.sqrt((z * z / 2 + t) / 2))
+        lt = pg_laplace(z, t)
         e = np.exp(-t * x)
         assert abs(e.mean() - lt) < 5 * e.std() / np.sqrt(N)
 
@@ -52,12 +60,30 @@ def test_device_pg1_ks_against_the_defining_series():
         assert stats.ks_2samp(x, ref).pvalue > 1e-3
 
 
+@pytest.mark.parametrize('z', [0.0, 3.125, 6.0, 60.0, 98.0, 300.0, 1e3, 1e6])
+def test_device_pg1_ks_against_the_exact_cdf(z):
+    """One-sample KS test of 2e5 device draws against the exact CDF of PG(1, z) (tests/_pg_theory.py: the image series,
+    accurate at any z -- where the truncated series of the test above is itself biased)."""
+    from occuspytial_amd._engine import device_draw
+    x = device_draw('pg1', np.full(200_000, z), key=4321 + int(z), it=5, stream=STREAM_OMEGA_B)
+    assert stats.kstest(x, lambda v: pg_cdf(v, z)).pvalue > 1e-3
+
+
 def test_device_draws_equal_the_oracle_draw_by_draw(oracle):
     """Same stream specification, two independent implementations (HIP device functions / C): PG(1, z) over a grid
-    of z with every branch of the sampler (tail / truncated inverse Gaussian below and above 1/t, |z| up to 60),
-    gamma variates over the shapes the tau conditional meets, normals, uniforms."""
+    of z with every branch of the sampler (tail / truncated inverse Gaussian below and above 1/t), over the whole range
+    of arguments the sampler takes: |z| from subnormal to just under the 1e100 guard, the branch at |z| = 3.125 to the
+    ulp, and the stretch where the right piece's mass 1 / (1 + k f exp(f t - Z)) has a subnormal reciprocal and then an
+    infinite denominator (|z| >= 96.83: there the right piece has probability 0 and 1 / (1 - 0) = 1 exactly); gamma
+    variates over the shapes the tau conditional meets, normals, uniforms."""
     from occuspytial_amd._engine import device_draw
-    z = np.concatenate([np.linspace(-8, 8, 4001), np.array([0.0, 1e-12, 25.0, -25.0, 60.0]), np.random.default_rng(1).normal(0, 3, 20000)])
+    mag = np.concatenate([np.logspace(-300, 99.99, 1201), [5e-324, 1e-310, 2.2250738585072014e-308],
+                          _ulps_around(PG_BRANCH, 3), _ulps_around(PG_OVERFLOW, 3),
+                          np.linspace(PG_SUBNORMAL, PG_OVERFLOW, 64), _ulps_around(PG_SUBNORMAL, 3),
+                          [96.8, 97.0, 98.0, 120.0, 300.0, 1e3, 1e4, 1e6, 1e99, np.nextafter(2e100, 0.0)]])
+    assert mag.max() < 2e100                              # (pg1_draw hands back NaN from Z = |z| / 2 = 1e100 on)
+    z = np.concatenate([np.linspace(-8, 8, 4001), np.array([0.0, -0.0, 1e-12, 25.0, -25.0, 60.0]), mag, -mag,
+                        np.random.default_rng(1).normal(0, 3, 20000)])
     dev = device_draw('pg1', z, key=77, it=3, stream=STREAM_OMEGA_B)
     ref = oracle.pg1(z, key=77, it=3, stream=STREAM_OMEGA_B)
     assert np.abs(dev / ref - 1).max() < 1e-10            # same accept/reject path everywhere, libm-level differences
@@ -99,15 +125,19 @@ def test_the_samplers_omega_b_kernel_draws_what_occ_draw_draws():
     prob = FlatProblem(Q, W, X, y)
     key = 0xC0FFEE1234567
     eng = Engine(prob, [key])
-    grid = np.tile(np.array([0.0, 0.7, -1.9, 3.2, 6.5]), prob.n // 5)
+    zs = (0.0, 0.7, -1.9, 3.2, 6.5, 98.0, -98.0, 300.0, -1e3, 1e4)   # (|z| >= 96.83: the right piece's mass overflows)
+    grid = np.tile(np.array(zs), prob.n // len(zs))
     eng.set_start(0, np.zeros(2), np.zeros(2), 1.0, grid)
     it = int(eng.get('iter'))
     eng.step()                                            # its prologue draws omega_b(it) from the state just set
     om = eng.get('omega_b')
     assert np.array_equal(om, device_draw('pg1', grid, key=key, it=it, stream=STREAM_OMEGA_B))
-    for j, z in enumerate((0.0, 0.7, -1.9, 3.2, 6.5)):
-        x = om[j::5]
-        assert abs(x.mean() - _pg_mean(z)) < 5 * np.sqrt(_pg_var(z) / x.size)
+    for j, z in enumerate(zs):
+        x = om[j::len(zs)]
+        assert abs(x.mean() - pg_mean(z)) < 5 * np.sqrt(pg_var(z) / x.size), (z, x.mean() / pg_mean(z) - 1)
+        # the variance against theory, to 6 standard errors of the sample variance (its own fourth moment)
+        d = x - x.mean()
+        assert abs(x.var() - pg_var(z)) < 6 * np.sqrt(((d ** 4).mean() - x.var() ** 2) / x.size), (z, x.var() / pg_var(z) - 1)
     eng.close()
 
 
@@ -124,6 +154,12 @@ def test_device_pg1_leaves_its_loops_on_arguments_no_chain_should_produce():
     assert np.isfinite(out[~bad]).all() and (out[~bad] > 0).all()
     big = (~bad) & (np.abs(z) >= 4e3)
     assert np.allclose(out[big] * 2 * np.abs(z[big]), 1.0, rtol=0.2)   # PG(1, z) concentrates at 1 / (2 |z|)
+    # and is centred there: the mean of 1e5 draws per argument within 5 standard errors of tanh(z/2) / (2z) (plus 1e-13
+    # relative for the rounding of the draws themselves, which is all that is left of the spread at 1e99)
+    N = 100_000
+    for z in (-4e3, 1e6, 1e99):
+        x = device_draw('pg1', np.full(N, z), key=17, it=2)
+        assert abs(x.mean() - pg_mean(z)) < 5 * np.sqrt(pg_var(z) / N) + 1e-13 * pg_mean(z), (z, x.mean() / pg_mean(z) - 1)
 
 
 def test_wave_sum_forms_agree_bit_for_bit():
