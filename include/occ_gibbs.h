@@ -113,7 +113,9 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
 
 /* State of one chain by name (reference attribute names, base.py:65-82 / logit.py):
  *   alpha(q) beta(p) tau(1) eta(n) z(n) k(n) omega_b(n) omega_a(R) exists(S) xz(2n) rhs(n)
- *   minres_itn(1) iter(1); reduced-rank model: theta(m), and eta is K theta (the reference's `spatial`)
+ *   minres_itn(1) iter(1); reduced-rank model: theta(m), and eta is K theta (the reference's `spatial`);
+ *   rsr_gram(m*m), for tests: K' diag(omega_b) K of the last theta update up to 128 columns, beyond that the rows of
+ *   the factor U (Lam = U'U) right of each 32-row panel's diagonal block (the rest is working storage)
  * occ_get_state copies into out (capacity cap doubles) and stores the length in *len.
  * occ_set_state accepts alpha beta tau eta z omega_a xz iter theta (theta also sets eta = K theta); omega_b of
  * the coming iteration is then redrawn from the new state. */

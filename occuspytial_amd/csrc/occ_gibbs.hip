@@ -2888,7 +2888,11 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     else if (nm == "tau") v.assign(1, sc.tau);
     else if (nm == "minres_itn") v.assign(1, (double)sc.minres_itn_last);
     else if (nm == "iter") v.assign(1, (double)it);
-    else if (nm == "rsr_gram" && s->rsr.m > 0) {  // K' diag(omega_b) K of the last theta update (upper tiles; tests)
+    else if (nm == "rsr_gram" && s->rsr.m > 0) {
+        // tests only, m x m row-major, of the last theta update.  m <= RSR_MAX_DIM: K' diag(omega_b) K (upper 16 x 16 tiles).
+        // m > RSR_MAX_DIM: k_rsrb_assemble adds tau Qr in place and k_rsrb_step overwrites each 32-row panel's rows right of
+        // its diagonal block with the factor U (Lam = U'U); the diagonal blocks hold trailing-update values, their factors
+        // are in big_dfac.  Entries below the diagonal are undefined.
         v.resize((size_t)s->rsr.m * s->rsr.m);
         HIP_TRY(copy_on(s, v.data(), s->rsr.gram + (size_t)chain * v.size(), sizeof(double) * v.size(), hipMemcpyDeviceToHost));
     }
