@@ -87,10 +87,16 @@ struct occ_sampler {
     hipStream_t stream = nullptr;  // main: eta_init -> minres ... -> beta -> z_ob
     hipStream_t side = nullptr;    // side: omega_a -> alpha_draw -> noise(t+1), forked/joined inside the graph
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool side_enabled = true;   // false: OCC_NO_SIDE_STREAM diagnostic
-    // fork/join as event wait/record nodes inside the two graphs: two graph launches per iteration and no
-    // graph -> kernel -> graph transitions on the critical path (8-13 us each on MI355X / ROCm 7.2)
-    bool event_nodes = true;
+    Plan plan;  // the launch plan creation chose (occ_plan.hpp; event_nodes: fork/join as event nodes inside the graphs)
+    // What runs now: the fused solve's form (FORM_STEPS: one launch per MINRES step), hand-overs by device counters (Ctx::sync;
+    // only with the CU partition) or events, the main stream's CUs (> 0: partition held).  launch_sync = false: launch_kind()
+    // launches kernels that neither wait nor publish (prologue, timing loops).
+    struct Running {
+        int form = FORM_STEPS, wide = 0, main_cus = 0;  // wide: PlanForm::wide (the form's workgroups per chain: iter.nbg)
+        bool flag_sync = false;
+    } run;
+    bool fused() const { return run.form != FORM_STEPS; }
+    bool launch_sync = true;
     Ctx ctx{};               // host copy of the descriptor
     Ctx *ctx_dev = nullptr;  // the copy kernels read
     KryArgs kry{};           // by-value argument block of k_minres
@@ -99,25 +105,7 @@ struct occ_sampler {
     // scheduled like the fused ICAR iteration (two streams with flag hand-overs, or one linear graph of GRAPH_SEQ iterations).
     RsrArgs rsr{};
     std::vector<double> rsr_K_host;  // n x m, for theta -> eta on the host (start values, set_state)
-    // fused iteration (occ_iter.hpp): k_iter + k_z_ob on one stream, the eta solve persistent inside k_iter;
-    // otherwise one launch per MINRES step on the main stream and omega_a / alpha / noise on the side stream
-    bool persistent = false;
-    int iter_window = 8;     // neighbour window of k_iter: 8 (two workgroups per CU) or 16 (rows of 9-16 off-diagonals, one per CU)
-    bool xcd_local = false;  // k_iter<8, 1>: one XCD per chain, exchange through that XCD's L2 (occ_iter.hpp)
-    bool xl_candidate = false, fused_fallback = false;
-    // k_tiles (occ_tiles.hpp): the persistent solve for problems too large for k_iter -- tiles of 256 sites with their vectors
-    // in LDS, T tiles per workgroup, G workgroups per chain in eight bands of B (one per XCD).  tiles_layout: the problem has
-    // that shape (256-thread blocks, the MINRES sums added in groups of T blocks: the launch-per-step kernels follow the
-    // same order, KryArgs::group_T); tiles: k_tiles is what K_ITER launches.
-    bool tiles_layout = false, tiles = false;
-    int tiles_T = 1, tiles_G = 0, tiles_B = 0;
-    bool any_fits = false;   // the any-placement form fits the main stream's CUs (arithmetic; the residency probe decides)
-    int nbg_any = 0;         // its workgroups per chain
-    int tpb_plain = 256;     // threads per block of the launch-per-step path when no fused form applies
     int iter_flags_extra = 0;  // OR-ed into k_iter's flags (2: residency probe)
-    bool generic = false;      // more than 8 occupancy or detection covariates: the P = 0 / Q = 0 kernels (run-time p, q), launch-per-step path
-    bool beta_split = false;   // beta drawn by k_beta_draw (one wave per chain) in front of k_z_ob: many blocks, launch-per-step path
-    int zob_debug = 0;         // OCC_DEBUG_ZOB_SKIP (timing experiments with occ_profile only): 8 = no z update, 16 = no omega_b draw
     bool device_timeout = false;  // the last error was a device-side wait that gave up (not a HIP API failure)
     // state of every chain at the start of the running occ_run / occ_step (fused engines only): what the call is re-run from
     double *snap_eta = nullptr;
@@ -135,25 +123,12 @@ struct occ_sampler {
     double *inj_u = nullptr;    // [n] uniforms of occ_cond_z
     int snap_parity = 0;
     int64_t fused_fallbacks = 0;  // occ_run calls that were re-run on the launch-per-step path after a device-side time-out
-    int xl_wide = 0;         // ... with 512-thread workgroups (a chain needs more waves than its XCD's main-stream SIMDs): 1 = a scalar
-                             // wave beside seven site waves, 2 = eight site waves, the first one leads
-    int xl_nbg = 0;          // workgroups per chain of the XCD-local form
-    int xl_per_cu = 1, xl_main = 0;  // its workgroups per CU; CUs of the main stream it wants (0: no partition)
-    int xl_per_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // ... per XCD, when the XCDs that host a chain get more than the others (first entry 0: evenly)
-    int main_hot_cus = 0;    // CUs the main stream's mask holds on XCD 0 (a chain's XCD)
     bool streams_serialised = false;  // the last stream probe found the two streams NOT running beside each other: hand-overs by events
     unsigned *probe_w = nullptr;      // the stream probe's words
     unsigned long long probe_gen = 0; // g_stream_gen at the last stream probe
     int64_t stream_probes = 0, repromotions = 0;
     unsigned *sync_buf = nullptr;     // the hand-over counters (Ctx::sync points here while they are in use)
-    // What creation decided -- the form of the fused kernel, the CU partition, device-side hand-overs -- kept so that an
-    // engine that had to leave it at run time (fallback_to_launch_per_step) can come back (try_repromote)
-    struct Preferred {
-        bool valid = false, persistent = false, xcd_local = false, flag_sync = false, tiles = false;
-        int share_on = 0, main_cus = 0;
-        std::vector<uint32_t> m_main, m_side;
-    } pref;
-    bool demoted = false;             // running without device-side waits after one of them gave up
+    bool demoted = false;             // running without device-side waits after one of them gave up (back to `plan`: try_repromote)
     int promote_wait = 0, promote_backoff = 1;  // calls until the next attempt to come back; doubled after a failed one
     std::string pair_note;            // why the engine did not get the masked pair it wanted (empty: it did, or wanted none)
     // The chains' scalars as the last occ_run / occ_step read them at its end (round 3: a call of a dozen iterations was mostly
@@ -174,14 +149,7 @@ struct occ_sampler {
     bool debug_close_window = false;  // tests (occ_set_state "debug_close_window"): the NEXT call's window is opened with zero iterations on the device
     bool wedged = false;           // a host wait ran into its deadline: the streams never drained; nothing of this engine is freed or reused
     int probe_wait = 0, probe_backoff = 1;  // calls until the stream probe is asked again after a negative answer
-    int share_cum[2][9] = {};  // cumulative CUs of the main / side stream's mask over the XCDs (Ctx::share_on)
-    int main_cus = 0;        // > 0: the main stream is restricted to this many CUs, the side stream to the others
-    // stream hand-overs by device-side sequence counters (Ctx::sync) instead of event nodes: only with the CU
-    // partition.  launch_sync = false makes launch_kind() launch kernels that neither wait nor publish
-    // (prologue, timing loops).
-    bool flag_sync = false, launch_sync = true;
     int graph_parity = 0;    // fused mode: sequence parity the captured pair of iterations starts with
-    int tpb = 256;
     std::vector<void *> allocs;
     std::string err;
     int launch_rc = 0;       // first failed kernel launch since the last take_launch_rc()
@@ -223,7 +191,6 @@ namespace {
 
 // launch sequences (iterations) per captured graph on the paths that need no host decision between iterations:
 // even, so that the sequence parity is the same at every replay; a graph boundary costs several microseconds
-constexpr int TILES_GB_DEFAULT = 1;  // tiles of a k_tiles workgroup whose gathers are in flight together (T = 4, diagonal form)
 constexpr int GRAPH_SEQ = 2;  // (16 per graph measured the same: the boundary between two replays is not what costs)
 
 #define HIP_TRY(expr)                                                                              \
@@ -246,11 +213,11 @@ static std::string host_state(const occ_sampler *s)
 {
     char buf[512];
     std::snprintf(buf, sizeof(buf),
-                  "device %d, %d chains, n %d; path: persistent %d xcd_local %d tiles %d rsr_m %d; hand-overs: flag_sync %d side_enabled %d "
+                  "device %d, %d chains, n %d; path: form %d (created %d) rsr_m %d; hand-overs: flag_sync %d side_enabled %d "
                   "event_nodes %d demoted %d streams_serialised %d; main_cus %d (%s pair); parity %d graph_parity %d snap_parity %d; "
                   "mirror_ok %d clean_exit %d need_prologue %d; graph launches %lld, eager iterations %lld, fallbacks %lld",
-                  s->device, s->ctx.C, s->ctx.n, (int)s->persistent, (int)s->xcd_local, (int)s->tiles, s->rsr.m, (int)s->flag_sync, (int)s->side_enabled,
-                  (int)s->event_nodes, (int)s->demoted, (int)s->streams_serialised, s->main_cus, (s->pair && !s->pair->m_main.empty()) ? "CU-masked" : "plain",
+                  s->device, s->ctx.C, s->ctx.n, s->run.form, s->plan.form, s->rsr.m, (int)s->run.flag_sync, (int)s->plan.side_enabled,
+                  (int)s->plan.event_nodes, (int)s->demoted, (int)s->streams_serialised, s->run.main_cus, (s->pair && !s->pair->m_main.empty()) ? "CU-masked" : "plain",
                   s->parity, s->graph_parity, s->snap_parity, (int)s->mirror_ok, (int)s->clean_exit, (int)s->need_prologue,
                   (long long)s->graph_launches, (long long)s->eager_iterations, (long long)s->fused_fallbacks);
     return buf;
@@ -460,9 +427,10 @@ static dim3 shared_grid(const Ctx &c, int kid, int per_chain)
 int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
 {
     const Ctx &c = s->ctx;
-    const dim3 blk((unsigned)s->tpb), gs((unsigned)c.nb_n, (unsigned)c.C), gr((unsigned)c.nb_r, (unsigned)c.C);
-    const int tp = s->generic ? 0 : c.p, tq = s->generic ? 0 : c.q;  // template arguments: 0 = the generic (run-time) instantiation
-    const size_t lds_p = s->generic ? generic_lds_bytes(nacc(c.p), s->tpb) : 0, lds_q = s->generic ? generic_lds_bytes(nacc(c.q), s->tpb) : 0;
+    const Plan &P = s->plan;
+    const dim3 blk((unsigned)P.tpb), gs((unsigned)c.nb_n, (unsigned)c.C), gr((unsigned)c.nb_r, (unsigned)c.C);
+    const int tp = P.generic ? 0 : c.p, tq = P.generic ? 0 : c.q;  // template arguments: 0 = the generic (run-time) instantiation
+    const size_t lds_p = P.generic ? generic_lds_bytes(nacc(c.p), P.tpb) : 0, lds_q = P.generic ? generic_lds_bytes(nacc(c.q), P.tpb) : 0;
     switch (kind) {
         case K_OMEGA_B: hipLaunchKernelGGL(pick_omega_b(tp), gs, blk, 0, st, OCC_ARGS); break;
         case K_NOISE:
@@ -480,9 +448,9 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
         case K_ALPHA_DRAW: hipLaunchKernelGGL(k_alpha_draw<0>, dim3((unsigned)c.C), dim3(512), 0, st, OCC_ARGS, s->launch_sync ? 1 : 0); break;
         case K_GATE: hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, st, s->ctx_dev, s->ctx.sc); break;
         case K_RSR_GRAM:
-            if (s->rsr.m > RSR_MAX_DIM && !std::getenv("OCC_NO_GRAM32")) {  // large bases: 32 x 32 blocks of G, then the K'u workgroups alone
+            if (P.gram32) {  // large bases: 32 x 32 blocks of G, then the K'u workgroups alone
                 // (8 waves per workgroup whatever the chain count: a chain's bits do not depend on how many chains run beside it)
-                if (c.C > 1 && !std::getenv("OCC_GRAM32_ONE_CHAIN"))  // two chains per workgroup: K streamed once for both
+                if (P.gram32_pair)  // two chains per workgroup: K streamed once for both
                     hipLaunchKernelGGL((k_rsr_gram32<2, GRAM32_WAVES>), dim3((unsigned)rsr_gram32_blocks(s->rsr.m), (unsigned)((c.C + 1) / 2)), dim3(64 * GRAM32_WAVES), rsr_gram32_lds(GRAM32_WAVES), st, s->rsr, e, s->launch_sync ? 1 : 0);
                 else
                     hipLaunchKernelGGL((k_rsr_gram32<1, GRAM32_WAVES>), dim3((unsigned)rsr_gram32_blocks(s->rsr.m), (unsigned)c.C), dim3(64 * GRAM32_WAVES), rsr_gram32_lds(GRAM32_WAVES), st, s->rsr, e, s->launch_sync ? 1 : 0);
@@ -510,62 +478,48 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
             }
             break;
         case K_RSR_ETA_BETA: hipLaunchKernelGGL(pick_rsr_eta_beta(c.p), gs, blk, 0, st, s->rsr, OCC_ARGS); break;
-        case K_ITER:
-            if (s->tiles) {  // k_tiles: eight bands of B + 1 workgroups per chain (the surplus one of a band returns at once)
-                const dim3 gt(XL_SLOTS * (unsigned)(s->tiles_B + 1), (unsigned)c.C), bt(TILE);
-                const size_t lds = tiles_lds_bytes(s->tiles_T);
-                const int fl = (s->launch_sync ? 1 : 0) | s->iter_flags_extra;
-                const bool dia = s->kry.dia_n > 0;
-                void (*kt)(const IterArgs, int, int) = s->tiles_T == 1   ? (dia ? k_tiles<8, 1, 1> : k_tiles<8, 1, 0>)
-                                                       : s->tiles_T == 2 ? (dia ? k_tiles<8, 2, 1> : k_tiles<8, 2, 0>)
-                                                       : s->tiles_T == 3 ? (dia ? k_tiles<8, 3, 1> : k_tiles<8, 3, 0>)
-                                                                         : (dia ? k_tiles<8, 4, 1> : k_tiles<8, 4, 0>);
-                if (dia && s->tiles_T == 4) {  // gathers of several tiles in flight together (occ_tiles.hpp, GB); OCC_TILES_GB: developer knob
-                    const char *gb = std::getenv("OCC_TILES_GB");
-                    const int g = gb ? std::atoi(gb) : TILES_GB_DEFAULT;
-                    if (g == 2) kt = k_tiles<8, 4, 1, 2>;
-                    else if (g == 4) kt = k_tiles<8, 4, 1, 4>;
-                }
-                if (s->ext_ev0) hipExtLaunchKernelGGL(kt, gt, bt, lds, st, s->ext_ev0, s->ext_ev1, 0, s->iter, e, fl);
-                else hipLaunchKernelGGL(kt, gt, bt, lds, st, s->iter, e, fl);
-            }
-            else if (s->xcd_local) {  // eight chains (one per XCD) per launch; more chains: the next eight right behind
-                for (int base = 0; base < c.C; base += XL_SLOTS) {
-                    IterArgs ia = s->iter;
-                    ia.chain_base = base;
-                    if (s->ext_ev0 && base == 0) {  // occ_profile: the dispatch's own begin / end timestamps
-                        const int fl = (s->launch_sync ? 1 : 0) | s->iter_flags_extra;
-                        if (s->xl_wide == 1) hipExtLaunchKernelGGL((k_iter<8, 1, 1>), dim3(XL_SLOTS * (unsigned)(ia.nbg + 1)), dim3(ITER_WG_XL), 0, st, s->ext_ev0, s->ext_ev1, 0, ia, e, fl);
-                        else if (s->xl_wide == 2) hipExtLaunchKernelGGL((k_iter<8, 1, 2>), dim3(XL_SLOTS * (unsigned)(ia.nbg + 1)), dim3(ITER_WG_XL), 0, st, s->ext_ev0, s->ext_ev1, 0, ia, e, fl);
-                        else if (s->iter_window == 16) hipExtLaunchKernelGGL((k_iter<16, 1, 0>), dim3(XL_SLOTS * (unsigned)(ia.nbg + 1)), dim3(ITER_WG), 0, st, s->ext_ev0, s->ext_ev1, 0, ia, e, fl);
-                        else hipExtLaunchKernelGGL((k_iter<8, 1, 0>), dim3(XL_SLOTS * (unsigned)(ia.nbg + 1)), dim3(ITER_WG), 0, st, s->ext_ev0, s->ext_ev1, 0, ia, e, fl);
-                        continue;
-                    }
-                    if (s->xl_wide == 1) hipLaunchKernelGGL((k_iter<8, 1, 1>), dim3(XL_SLOTS * (unsigned)(ia.nbg + 1)), dim3(ITER_WG_XL), 0, st, ia, e, (s->launch_sync ? 1 : 0) | s->iter_flags_extra);
-                    else if (s->xl_wide == 2) hipLaunchKernelGGL((k_iter<8, 1, 2>), dim3(XL_SLOTS * (unsigned)(ia.nbg + 1)), dim3(ITER_WG_XL), 0, st, ia, e, (s->launch_sync ? 1 : 0) | s->iter_flags_extra);
-                    else if (s->iter_window == 16) hipLaunchKernelGGL((k_iter<16, 1, 0>), dim3(XL_SLOTS * (unsigned)(ia.nbg + 1)), dim3(ITER_WG), 0, st, ia, e, (s->launch_sync ? 1 : 0) | s->iter_flags_extra);
-                    else hipLaunchKernelGGL((k_iter<8, 1, 0>), dim3(XL_SLOTS * (unsigned)(ia.nbg + 1)), dim3(ITER_WG), 0, st, ia, e, (s->launch_sync ? 1 : 0) | s->iter_flags_extra);
-                }
-            }
-            else if (s->ext_ev0) {
-                const int fl = (s->launch_sync ? 1 : 0) | s->iter_flags_extra;
-                if (s->iter_window == 8) hipExtLaunchKernelGGL((k_iter<8, 0, 0>), dim3((unsigned)s->iter.nbg, (unsigned)c.C), dim3(ITER_WG), 0, st, s->ext_ev0, s->ext_ev1, 0, s->iter, e, fl);
-                else hipExtLaunchKernelGGL((k_iter<16, 0, 0>), dim3((unsigned)s->iter.nbg, (unsigned)c.C), dim3(ITER_WG), 0, st, s->ext_ev0, s->ext_ev1, 0, s->iter, e, fl);
-            }
-            else if (s->iter_window == 8) hipLaunchKernelGGL((k_iter<8, 0, 0>), dim3((unsigned)s->iter.nbg, (unsigned)c.C), dim3(ITER_WG), 0, st, s->iter, e, (s->launch_sync ? 1 : 0) | s->iter_flags_extra);
-            else hipLaunchKernelGGL((k_iter<16, 0, 0>), dim3((unsigned)s->iter.nbg, (unsigned)c.C), dim3(ITER_WG), 0, st, s->iter, e, (s->launch_sync ? 1 : 0) | s->iter_flags_extra);
-            break;
-        default:
-            if (s->tpb == 64) {  // 64-site slices (fused paths): 256-thread blocks, beta once per block, partial sums still per slice
-                const unsigned nb4 = (unsigned)((c.n + 255) / 256);
-                if (s->generic) hipLaunchKernelGGL((k_beta_draw<0, 0>), dim3((unsigned)c.C), dim3(256), 0, st, OCC_ARGS);
-                hipLaunchKernelGGL(pick_z_ob(tp), s->generic ? dim3(nb4 * 2, (unsigned)c.C) : shared_grid(c, 0, (int)nb4 * 2), dim3(256), 0, st, OCC_ARGS,
-                                   (s->launch_sync ? 1 : 0) | 2 | s->zob_debug);
+        case K_ITER: {
+            // k_tiles: eight bands of B + 1 workgroups per chain (the surplus one of a band returns at once); one XCD per
+            // chain: eight chains (one per XCD) per launch, more chains: the next eight right behind; any placement
+            const int fm = s->run.form, fl = (s->launch_sync ? 1 : 0) | s->iter_flags_extra, T = P.tiles_T;
+            void (*k)(const IterArgs, int, int) = nullptr;
+            dim3 grid(XL_SLOTS * (unsigned)(s->iter.nbg + 1)), bt(s->run.wide ? ITER_WG_XL : ITER_WG);
+            size_t lds = 0;
+            if (fm == FORM_TILES) {
+                k = T == 1   ? (P.dia ? k_tiles<8, 1, 1> : k_tiles<8, 1, 0>)
+                    : T == 2 ? (P.dia ? k_tiles<8, 2, 1> : k_tiles<8, 2, 0>)
+                    : T == 3 ? (P.dia ? k_tiles<8, 3, 1> : k_tiles<8, 3, 0>)
+                             : (P.dia ? k_tiles<8, 4, 1> : k_tiles<8, 4, 0>);
+                if (P.tiles_gb == 2) k = k_tiles<8, 4, 1, 2>;  // gathers of several tiles in flight together (occ_tiles.hpp, GB)
+                else if (P.tiles_gb == 4) k = k_tiles<8, 4, 1, 4>;
+                grid = dim3(XL_SLOTS * (unsigned)(P.tiles_B + 1), (unsigned)c.C), bt = dim3(TILE), lds = tiles_lds_bytes(T);
+            } else if (fm == FORM_XCD) {
+                if (s->run.wide == 1) k = k_iter<8, 1, 1>;
+                else if (s->run.wide == 2) k = k_iter<8, 1, 2>;
+                else k = P.iter_window == 16 ? k_iter<16, 1, 0> : k_iter<8, 1, 0>;
             } else {
-                if (s->generic) hipLaunchKernelGGL((k_beta_draw<0, 0>), dim3((unsigned)c.C), dim3(256), 0, st, OCC_ARGS);
-                else if (s->beta_split) hipLaunchKernelGGL(OCC_PICK_P(k_beta_draw, c.p), dim3((unsigned)c.C), dim3(64), 0, st, OCC_ARGS);
+                k = P.iter_window == 8 ? k_iter<8, 0, 0> : k_iter<16, 0, 0>;
+                grid = dim3((unsigned)s->iter.nbg, (unsigned)c.C);
+            }
+            for (int base = 0; base < (fm == FORM_XCD ? c.C : 1); base += XL_SLOTS) {
+                IterArgs ia = s->iter;  // (chain_base 0 but for the XCD-local form's further launches of eight)
+                ia.chain_base = base;
+                if (s->ext_ev0 && base == 0) hipExtLaunchKernelGGL(k, grid, bt, lds, st, s->ext_ev0, s->ext_ev1, 0, ia, e, fl);  // occ_profile: the dispatch's own begin / end timestamps
+                else hipLaunchKernelGGL(k, grid, bt, lds, st, ia, e, fl);
+            }
+            break;
+        }
+        default:
+            if (P.tpb == 64) {  // 64-site slices (fused paths): 256-thread blocks, beta once per block, partial sums still per slice
+                const unsigned nb4 = (unsigned)((c.n + 255) / 256);
+                if (P.generic) hipLaunchKernelGGL((k_beta_draw<0, 0>), dim3((unsigned)c.C), dim3(256), 0, st, OCC_ARGS);
+                hipLaunchKernelGGL(pick_z_ob(tp), P.generic ? dim3(nb4 * 2, (unsigned)c.C) : shared_grid(c, 0, (int)nb4 * 2), dim3(256), 0, st, OCC_ARGS,
+                                   (s->launch_sync ? 1 : 0) | 2 | P.zob_flags);
+            } else {
+                if (P.generic) hipLaunchKernelGGL((k_beta_draw<0, 0>), dim3((unsigned)c.C), dim3(256), 0, st, OCC_ARGS);
+                else if (P.beta_split) hipLaunchKernelGGL(OCC_PICK_P(k_beta_draw, c.p), dim3((unsigned)c.C), dim3(64), 0, st, OCC_ARGS);
                 hipLaunchKernelGGL(pick_z_ob(tp), dim3((unsigned)c.nb_n * 2, (unsigned)c.C), blk, 0, st, OCC_ARGS,
-                                   (s->launch_sync ? 1 : 0) | s->zob_debug | (s->beta_split ? 4 : 0));
+                                   (s->launch_sync ? 1 : 0) | P.zob_flags | (P.beta_split ? 4 : 0));
             }
             break;
     }
@@ -597,7 +551,7 @@ int take_launch_rc(occ_sampler *s)
 int read_scalars(occ_sampler *s, std::vector<ChainScalars> &h)
 {
     h.resize(s->ctx.C);
-    if (s->flag_sync) WAIT_TRY(s->side);  // its last k_noise is not waited for by the main stream
+    if (s->run.flag_sync) WAIT_TRY(s->side);  // its last k_noise is not waited for by the main stream
     if (!s->pin_sc) HIP_TRY(hipHostMalloc((void **)&s->pin_sc, 2 * sizeof(ChainScalars) * h.size(), hipHostMallocDefault));
     ChainScalars *back = s->pin_sc + h.size();
     HIP_TRY(hipMemcpyAsync(back, s->ctx.sc, sizeof(ChainScalars) * h.size(), hipMemcpyDeviceToHost, s->stream));
@@ -692,7 +646,7 @@ int eager_sequence(occ_sampler *s)
     }
     LAUNCH(s, s->stream, K_OMEGA_A, e);
     LAUNCH(s, s->stream, K_NOISE, e, 1);
-    if (s->persistent) {
+    if (s->fused()) {
         LAUNCH(s, s->stream, K_ITER, e);
     } else {
         LAUNCH(s, s->stream, K_ETA_INIT, e);
@@ -755,7 +709,7 @@ int build_graph(occ_sampler *s, int cap)
     WAIT_TRY(s->stream);
     destroy_head(s);
     int rc;
-    if (s->rsr.m > 0 && !s->flag_sync) {  // reduced-rank model: GRAPH_SEQ iterations (alternating parity) on the main stream
+    if (s->rsr.m > 0 && !s->run.flag_sync) {  // reduced-rank model: GRAPH_SEQ iterations (alternating parity) on the main stream
         const bool old_sync = s->launch_sync;
         s->launch_sync = false;
         HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
@@ -767,7 +721,7 @@ int build_graph(occ_sampler *s, int cap)
         s->krylov_cap = 0;
         return take_launch_rc(s);
     }
-    if (s->flag_sync) {
+    if (s->run.flag_sync) {
         // GRAPH_SEQ sequences (alternating parity) per graph and stream, no event nodes: the kernels hand over through
         // the device counters of Ctx::sync.  The counters restart with the capture: the main stream's sequence numbers
         // live in two words indexed by the sequence PARITY, and a capture that starts with the other parity than the last
@@ -809,7 +763,7 @@ int build_graph(occ_sampler *s, int cap)
     }
     for (int e = 0; e < 2; ++e) {
         HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-        if (s->persistent) {
+        if (s->fused()) {
             LAUNCH(s, s->stream, K_ITER, e);
         } else {
             LAUNCH(s, s->stream, K_ETA_INIT, e);
@@ -817,7 +771,7 @@ int build_graph(occ_sampler *s, int cap)
             LAUNCH(s, s->stream, K_BETA_PARTIAL, e, cap + 3);
         }
         HIP_TRY(hipStreamEndCapture(s->stream, &s->head_graph[e]));
-        if (s->event_nodes) {  // ... -> wait(side chain of this iteration) -> k_z_ob -> record
+        if (s->plan.event_nodes) {  // ... -> wait(side chain of this iteration) -> k_z_ob -> record
             hipGraphNode_t leaf, wait, rec;
             if ((rc = graph_leaf(s, s->head_graph[e], &leaf))) return rc;
             HIP_TRY(hipGraphAddEventWaitNode(&wait, s->head_graph[e], &leaf, 1, s->ev_side[e]));
@@ -830,7 +784,7 @@ int build_graph(occ_sampler *s, int cap)
         }
         HIP_TRY(hipGraphInstantiate(&s->head[e], s->head_graph[e], nullptr, nullptr, 0));
         if (s->tail[e]) continue;
-        if (s->event_nodes) {  // wait(previous k_z_ob) -> side chain -> record
+        if (s->plan.event_nodes) {  // wait(previous k_z_ob) -> side chain -> record
             hipGraphNode_t leaf, wait, rec;
             HIP_TRY(hipGraphCreate(&s->tail_graph[e], 0));
             HIP_TRY(hipGraphAddEventWaitNode(&wait, s->tail_graph[e], nullptr, 0, s->ev_z[e ^ 1]));
@@ -862,7 +816,7 @@ int build_graph(occ_sampler *s, int cap)
 int enqueue_sequence(occ_sampler *s)
 {
     const int e = s->parity;
-    if (s->flag_sync) {  // GRAPH_SEQ sequences on each stream
+    if (s->run.flag_sync) {  // GRAPH_SEQ sequences on each stream
         HIP_TRY(hipGraphLaunch(s->tail[0], s->side));
         HIP_TRY(hipGraphLaunch(s->head[0], s->stream));
         return OCC_OK;
@@ -871,13 +825,13 @@ int enqueue_sequence(occ_sampler *s)
         HIP_TRY(hipGraphLaunch(s->head[0], s->stream));
         return OCC_OK;
     }
-    if (s->event_nodes) {  // the graphs carry their own waits and records
+    if (s->plan.event_nodes) {  // the graphs carry their own waits and records
         HIP_TRY(hipGraphLaunch(s->tail[e], s->side));
         HIP_TRY(hipGraphLaunch(s->head[e], s->stream));
         s->parity ^= 1;
         return OCC_OK;
     }
-    if (s->side_enabled) {
+    if (s->plan.side_enabled) {
         HIP_TRY(hipStreamWaitEvent(s->side, s->ev_z[e ^ 1], 0));
         HIP_TRY(hipGraphLaunch(s->tail[e], s->side));
         HIP_TRY(hipEventRecord(s->ev_side[e], s->side));
@@ -888,7 +842,7 @@ int enqueue_sequence(occ_sampler *s)
         HIP_TRY(hipGraphLaunch(s->head[e], s->stream));
     }
     LAUNCH(s, s->stream, K_Z_OB, e);
-    if (s->side_enabled) HIP_TRY(hipEventRecord(s->ev_z[e], s->stream));
+    if (s->plan.side_enabled) HIP_TRY(hipEventRecord(s->ev_z[e], s->stream));
     s->parity ^= 1;
     return take_launch_rc(s);
 }
@@ -1108,26 +1062,30 @@ void drop_pair(occ_sampler *s)
     adopt_pair(s, nullptr);
 }
 
-// The two streams without a CU partition (the pooled unmasked pair of the device).
+// The two streams without a CU partition (the pooled unmasked pair of the device), in place of any the engine holds.
 int create_plain_streams(occ_sampler *s)
 {
+    drop_pair(s);
     std::string why;
     StreamPair *p = acquire_pair(s->device, {}, {}, &why);
     if (!p) return set_error(s, OCC_E_HIP, why.c_str());
     adopt_pair(s, p);
-    s->main_cus = 0;
-    s->flag_sync = false;
-    s->ctx.share_on = 0;
+    s->run.main_cus = s->ctx.share_on = 0;
+    s->run.flag_sync = false;
     return OCC_OK;
 }
 
-// ICAR model on the launch-per-step path: no CU partition, hand-overs by events (the device-counter hand-overs and
-// the partition exist for the fused kernel's sake).
-int demote_streams(occ_sampler *s, bool also_reduced_rank = false)
+// Down to one launch per MINRES step: no CU partition, hand-overs by events (both exist for the fused kernel's sake).  Creation
+// when no fused form is resident, the run-time fallback and a failed return to the plan (try_repromote) all come here.
+int drop_to_launch_per_step(occ_sampler *s)
 {
-    if ((s->rsr.m > 0 && !also_reduced_rank) || s->main_cus == 0) return OCC_OK;
-    drop_pair(s);
-    return create_plain_streams(s);
+    int rc;
+    s->run.form = FORM_STEPS;
+    if (s->run.main_cus > 0 && (rc = create_plain_streams(s))) return rc;
+    s->run.flag_sync = false;
+    s->ctx.sync = s->iter.sync = s->rsr.sync = nullptr;
+    HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
+    return OCC_OK;
 }
 
 // Do the engine's two streams run BESIDE each other?  The device-side hand-overs presume it.  A kernel on the side stream
@@ -1174,12 +1132,20 @@ int stream_probe(occ_sampler *s, bool *beside)
     return OCC_OK;
 }
 
-// CUs of the main stream with k_tiles: half the device (whole shader engines per XCD), OCC_TILES_MAIN_CUS overrides
-int tiles_main_cus(int ncu)
+// The plan knobs (occ_plan.hpp), read once per engine at its creation
+PlanOptions plan_options_from_env()
 {
-    int m = (ncu / 64) * 32;
-    if (const char *e = std::getenv("OCC_TILES_MAIN_CUS")) m = std::max(32, std::min((std::atoi(e) / 32) * 32, ncu - 32));
-    return m;
+    auto set = [](const char *name) { return std::getenv(name) != nullptr; };
+    auto num = [](const char *name, int unset) { const char *v = std::getenv(name); return v ? std::atoi(v) : unset; };
+    PlanOptions o;
+    o.no_persistent = set("OCC_NO_PERSISTENT"); o.no_tiles = set("OCC_NO_TILES"); o.no_xcd_local = set("OCC_NO_XCD_LOCAL"); o.no_scalar_wave = set("OCC_NO_SCALAR_WAVE");
+    o.no_xcd_shares = set("OCC_NO_XCD_SHARES"); o.no_beta_split = set("OCC_NO_BETA_SPLIT"); o.no_side_stream = set("OCC_NO_SIDE_STREAM"); o.no_dia = set("OCC_NO_DIA");
+    o.stream_events = set("OCC_STREAM_EVENTS"); o.event_sync = set("OCC_EVENT_SYNC"); o.skip_residency_probe = set("OCC_DEBUG_SKIP_RESIDENCY_PROBE");
+    o.no_gram32 = set("OCC_NO_GRAM32"); o.gram32_one_chain = set("OCC_GRAM32_ONE_CHAIN"); o.break_handover = set("OCC_DEBUG_BREAK_HANDOVER");
+    o.force_tiles = num("OCC_FORCE_TILES", KNOB_UNSET); o.tiles_main_cus = num("OCC_TILES_MAIN_CUS", KNOB_UNSET); o.cold_cus = num("OCC_DEBUG_COLD_CUS", KNOB_UNSET);
+    o.cu_split = num("OCC_CU_SPLIT", KNOB_UNSET); o.main_share = num("OCC_DEBUG_MAIN_SHARE", KNOB_UNSET); o.surplus_last = num("OCC_DEBUG_SURPLUS_LAST", 0);
+    o.zob_skip = num("OCC_DEBUG_ZOB_SKIP", 0); o.tiles_gb = num("OCC_TILES_GB", TILES_GB_DEFAULT);
+    return o;
 }
 
 // k_tiles' invariant between launches (canaries in record buffer 1): established at creation and
@@ -1194,7 +1160,7 @@ int tiles_reset(occ_sampler *s)
     return OCC_OK;
 }
 
-// Residency probe of the fused iteration kernel in the form s->xcd_local / xl_wide / iter_window / iter.nbg select:
+// Residency probe of the fused iteration kernel in the form s->run and iter.nbg select:
 // k_iter itself (flags bit 1) -- same grid, registers and LDS as the real launch -- runs ONE barrier among the
 // workgroups of every chain with a short time limit, three times.  It passes exactly when every chain's workgroups
 // are resident together on the CUs the main stream owns (and, one XCD per chain, share that XCD: a flag carries its
@@ -1220,9 +1186,10 @@ int residency_probe(occ_sampler *s, bool *ok)
     HIP_TRY(fill_on(s, s->ctx.bar, 0, sizeof(unsigned) * (size_t)s->ctx.C * BAR_STRIDE));
     HIP_TRY(fill_on(s, s->ctx.claim, 0, sizeof(unsigned) * (size_t)s->ctx.C * 16));
     if ((rc = read_scalars(s, h))) return rc;
-    for (auto &sc : h) { sc.bar_base = s->tiles ? sc.bar_base + 16u : 0u; sc.err = 0; }  // (k_tiles: the tag of its tagged records, never reused)
+    const bool tiles = s->run.form == FORM_TILES;
+    for (auto &sc : h) { sc.bar_base = tiles ? sc.bar_base + 16u : 0u; sc.err = 0; }  // (k_tiles: the tag of its tagged records, never reused)
     if ((rc = write_scalars(s, h))) return rc;
-    return s->tiles ? tiles_reset(s) : OCC_OK;
+    return tiles ? tiles_reset(s) : OCC_OK;
 }
 
 }  // namespace
@@ -1487,7 +1454,6 @@ static int build_layout(occ_sampler *s, const occ_problem *pb, HostLayout &L)
 static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, const uint64_t *keys)
 {
     if (!keys || n_chains < 1) return set_error(s, OCC_E_BADARG, "bad keys / n_chains");
-    struct { int rsr_dim; } pbv = {L.rsr_dim}, *pb = &pbv;  // (the body below reads pb->rsr_dim)
     DeviceLease lease = lease_device(s->device);  // probes and uploads run on streams other engines of the device share
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
@@ -1499,9 +1465,6 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
         HIP_TRY(hipEventCreateWithFlags(&s->ev_z[e], hipEventDisableTiming | hipEventReleaseToDevice));
         HIP_TRY(hipEventCreateWithFlags(&s->ev_side[e], hipEventDisableTiming | hipEventReleaseToDevice));
     }
-    s->side_enabled = std::getenv("OCC_NO_SIDE_STREAM") == nullptr;
-    if (const char *zd = std::getenv("OCC_DEBUG_ZOB_SKIP")) s->zob_debug = (std::atoi(zd) & 3) << 3;
-    s->event_nodes = s->side_enabled && std::getenv("OCC_STREAM_EVENTS") == nullptr;  // diagnostic: fork/join by stream calls
 
     const int n = L.n, S = L.S, R = L.R, p = L.p, q = L.q, C = n_chains;
     Ctx &c = s->ctx;
@@ -1518,226 +1481,39 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
     const uint8_t *dia_mask_dev = nullptr;
     int rc;
 
-    // ---- launch geometry: one site (or visit row) per thread; enough blocks to spread over the CUs
-    int tpb = 256;
-    while (tpb > 64 && ((long long)n * C + tpb - 1) / tpb < 512) tpb >>= 1;
-    // Fused iteration kernel (occ_iter.hpp): every workgroup of every chain must be resident at once (at most two
-    // per CU) and a matrix row must fit the register-resident neighbour window.  Its partial sums are per
-    // 64-site slice, so the other kernels use 64-thread blocks too.
-    {
-        int wmax = 0;
-        for (int sl = 0; sl < nslice; ++sl) wmax = std::max(wmax, (sell_ptr[sl + 1] - sell_ptr[sl]) / 64);
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, s->device));
-        const int nbg = (n + ITER_WG - 1) / ITER_WG;
-        s->iter.nbg = nbg;
-        // (k_iter's 240 VGPRs allow two of its workgroups per CU: 8 chains at 100x100 run 210 us per iteration that way
-        // against 251 us with one launch per MINRES step)
-        s->iter_window = wmax <= 8 ? 8 : 16;
-        const int wg_per_cu = s->iter_window == 8 ? 2 : 1;  // 255 and ~400 VGPRs
-        s->generic = p > MAXC || q > MAXC;
-        const bool fused_shape = pb->rsr_dim == 0 && wmax <= 16 && !s->generic;
-        const bool fused_ok = !std::getenv("OCC_NO_PERSISTENT") && fused_shape;
-        s->persistent = fused_ok && (long long)nbg * C <= (long long)wg_per_cu * prop.multiProcessorCount;
-        // k_tiles for what k_iter cannot hold (more sites than 64 workgroups of 512 per chain, more workgroups than two per
-        // CU): T tiles of 256 sites per workgroup, four workgroups per CU (128 registers; LDS: 16 KB per tile) on HALF the
-        // device -- the Polya-Gamma kernels of the side stream need the other half at these sizes (1.25 M draws per
-        // iteration at 500x500) -- and at most 512 workgroups per chain (a band's records: one per lane).  The
-        // LAYOUT (256-thread blocks, sums grouped by T) is decided by the shape alone, so that OCC_NO_PERSISTENT=1 and a
-        // run-time fallback run the launch-per-step kernels in the same summation order: same bits.
-        {
-            const int ntile = (n + TILE - 1) / TILE, main_t = tiles_main_cus(prop.multiProcessorCount);
-            const char *ft = std::getenv("OCC_FORCE_TILES");  // tests: 1 .. 4 = that many tiles per workgroup whatever the size
-            int T = 0;
-            for (int t : {1, 2, 4, 3}) {  // the fewest tiles per workgroup whose workgroups are all resident (4 before 3: it keeps its registers)
-                if (T != 0) break;
-                const int g = (ntile + t - 1) / t;
-                if ((long long)C * g <= (long long)tiles_wg_per_cu(t) * main_t && g <= 512) T = t;
-            }
-            if (ft && std::atoi(ft) >= 1 && std::atoi(ft) <= 4) T = std::atoi(ft);
-            // (beyond 64 workgroups of 512 sites per chain k_iter only has its any-placement form, every exchange a round trip to
-            // the memory side: 250x250 x 1 chain 186 us per iteration against 123 with tiles, x 2 chains 322 / 161, 350x350
-            // 299 / 152; at 150x150 x 2 chains k_iter still wins, 117 / 136)
-            const bool big = n > XL_MAX_WG * ITER_WG_XL && ((long long)nbg * C > 2LL * prop.multiProcessorCount || (long long)n * C >= 50000);
-            s->tiles_layout = fused_shape && wmax <= 8 && T > 0 && !std::getenv("OCC_NO_TILES") && (big || ft != nullptr);
-            if (s->tiles_layout) {
-                s->tiles_T = T;
-                s->tiles_G = (ntile + T - 1) / T;
-                s->tiles_B = (s->tiles_G + XL_SLOTS - 1) / XL_SLOTS;
-                s->persistent = false;  // (k_iter's forms are out: decided below)
-            }
-        }
-        // one XCD per chain (k_iter<8, 1, *>); candidates -- the probe below decides.  Per XCD the main stream has 20 CUs
-        // (24 for larger lattices, 28 when few chains leave the side stream little to do), whole shader engines'
-        // worth: an XCD deals a chain's workgroups round-robin over its four shader engines, so its CUs in the mask
-        // must be a multiple of four (26 workgroups on 26 CUs per XCD dead-locked, on 28 they run).
-        //   A  256-thread workgroups, one per CU            nbg <= 20
-        //   B  512-thread workgroups (scalar wave + 448 sites), one per CU: ceil(n / 448) <= 28 CUs of the chain's XCD
-        //   C  256-thread workgroups, two per CU            nbg <= 64 (partition of at most 24 CUs per XCD, else none)
-        // Form B with fewer than eight chains: only the XCDs that host a chain need that many CUs -- the others give the
-        // main stream fewer, so that the side stream keeps its share of the device (4 chains at 100x100: 24 CUs on four
-        // XCDs, 16 on the other four: 160 + 96 as before).
-        {
-            const int ncu = prop.multiProcessorCount, nbg512 = (n + ITER_SITES_SW - 1) / ITER_SITES_SW;  // (one wave of the 512 threads owns no sites)
-            const int nbg512p = (n + ITER_WG_XL - 1) / ITER_WG_XL;                                        // (eight site waves)
-            const int base = (ncu * 5 / 64) * 8;  // 160 of 256
-            // (more than eight chains: launches of eight, one behind the other -- 16 chains at 100x100 then run 2 x 60 us where
-            // the launch-per-step path took 374)
-            // (rows of 9-16 off-diagonals -- the irregular graph of BASELINE config 5 -- take the one-XCD form too, in its
-            // 256-thread, one-workgroup-per-CU shape (round 3): every step's exchange through one L2 instead of the memory side)
-            const bool xl_any = fused_ok && C <= 8 * XL_SLOTS && !std::getenv("OCC_NO_XCD_LOCAL");
-            const bool xl_ok = xl_any && s->iter_window == 8;
-            auto part = [&](int per_xcd) { return std::max(32 * ((per_xcd + 3) / 4), base); };
-            s->xl_candidate = false;
-            for (int x = 0; x < XL_SLOTS; ++x) s->xl_per_xcd[x] = 0;
-            const int need = 4 * ((nbg512 + 3) / 4), hot = std::min(C, XL_SLOTS), per_xcd = ncu / XL_SLOTS;
-            int wide_main = 0, wide_xcd[XL_SLOTS];
-            if (need <= per_xcd - 4) {  // the hot XCDs leave the side stream one CU per shader engine at least
-                int rest = need;
-                if (hot < XL_SLOTS) {
-                    rest = 4 * (int)std::lround((double)(base - hot * need) / (4.0 * (XL_SLOTS - hot)));
-                    rest = std::max(8, std::min(rest, need));
-                    while (hot * need + (XL_SLOTS - hot) * rest > ncu - 96 && rest > 8) rest -= 4;  // the side stream keeps 96 CUs
-                    if (const char *cc = std::getenv("OCC_DEBUG_COLD_CUS")) rest = std::max(4, std::min(std::atoi(cc) / 4 * 4, need));  // developer knob
+    // ---- the launch plan (occ_plan.hpp): what the shape asks for, the streams, then what the partition granted allows
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, s->device));
+    PlanShape shape;
+    shape.n = n; shape.rows = R; shape.chains = C; shape.p = p; shape.q = q; shape.rsr_dim = L.rsr_dim; shape.dia = !dia_off.empty();
+    for (int sl = 0; sl < nslice; ++sl) shape.wmax = std::max(shape.wmax, (sell_ptr[sl + 1] - sell_ptr[sl]) / 64);
+    Plan &P = s->plan;
+    std::string why;
+    if (!plan_wanted(shape, prop.multiProcessorCount, plan_options_from_env(), &P, &why)) return set_error(s, OCC_E_BADARG, why.c_str());
+    s->iter.nbg = P.nbg;
+    // the pooled pair with that partition; a runtime that cannot mask CUs, or a device at its cap of masked pairs: plain streams
+    if (P.partition) {
+        if (StreamPair *pr = acquire_pair(s->device, P.m_main, P.m_side, &s->pair_note)) {
+            adopt_pair(s, pr);
+            s->pair_note.clear();
+            s->run.main_cus = P.nmain, s->run.flag_sync = !P.opt.event_sync;  // (OCC_EVENT_SYNC diagnostic: hand-overs by event nodes)
+            if (s->run.flag_sync) {
+                bool beside = true;
+                if ((rc = stream_probe(s, &beside))) return rc;
+                if (!beside) {  // hand-overs by event nodes (ICAR) / everything on one stream (reduced-rank model); asked again at
+                    s->run.flag_sync = false, s->streams_serialised = true;  // the head of the next call (refresh_paths)
+                    s->probe_wait = s->probe_backoff = 1;
                 }
-                for (int x = 0; x < XL_SLOTS; ++x) { wide_xcd[x] = x < hot ? need : rest; wide_main += wide_xcd[x]; }
             }
-            if (xl_any && nbg <= base / XL_SLOTS) {
-                s->xl_candidate = true; s->xl_wide = 0; s->xl_nbg = nbg; s->xl_per_cu = 1; s->xl_main = base;
-            } else if (xl_ok && nbg512 <= 64 && wide_main > 0 && wide_main <= ncu - 96 && hot <= 5 && !std::getenv("OCC_NO_SCALAR_WAVE")) {
-                // (the scalar wave's seventh of the sites costs CUs: taken while the side stream keeps its 96 and most of them on
-                // XCDs without a chain -- 100x100: 4 chains 70.0 us per iteration against 80.0 with eight site waves, 5 chains
-                // 80.3 / 81.8, 6 chains 99.3 / 82.3; 8 chains on 192 + 64 CUs 121.7 / 92.5, side-stream bound)
-                s->xl_candidate = true; s->xl_wide = 1; s->xl_nbg = nbg512; s->xl_per_cu = 1; s->xl_main = wide_main;
-                for (int x = 0; x < XL_SLOTS; ++x) s->xl_per_xcd[x] = wide_xcd[x];
-            } else if (xl_ok && nbg512p <= 64 && (part(nbg512p) <= ncu - 64 || (part(nbg512p) <= ncu - 32 && C <= 2))) {
-                s->xl_candidate = true; s->xl_wide = 2; s->xl_nbg = nbg512p; s->xl_per_cu = 1; s->xl_main = part(nbg512p);
-            } else if (xl_ok && nbg <= 64 && nbg <= 2 * (ncu / XL_SLOTS)) {
-                s->xl_candidate = true; s->xl_wide = 0; s->xl_nbg = nbg; s->xl_per_cu = 2;
-                s->xl_main = part((nbg + 1) / 2) <= ncu - 64 ? part((nbg + 1) / 2) : 0;  // 0: no CU partition
-            }
-        }
-        s->fused_fallback = s->persistent;  // what holds without the XCD-local form
-        s->persistent = s->persistent || s->xl_candidate;
-        if (s->tiles_layout) {
-            s->xl_candidate = false;
-            s->fused_fallback = false;
-            s->tiles = fused_ok;
-            s->persistent = s->tiles;
-            tpb = TILE;
-        }
-        s->tpb_plain = tpb;  // what the launch-per-step path takes when no fused form applies
-        if (s->persistent && !s->tiles) tpb = 64;
-    }
-    // ---- streams.  The main stream carries the critical path (the eta solve); omega_a / alpha / noise of the
-    // same iteration run beside it on the side stream.  With the fused iteration kernel the two streams get
-    // DISJOINT sets of CUs: k_iter's workgroups are latency-bound with one wave per SIMD, and Polya-Gamma waves
-    // sharing their SIMDs (long quarter-rate instructions, another kernel's code in the instruction cache) cost
-    // the solve more than the side work gains from the extra CUs (100x100, 4 chains: 143 -> 127 us per
-    // iteration).  A mask of N bits enables N CUs spread evenly over the 8 XCDs (tools/xcc_probe3.hip), and the
-    // k_iter grid is dealt round-robin over the XCDs: a multiple of 8 keeps one workgroup per CU.
-    {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, s->device));
-        const int ncu = prop.multiProcessorCount;
-        // at least 5/8 of the device for the main stream: k_z_ob's Polya-Gamma draws run there too
-        int nmain = std::max(((s->iter.nbg * C + 7) / 8) * 8, (ncu * 5 / 64) * 8);
-        // more workgroups than the partition can give one CU each: the 8-wide window runs two per CU
-        if (nmain > ncu - 32 && s->iter_window == 8) nmain = std::max((((s->iter.nbg * C + 1) / 2 + 7) / 8) * 8, (ncu * 5 / 64) * 8);
-        // one XCD per chain (decided for good by the probe below): a chain's nbg workgroups share the nmain / 8 CUs of
-        // one XCD whatever the number of chains, two per CU
-        if (s->xl_candidate) nmain = s->xl_main;  // 0: none
-        if (pb->rsr_dim > 0) nmain = ((ncu * 3 / 4) / 8) * 8;  // reduced-rank model: k_rsr_gram's tiles and the theta solve
-        // ... with a large basis (the m x m system in device memory: k_rsr_gram32, k_rsrb_*) the main sequence is milliseconds of
-        // device-filling kernels and the side sequence 30 us: no partition, one stream (round 3 kept 64 CUs for a side stream
-        // whose k_omega_a spent 4.3 ms of a 4.4 ms iteration waiting at its gate)
-        if (pb->rsr_dim > RSR_MAX_DIM) nmain = 0;
-        if (s->tiles) nmain = tiles_main_cus(ncu);             // k_tiles: eight tiles per CU
-        if (const char *split = std::getenv("OCC_CU_SPLIT")) {  // developer knob: CUs of the main stream; 0: no masks
-            nmain = std::atoi(split);
-            // a partition is cut in whole shader engines per XCD (see above): multiples of 32 CUs, both streams non-empty
-            if (nmain != 0 && (nmain < 32 || nmain % 32 != 0 || nmain > ncu - 32))
-                return set_error(s, OCC_E_BADARG, "OCC_CU_SPLIT must be 0 (no partition) or a multiple of 32 that leaves the side stream at least 32 CUs");
-        }
-        if ((s->persistent || pb->rsr_dim > 0) && s->side_enabled && nmain >= 8 && nmain <= ncu - 32) {
-            // bit i of a mask is CU i / 8 of XCD i % 8: the main stream takes the first per[x] CUs of XCD x
-            std::vector<uint32_t> m_main((ncu + 31) / 32, 0u), m_side((ncu + 31) / 32, 0u);
-            int per[XL_SLOTS];
-            for (int x = 0; x < XL_SLOTS; ++x) per[x] = (s->xl_candidate && s->xl_per_xcd[0] > 0 && !std::getenv("OCC_CU_SPLIT")) ? s->xl_per_xcd[x] : nmain / XL_SLOTS;
-            for (int i = 0; i < ncu; ++i) (i / XL_SLOTS < per[i % XL_SLOTS] ? m_main : m_side)[i / 32] |= 1u << (i % 32);
-            s->main_hot_cus = per[0];
-            // the XCDs' shares of each stream's CUs (tile_of_block_shared), when they differ; the tile tables follow
-            // once the block sizes are known
-            c.share_on = 0;
-            s->share_cum[0][0] = s->share_cum[1][0] = 0;
-            for (int x = 0; x < XL_SLOTS; ++x) {
-                s->share_cum[0][x + 1] = s->share_cum[0][x] + per[x];
-                s->share_cum[1][x + 1] = s->share_cum[1][x] + (ncu / XL_SLOTS - per[x]);
-                if (per[x] != per[0]) c.share_on = 1;
-            }
-            if (std::getenv("OCC_NO_XCD_SHARES")) c.share_on = 0;
-            // the pooled pair with this partition; a runtime that cannot mask CUs, or a device that has its share of masked
-            // pairs already, gets the unpartitioned streams below
-            if (StreamPair *pr = acquire_pair(s->device, m_main, m_side, &s->pair_note)) {
-                adopt_pair(s, pr);
-                s->pair_note.clear();
-                s->pref.m_main = m_main;
-                s->pref.m_side = m_side;
-                s->main_cus = nmain;
-                s->flag_sync = std::getenv("OCC_EVENT_SYNC") == nullptr;  // diagnostic: hand-overs by event nodes
-                if (s->flag_sync) {
-                    bool beside = true;
-                    if ((rc = stream_probe(s, &beside))) return rc;
-                    if (!beside) {
-                        s->flag_sync = false;  // hand-overs by event nodes (ICAR) / everything on one stream (reduced-rank model)
-                        s->streams_serialised = true;
-                        s->probe_wait = s->probe_backoff = 1;  // (asked again at the head of the next call: refresh_paths)
-                    }
-                }
-            } else {
-                c.share_on = 0;
-                if (std::getenv("OCC_VERBOSE")) std::fprintf(stderr, "[occ] no CU partition for this engine: %s\n", s->pair_note.c_str());
-            }
-        }
-        if (s->main_cus == 0 && (rc = create_plain_streams(s))) return rc;
-    }
-    // ---- which form of the fused iteration kernel?  Arithmetic first (workgroups against the CUs the main stream
-    // owns); the RESIDENCY PROBE further down -- k_iter itself, one barrier per chain -- has the last word.
-    {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, s->device));
-        const int cus = s->main_cus > 0 ? s->main_cus : prop.multiProcessorCount;
-        s->any_fits = s->fused_fallback && (long long)s->iter.nbg * C <= (long long)(s->iter_window == 8 ? 2 : 1) * cus;
-        s->nbg_any = s->iter.nbg;
-        const bool trust = std::getenv("OCC_DEBUG_SKIP_RESIDENCY_PROBE") != nullptr;  // tests of the run-time fallback
-        const int hot_cus = s->main_cus > 0 ? s->main_hot_cus : prop.multiProcessorCount / XL_SLOTS;  // CUs of a chain's XCD
-        if (!trust && s->xl_candidate && s->xl_nbg > s->xl_per_cu * hot_cus) s->xl_candidate = false;
-        if (s->tiles && !trust && (long long)s->tiles_G * C > (long long)tiles_wg_per_cu(s->tiles_T) * cus) s->tiles = false;
-        s->persistent = s->xl_candidate || s->any_fits || s->tiles;
-        if (!s->persistent) {
-            tpb = s->tpb_plain;
-            if (pb->rsr_dim == 0 && (rc = demote_streams(s))) return rc;
+        } else if (std::getenv("OCC_VERBOSE")) {
+            std::fprintf(stderr, "[occ] no CU partition for this engine: %s\n", s->pair_note.c_str());
         }
     }
-    s->tpb = tpb;
-    c.nb_n = (n + tpb - 1) / tpb;
-    s->beta_split = tpb != 64 && c.nb_n >= 128 && !std::getenv("OCC_NO_BETA_SPLIT");
-    c.nb_r = std::max(1, (R + tpb - 1) / tpb);
-    if (c.share_on) {  // tiles of the device-filling kernels per XCD, in proportion to the CUs of their stream
-        const int per_chain[3] = {tpb == 64 ? 2 * ((n + 255) / 256) : 2 * c.nb_n, c.nb_r, (n + 255) / 256}, which[3] = {0, 1, 1};
-        c.surplus_last = 0;
-        if (const char *sl = std::getenv("OCC_DEBUG_SURPLUS_LAST")) c.surplus_last = std::atoi(sl);
-        if (const char *cw = std::getenv("OCC_DEBUG_MAIN_SHARE")) {  // developer knob: weight of an XCD without a chain in k_z_ob's shares
-            const int w = std::atoi(cw), hot = std::min(C, XL_SLOTS);
-            for (int x = hot; x < XL_SLOTS; ++x) s->share_cum[0][x + 1] = s->share_cum[0][x] + w;
-        }
-        for (int k = 0; k < 3; ++k) {
-            const long long T = (long long)per_chain[k] * C, W = s->share_cum[which[k]][8];
-            c.tile_most[k] = 0;
-            for (int x = 0; x <= XL_SLOTS; ++x) c.tile_first[k][x] = (int)(T * s->share_cum[which[k]][x] / W);
-            for (int x = 0; x < XL_SLOTS; ++x) c.tile_most[k] = std::max(c.tile_most[k], c.tile_first[k][x + 1] - c.tile_first[k][x]);
-        }
-    }
+    plan_granted(P, s->run.main_cus > 0);
+    if (P.main_cus == 0 && (rc = create_plain_streams(s))) return rc;  // (no partition, or no fused form fits the one granted)
+    c.share_on = P.share_on; c.nb_n = P.nb_n; c.nb_r = P.nb_r; c.surplus_last = P.surplus_last;
+    std::memcpy(c.tile_first, P.tile_first, sizeof(c.tile_first));
+    std::memcpy(c.tile_most, P.tile_most, sizeof(c.tile_most));
 
     // ---- device memory ------------------------------------------------------------------------------
     if ((rc = upload(s, &c.sell_ptr, sell_ptr, "sell_ptr"))) return rc;
@@ -1794,18 +1570,18 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
     c.claim = nullptr;
     c.iter_clock = nullptr;
     c.sync = nullptr;
-    if (s->main_cus > 0) {  // a CU partition: the counters exist even while events hand over (the mode can change at run time)
+    if (s->run.main_cus > 0) {  // a CU partition: the counters exist even while events hand over (the mode can change at run time)
         if ((rc = dev_alloc(s, &s->sync_buf, (size_t)SYNC_WORDS))) return rc;
-        if (std::getenv("OCC_DEBUG_BREAK_HANDOVER")) {  // tests of the run-time fallback: the side stream never announces its noise
+        if (P.opt.break_handover) {  // tests of the run-time fallback: the side stream never announces its noise
             const unsigned one = 1u;
             HIP_TRY(copy_on(s, s->sync_buf + SYNC_DEBUG, &one, sizeof(one), hipMemcpyHostToDevice));
         }
     }
-    if (s->flag_sync) {
+    if (s->run.flag_sync) {
         c.sync = s->sync_buf;
         s->iter.sync = c.sync;
     }
-    if (s->tiles) {
+    if (P.tiles) {
         const size_t npad = ((size_t)n + 7) / 8 * 8;  // (a chain's exchange buffer starts on a 128-byte line)
         s->iter.tiles_npad = (int)npad;
         if ((rc = dev_alloc(s, &s->iter.tex[0], 3 * (size_t)C * npad))) return rc;  // (one allocation: k_tiles addresses the three through one descriptor)
@@ -1813,10 +1589,10 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
         s->iter.tex[2] = s->iter.tex[0] + 2 * (size_t)C * npad;
         if ((rc = dev_alloc(s, &s->iter.trec, (size_t)C * c.nb_n * 4))) return rc;
         if ((rc = dev_alloc(s, &s->iter.tband, (size_t)C * 3 * XL_SLOTS * 4))) return rc;
-        if ((rc = dev_alloc(s, &s->iter.tflag, (size_t)C * 2 * s->tiles_G))) return rc;
-        s->iter.tiles_T = s->tiles_T; s->iter.tiles_G = s->tiles_G; s->iter.tiles_B = s->tiles_B;
+        if ((rc = dev_alloc(s, &s->iter.tflag, (size_t)C * 2 * P.tiles_G))) return rc;
+        s->iter.tiles_T = P.tiles_T; s->iter.tiles_G = P.tiles_G; s->iter.tiles_B = P.tiles_B;
     }
-    if (s->persistent) {
+    if (P.persistent) {
         if ((rc = dev_alloc(s, &c.iter_clock, 4))) return rc;
         s->iter.clock = c.iter_clock;
         if ((rc = dev_alloc(s, &c.bar, (size_t)C * BAR_STRIDE))) return rc;
@@ -1835,11 +1611,11 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
     {
         KryArgs &k = s->kry;
         k.n = c.n; k.nb_n = c.nb_n; k.ell_w = c.ell_w; k.maxiter = c.maxiter;
-        k.group_T = s->tiles_layout ? s->tiles_T : 1;
-        k.group_B = s->tiles_layout ? s->tiles_B : 0;
+        k.group_T = P.tiles_layout ? P.tiles_T : 1;
+        k.group_B = P.tiles_layout ? P.tiles_B : 0;
         k.dia_n = 0;
         k.dia_mask = nullptr;
-        if (!dia_off.empty() && !std::getenv("OCC_NO_DIA")) {
+        if (P.dia) {
             k.dia_n = (int)dia_off.size();
             for (size_t d = 0; d < dia_off.size(); ++d) { k.dia_off[d] = dia_off[d]; k.dia_val[d] = dia_val[d]; }
             k.dia_mask = dia_mask_dev;
@@ -1860,46 +1636,26 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
         t.tau_rate = c.tau_rate; t.tau_shape = c.tau_shape;
         t.C = c.C; t.p = c.p; t.q = c.q;
     }
-    // ---- fused iteration kernel: which form is RESIDENT?  One XCD per chain first, then any placement, else one launch
-    // per MINRES step (the partial sums stay per 64-site slice: the three paths return the same bits).
-    if (s->persistent) {
-        const bool trust = std::getenv("OCC_DEBUG_SKIP_RESIDENCY_PROBE") != nullptr;  // tests of the run-time fallback
-        bool ok = false;
-        if (s->tiles) {
-            ok = trust;
-            if (trust) { if ((rc = tiles_reset(s))) return rc; }
-            else if ((rc = residency_probe(s, &ok))) return rc;
-            if (std::getenv("OCC_VERBOSE"))
-                std::fprintf(stderr, "[occ] k_tiles: %d tiles per workgroup, %d workgroups per chain in bands of %d per XCD, main stream %d CUs: %s\n",
-                             s->tiles_T, s->tiles_G, s->tiles_B, s->main_cus, ok ? "resident" : "NOT resident");
-            if (!ok) s->tiles = false;
+    // ---- fused iteration kernel: which form is RESIDENT?  The ladder in order, each form asked by the residency probe (same bits)
+    for (const PlanForm &f : P.ladder) {
+        s->iter.nbg = f.nbg;
+        if (f.form == FORM_STEPS) {  // (after fused forms that are not resident: down to it)
+            if (P.persistent && (rc = drop_to_launch_per_step(s))) return rc;
+            if (P.persistent && std::getenv("OCC_VERBOSE")) std::fprintf(stderr, "[occ] the fused iteration kernel is not resident on this device: one launch per MINRES step\n");
+            break;
         }
-        if (s->xl_candidate) {
-            s->xcd_local = true;
-            s->iter.nbg = s->xl_nbg;
-            ok = trust;
-            if (!trust && (rc = residency_probe(s, &ok))) return rc;
-            if (std::getenv("OCC_VERBOSE"))
-                std::fprintf(stderr, "[occ] one XCD per chain: %d workgroups of %d threads per chain, main stream %d CUs (%d on a chain's XCD): %s\n",
-                             s->xl_nbg, s->xl_wide ? ITER_WG_XL : ITER_WG, s->main_cus, s->main_hot_cus, ok ? "resident" : "NOT resident");
-            if (!ok) s->xcd_local = false;
-        }
-        if (!ok && s->any_fits) {
-            s->xl_wide = 0;
-            s->iter.nbg = s->nbg_any;
-            ok = trust;
-            if (!trust && (rc = residency_probe(s, &ok))) return rc;
-        }
-        if (!ok) {
-            s->persistent = false;
-            s->iter.nbg = s->nbg_any;
-            if ((rc = demote_streams(s))) return rc;
-            if (!s->flag_sync) { c.sync = nullptr; s->iter.sync = nullptr; }
-            if (std::getenv("OCC_VERBOSE")) std::fprintf(stderr, "[occ] the fused iteration kernel is not resident on this device: one launch per MINRES step\n");
-        }
+        s->run.form = f.form, s->run.wide = f.wide;
+        bool ok = P.opt.skip_residency_probe;  // tests of the run-time fallback
+        if ((rc = ok ? (f.form == FORM_TILES ? tiles_reset(s) : OCC_OK) : residency_probe(s, &ok))) return rc;
+        if (std::getenv("OCC_VERBOSE"))
+            std::fprintf(stderr, "[occ] fused form %d: %d workgroups of %d threads per chain, main stream %d CUs (%d on a chain's XCD): %s\n", f.form,
+                         f.form == FORM_TILES ? P.tiles_G : f.nbg, f.form == FORM_TILES ? TILE : f.wide ? ITER_WG_XL : ITER_WG, s->run.main_cus,
+                         P.main_hot_cus, ok ? "resident" : "NOT resident");
+        if (ok) break;
     }
-    if (pb->rsr_dim > 0) {  // reduced-rank model
-        const int m = pb->rsr_dim;
+    plan_settle(P, s->run.form);  // what the engine comes back to after a run-time fallback (try_repromote)
+    if (L.rsr_dim > 0) {  // reduced-rank model
+        const int m = L.rsr_dim;
         const std::vector<double> &Kh = L.Kh, &Qh = L.Qh, &Eh = L.Eh;
         std::vector<double> Kth((size_t)m * n);
         for (int i = 0; i < n; ++i)
@@ -1947,15 +1703,6 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
     // (the engine's own two streams, not hipDeviceSynchronize: other engines' pooled streams are not this call's business)
     WAIT_TRY(s->stream);
     WAIT_TRY(s->side);
-    // what the engine comes back to after a run-time fallback (try_repromote)
-    s->pref.valid = true;
-    s->pref.persistent = s->persistent;
-    s->pref.xcd_local = s->xcd_local;
-    s->pref.tiles = s->tiles;
-    s->pref.flag_sync = s->main_cus > 0 && s->sync_buf != nullptr && std::getenv("OCC_EVENT_SYNC") == nullptr;
-    s->pref.share_on = c.share_on;
-    s->pref.main_cus = s->main_cus;
-    if (s->main_cus == 0) { s->pref.m_main.clear(); s->pref.m_side.clear(); }
     return OCC_OK;
 }
 
@@ -2530,10 +2277,10 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
         for (int64_t i = 0; i < n_iter; ++i)
             if ((rc = eager_sequence(s))) return rc;
         done_min = n_iter;
-    } else if (s->persistent && !s->flag_sync) {
+    } else if (s->fused() && !s->run.flag_sync) {
         if (!s->head[0] && (rc = build_graph(s, 0))) return rc;  // the solve is one launch: nothing to calibrate
         if (s->need_prologue && (rc = launch_prologue(s))) return rc;
-    } else if (s->flag_sync || s->rsr.m > 0) {
+    } else if (s->run.flag_sync || s->rsr.m > 0) {
         if (s->need_prologue && (rc = launch_prologue(s))) return rc;
         // the solve is one launch: nothing to calibrate.  The captured pair of iterations starts with one
         // sequence parity: an odd number of stepped iterations since the capture is realigned by one more step.
@@ -2561,8 +2308,8 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
         if ((rc = launch_prologue(s))) return rc;
     }
     // the first side chain waits for "the previous k_z_ob": everything enqueued so far
-    if (done_min < n_iter && s->side_enabled && !s->flag_sync && s->rsr.m == 0) HIP_TRY(hipEventRecord(s->ev_z[s->parity ^ 1], s->stream));
-    const int64_t seq_per_enqueue = (s->flag_sync || s->rsr.m > 0) ? GRAPH_SEQ : 1;
+    if (done_min < n_iter && s->plan.side_enabled && !s->run.flag_sync && s->rsr.m == 0) HIP_TRY(hipEventRecord(s->ev_z[s->parity ^ 1], s->stream));
+    const int64_t seq_per_enqueue = (s->run.flag_sync || s->rsr.m > 0) ? GRAPH_SEQ : 1;
 
     // (iteration, launches spent on a carried solve) of every chain after the previous batch: every sequence moves every
     // unfinished chain -- by one iteration, or by the captured launches of a solve it carries on (Ctl::koff)
@@ -2623,7 +2370,7 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
         }
         // re-size the captured solve from the solves since the last decision: mean + 2.5 sd
         const unsigned long long ds = solves - s->seen_solves;
-        if (!force && !s->persistent && s->rsr.m == 0 && ds >= 32 && done_min < n_iter) {
+        if (!force && !s->fused() && s->rsr.m == 0 && ds >= 32 && done_min < n_iter) {
             const double mean = (double)(tot - s->seen_tot) / ds;
             const double var = std::max(0.0, (double)(sq - s->seen_sq) / ds - mean * mean);
             const int want = std::max(4, (int)std::ceil(mean + 2.5 * std::sqrt(var)));
@@ -2671,11 +2418,11 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
 // mode and go with it; the counters restart from zero (a consistent state: sequence 0, whatever the parity).
 static int set_handover(occ_sampler *s, bool flags)
 {
-    if (s->flag_sync == flags) return OCC_OK;
+    if (s->run.flag_sync == flags) return OCC_OK;
     WAIT_TRY(s->stream);
     WAIT_TRY(s->side);
     destroy_graph(s);
-    s->flag_sync = flags;
+    s->run.flag_sync = flags;
     s->ctx.sync = flags ? s->sync_buf : nullptr;
     s->iter.sync = s->ctx.sync;
     s->rsr.sync = s->ctx.sync;
@@ -2695,18 +2442,10 @@ static int fallback_to_launch_per_step(occ_sampler *s)
         std::fprintf(stderr, "[occ] %s -- re-running the call without hand-overs between the streams%s\n",
                      s->err.c_str(), s->rsr.m > 0 ? "" : ", one launch per MINRES step");
     destroy_graph(s);
-    s->persistent = false;
-    s->xcd_local = false;
-    s->tiles = false;
     s->device_timeout = false;
     s->launch_rc = OCC_OK;
     int rc;
-    if ((rc = demote_streams(s, true))) return rc;
-    s->flag_sync = false;
-    c.sync = nullptr;
-    s->iter.sync = nullptr;
-    s->rsr.sync = nullptr;
-    HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
+    if ((rc = drop_to_launch_per_step(s))) return rc;
     HIP_TRY(copy_on(s, c.eta, s->snap_eta, sizeof(double) * Cn, hipMemcpyDeviceToDevice));
     HIP_TRY(copy_on(s, c.z, s->snap_z, Cn, hipMemcpyDeviceToDevice));
     HIP_TRY(copy_on(s, c.Xv, s->snap_x, sizeof(double2) * Cn, hipMemcpyDeviceToDevice));
@@ -2730,9 +2469,9 @@ static int fallback_to_launch_per_step(occ_sampler *s)
 // bitwise equal and omega_b / the noise of the coming iteration are where the next kernel looks for them: nothing else to do.
 static int try_repromote(occ_sampler *s)
 {
-    if (!s->demoted || !s->pref.valid || std::getenv("OCC_NO_REPROMOTE")) return OCC_OK;
+    if (!s->demoted || std::getenv("OCC_NO_REPROMOTE")) return OCC_OK;
     if (--s->promote_wait > 0) return OCC_OK;
-    Ctx &c = s->ctx;
+    const Plan &P = s->plan;
     int rc;
     auto stay = [&](const char *why) {
         if (std::getenv("OCC_VERBOSE")) std::fprintf(stderr, "[occ] not back on the fused path: %s\n", why);
@@ -2743,47 +2482,31 @@ static int try_repromote(occ_sampler *s)
     WAIT_TRY(s->stream);
     WAIT_TRY(s->side);
     destroy_graph(s);
-    if (s->pref.main_cus > 0) {  // the CU partition
+    if (P.main_cus > 0) {  // the CU partition
         std::string why;
-        StreamPair *pr = acquire_pair(s->device, s->pref.m_main, s->pref.m_side, &why);
+        StreamPair *pr = acquire_pair(s->device, P.m_main, P.m_side, &why);
         if (!pr) return stay(why.c_str());
         drop_pair(s);
         adopt_pair(s, pr);
-        s->main_cus = s->pref.main_cus;
-        c.share_on = s->pref.share_on;
+        s->run.main_cus = P.main_cus, s->ctx.share_on = P.share_on;
     }
-    auto back_out = [&](const char *why) -> int {  // to the demoted state
-        s->persistent = false;
-        s->xcd_local = false;
-        s->tiles = false;
-        int brc = demote_streams(s, true);
-        if (brc) return brc;
-        s->flag_sync = false;
-        c.sync = nullptr; s->iter.sync = nullptr; s->rsr.sync = nullptr;
-        HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
-        return stay(why);
-    };
     bool ok = true;
-    if (s->pref.flag_sync) {
-        if ((rc = stream_probe(s, &ok))) return rc;
-        if (!ok) return back_out("the two streams do not run beside each other");
+    if (P.flag_sync && (rc = stream_probe(s, &ok))) return rc;
+    const char *why = "the two streams do not run beside each other";
+    if (ok) {
+        s->run.form = P.form;
+        HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
+        if (s->fused() && (rc = residency_probe(s, &ok))) return rc;
+        why = "the fused kernel's workgroups are not resident together";
     }
-    s->persistent = s->pref.persistent;
-    s->xcd_local = s->pref.xcd_local;
-    s->tiles = s->pref.tiles;
-    HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
-    if (s->pref.persistent) {
-        if ((rc = residency_probe(s, &ok))) return rc;
-        if (!ok) return back_out("the fused kernel's workgroups are not resident together");
-    }
-    s->flag_sync = false;
-    if ((rc = set_handover(s, s->pref.flag_sync))) return rc;
-    if (!s->pref.flag_sync) HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
+    if (!ok) return (rc = drop_to_launch_per_step(s)) ? rc : stay(why);
+    if ((rc = set_handover(s, P.flag_sync))) return rc;
+    if (!P.flag_sync) HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
     s->streams_serialised = false;
     s->demoted = false;
     s->promote_backoff = 1;
     s->repromotions += 1;
-    if (std::getenv("OCC_VERBOSE")) std::fprintf(stderr, "[occ] back on the paths creation chose (fused kernel %d, device-side hand-overs %d)\n", (int)s->persistent, (int)s->flag_sync);
+    if (std::getenv("OCC_VERBOSE")) std::fprintf(stderr, "[occ] back on the paths creation chose (fused kernel %d, device-side hand-overs %d)\n", (int)s->fused(), (int)s->run.flag_sync);
     return OCC_OK;
 }
 
@@ -2795,8 +2518,8 @@ static int refresh_paths(occ_sampler *s)
     if ((rc = try_repromote(s))) return rc;
     // (a negative answer is not for life either: asked again after 1, 2, 4 ... 64 calls, as try_repromote does)
     bool ask = s->probe_gen != g_stream_gen.load();
-    if (!ask && s->streams_serialised && !s->flag_sync && --s->probe_wait <= 0) ask = true;
-    if (!s->demoted && s->main_cus > 0 && s->sync_buf && s->pref.flag_sync && ask) {
+    if (!ask && s->streams_serialised && !s->run.flag_sync && --s->probe_wait <= 0) ask = true;
+    if (!s->demoted && s->run.main_cus > 0 && s->sync_buf && s->plan.flag_sync && ask) {
         bool beside = true;
         if ((rc = stream_probe(s, &beside))) return rc;
         s->streams_serialised = !beside;
@@ -2814,7 +2537,7 @@ int occ_step(occ_sampler *s)
     HIP_TRY(hipSetDevice(s->device));
     int rc;
     if ((rc = refresh_paths(s))) return rc;
-    const bool fused = (s->persistent && s->rsr.m == 0) || s->flag_sync;  // paths with device-side waits: re-run without them if one gives up
+    const bool fused = (s->fused() && s->rsr.m == 0) || s->run.flag_sync;  // paths with device-side waits: re-run without them if one gives up
     s->device_timeout = false;
     rc = step_impl(s, fused);
     if (rc == OCC_E_HIP && fused && s->device_timeout) {
@@ -2833,7 +2556,7 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
     HIP_TRY(hipSetDevice(s->device));
     int rc;
     if ((rc = refresh_paths(s))) return rc;
-    const bool fused = (s->persistent && s->rsr.m == 0) || s->flag_sync;
+    const bool fused = (s->fused() && s->rsr.m == 0) || s->run.flag_sync;
     s->device_timeout = false;
     rc = run_impl(s, n_iter, burnin, out_alpha, out_beta, out_tau, fused);
     if (rc == OCC_E_HIP && fused && s->device_timeout) {
@@ -2998,15 +2721,15 @@ int occ_get_stats(occ_sampler *s, occ_stats *out)
     out->last_run_ms = s->last_run_ms;
     out->n_blocks_sites = s->ctx.nb_n;
     out->n_blocks_rows = s->ctx.nb_r;
-    out->threads_per_block = s->tpb;
+    out->threads_per_block = s->plan.tpb;
     out->n_chains = s->ctx.C;
-    out->persistent_solve = s->persistent ? (s->tiles ? 3 : s->xcd_local ? 2 : 1) : 0;
-    out->solve_workgroups = s->tiles ? s->tiles_G : s->iter.nbg;
-    out->main_stream_cus = s->main_cus;
+    out->persistent_solve = s->run.form;
+    out->solve_workgroups = s->run.form == FORM_TILES ? s->plan.tiles_G : s->iter.nbg;
+    out->main_stream_cus = s->run.main_cus;
     out->fused_fallbacks = (int32_t)s->fused_fallbacks;
     out->repromotions = (int32_t)s->repromotions;
     out->stream_probes = (int32_t)s->stream_probes;
-    out->handover_mode = s->flag_sync ? 2 : 1;
+    out->handover_mode = s->run.flag_sync ? 2 : 1;
     {
         int masked = 0, plain = 0, idle = 0;
         count_pairs(s->device, &masked, &plain, &idle);
@@ -3069,14 +2792,14 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     // the MINRES iterations they ran show in occ_get_stats (krylov_total, solves) before and after.
     counts[K_ITER] = 0;
     total_us[K_ITER] = 0.0;
-    if (s->persistent) {
+    if (s->fused()) {
         std::vector<ChainScalars> h0;
         if ((rc = read_scalars(s, h0))) return rc;
         if (s->need_prologue && (rc = launch_prologue(s))) return rc;
         // hand-overs as in occ_run: device counters, or stream events; OCC_EAGER_ONLY (counter collection
         // serialises kernels): everything on the main stream in the reference's order, no hand-overs at all
-        const bool one_stream = std::getenv("OCC_EAGER_ONLY") != nullptr || !s->side_enabled;
-        const bool flags = s->flag_sync && !one_stream;
+        const bool one_stream = std::getenv("OCC_EAGER_ONLY") != nullptr || !s->plan.side_enabled;
+        const bool flags = s->run.flag_sync && !one_stream;
         const bool ev = !flags && !one_stream;
         const bool old_sync = s->launch_sync;
         s->launch_sync = flags;
@@ -3260,7 +2983,7 @@ int occ_cond_tau(occ_sampler *s, int32_t chain, double gamma_variate, double *ta
     if (rc) return rc;
     const Ctx &c = s->ctx;
     const int e = s->parity;
-    const dim3 blk((unsigned)s->tpb), gs((unsigned)c.nb_n, 1u);
+    const dim3 blk((unsigned)s->plan.tpb), gs((unsigned)c.nb_n, 1u);
     hipLaunchKernelGGL(k_quad, gs, blk, 0, s->stream, OCC_CARGS);
     hipLaunchKernelGGL(k_eta_init<1>, gs, blk, 0, s->stream, OCC_CARGS);  // tau = (1 / rate) gamma; its right-hand side is not used
     ChainScalars sc;
@@ -3285,7 +3008,7 @@ int occ_cond_eta(occ_sampler *s, int32_t chain, const double *omega_b, const dou
     if ((rc = copy_in(s, c.enorm[it & 1] + co, eps_site, n))) return rc;
     if ((rc = copy_in(s, c.uprior[it & 1] + co, prior_term, n))) return rc;
     const int e = s->parity;
-    const dim3 blk((unsigned)s->tpb), gs((unsigned)c.nb_n, 1u);
+    const dim3 blk((unsigned)s->plan.tpb), gs((unsigned)c.nb_n, 1u);
     hipLaunchKernelGGL(k_eta_init<1>, gs, blk, 0, s->stream, OCC_CARGS);
     int k_last = 0;
     Slot slot;
@@ -3302,7 +3025,7 @@ int occ_cond_eta(occ_sampler *s, int32_t chain, const double *omega_b, const dou
         if (slot.done) { k_last = k; break; }
         if ((long long)k > c.maxiter + 3) return set_error(s, OCC_E_MINRES, "MINRES solver did not converge!");
     }
-    hipLaunchKernelGGL(pick_beta_partial(s->generic ? 0 : c.p), gs, blk, s->generic ? generic_lds_bytes(nacc(c.p), s->tpb) : 0, s->stream, OCC_CARGS, k_last);
+    hipLaunchKernelGGL(pick_beta_partial(s->plan.generic ? 0 : c.p), gs, blk, s->plan.generic ? generic_lds_bytes(nacc(c.p), s->plan.tpb) : 0, s->stream, OCC_CARGS, k_last);
     ChainScalars sc;
     if ((rc = cond_end(s, chain, &sc))) return rc;
     if ((rc = copy_out(s, rhs_out, c.rhs + co, n))) return rc;
@@ -3330,9 +3053,9 @@ int occ_cond_beta(occ_sampler *s, int32_t chain, const double *omega_b, const do
     const size_t n = (size_t)c.n, co = (size_t)chain * n;
     if ((rc = copy_in(s, c.omega_b[it & 1] + co, omega_b, n))) return rc;
     const int e = s->parity;
-    const dim3 blk((unsigned)s->tpb), gs((unsigned)c.nb_n, 1u);
-    if (s->generic) {
-        hipLaunchKernelGGL(k_beta_sums<0>, gs, blk, generic_lds_bytes(nacc(c.p), s->tpb), s->stream, OCC_CARGS);
+    const dim3 blk((unsigned)s->plan.tpb), gs((unsigned)c.nb_n, 1u);
+    if (s->plan.generic) {
+        hipLaunchKernelGGL(k_beta_sums<0>, gs, blk, generic_lds_bytes(nacc(c.p), s->plan.tpb), s->stream, OCC_CARGS);
         hipLaunchKernelGGL((k_beta_draw<0, 1>), dim3(1), dim3(256), 0, s->stream, OCC_CARGS);
     } else {
         hipLaunchKernelGGL(OCC_PICK_P(k_beta_sums, c.p), gs, blk, 0, s->stream, OCC_CARGS);
@@ -3356,9 +3079,9 @@ int occ_cond_alpha(occ_sampler *s, int32_t chain, const double *omega_a, const d
     const Ctx &c = s->ctx;
     if ((rc = copy_in(s, c.omega_a + (size_t)chain * c.R, omega_a, (size_t)c.R))) return rc;
     const int e = s->parity;
-    const dim3 blk((unsigned)s->tpb), gr((unsigned)c.nb_r, 1u);
+    const dim3 blk((unsigned)s->plan.tpb), gr((unsigned)c.nb_r, 1u);
 #define OCC_OMEGA_A_INJ(q) ((q) == 1 ? k_omega_a<1, 1> : (q) == 2 ? k_omega_a<2, 1> : (q) == 3 ? k_omega_a<3, 1> : (q) == 4 ? k_omega_a<4, 1> : (q) == 5 ? k_omega_a<5, 1> : (q) == 6 ? k_omega_a<6, 1> : (q) == 7 ? k_omega_a<7, 1> : k_omega_a<8, 1>)
-    if (s->generic) hipLaunchKernelGGL((k_omega_a<0, 1>), gr, blk, generic_lds_bytes(nacc(c.q), s->tpb), s->stream, OCC_CARGS, 0);
+    if (s->plan.generic) hipLaunchKernelGGL((k_omega_a<0, 1>), gr, blk, generic_lds_bytes(nacc(c.q), s->plan.tpb), s->stream, OCC_CARGS, 0);
     else hipLaunchKernelGGL(OCC_OMEGA_A_INJ(c.q), gr, blk, 0, s->stream, OCC_CARGS, 0);
     hipLaunchKernelGGL(k_alpha_draw<1>, dim3(1), dim3(512), 0, s->stream, OCC_CARGS, 0);
     ChainScalars sc;
@@ -3380,8 +3103,8 @@ int occ_cond_z(occ_sampler *s, int32_t chain, const double *u, double *z_out)
     const size_t n = (size_t)c.n;
     if ((rc = copy_in(s, s->inj_u, u, n))) return rc;
     const int e = s->parity;
-    const dim3 blk((unsigned)s->tpb), gs((unsigned)c.nb_n, 1u);
-    hipLaunchKernelGGL(OCC_PICK_P(k_cond_beta_z, s->generic ? 0 : c.p), gs, blk, 0, s->stream, OCC_CARGS);
+    const dim3 blk((unsigned)s->plan.tpb), gs((unsigned)c.nb_n, 1u);
+    hipLaunchKernelGGL(OCC_PICK_P(k_cond_beta_z, s->plan.generic ? 0 : c.p), gs, blk, 0, s->stream, OCC_CARGS);
     if ((rc = cond_end(s, chain, nullptr))) return rc;
     if (z_out) {
         std::vector<uint8_t> z(n);

@@ -46,14 +46,9 @@ namespace occ {
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
-constexpr int ITER_WG = 256;                    // threads per workgroup of k_iter, any placement
-constexpr int ITER_WG_XL = 512;                 // ... one XCD per chain: two waves per SIMD IN one workgroup (see k_iter)
-constexpr int ITER_SITES_SW = 448;              // ... of which the first wave owns no sites (the scalar wave): seven site waves
 constexpr unsigned ITER_SPIN_LIMIT = 1u << 21;  // polls (about a microsecond each) before a barrier gives up
 constexpr unsigned ITER_PROBE_SPIN_LIMIT = 1u << 14;  // ... in the residency probe at creation (flags bit 1 of k_iter)
 constexpr int BAR_STRIDE = 64;                  // unsigned words per chain in IterArgs::bar: the counter, or one flag per workgroup
-constexpr int XL_MAX_WG = 64;                   // workgroups per chain of an XCD-local launch (one flag per lane of the polling wave)
-constexpr int XL_SLOTS = 8;                     // chains of an XCD-local launch = XCDs the grid's x dimension walks over
 
 // Developer builds (-DOCC_SOLVE_STAMPS, `make stamps`) record s_memtime at a few points of every MINRES step of
 // chain 0 / workgroup 0; the product build compiles the hooks away.

@@ -39,18 +39,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "occ_plan.hpp"
 #include "occ_rng.hpp"
 
 namespace occ {
 
-constexpr int MAXC = 8;                             // covariates of the register-resident fast path (templates on P, Q)
 constexpr int NACC_MAX = MAXC * (MAXC + 1) / 2 + MAXC;  // 44
 constexpr int MAXG = 32;                            // OCC_MAX_COVARIATES: the generic path (P = 0 instantiations, run-time p and q)
 constexpr int NACC_G = MAXG * (MAXG + 1) / 2 + MAXG;    // 560
 constexpr int NSLOT = 4;
 constexpr int MAX_WAVES = 4;  // threads per block <= 256
-
-__host__ __device__ constexpr int nacc(int d) { return d * (d + 1) / 2 + d; }
 
 // MINRES scalar state of one chain; slot s is written by step s and read by step s+1.
 #ifndef OCC_SLOT_ALIGN

@@ -1,0 +1,50 @@
+// occ_plan_capi.cpp -- the planner (occ_plan.hpp) behind a C entry point for tests/test_plan_cpu.py (ctypes).  Test
+// infrastructure: `make plan` builds it with g++ into build/; it is never linked into libocc_gibbs.so.
+#include <cstdio>
+
+#include "occ_plan.hpp"
+
+using namespace occ;
+
+extern "C" {
+
+struct OccPlanOut {  // (mirrored by tests/test_plan_cpu.py)
+    int32_t form, main_cus, tpb, nb_n, nb_r, beta_split, share_on, surplus_last, iter_window, generic, nbg;
+    int32_t tiles_T, tiles_G, xl_wide, xl_nbg, xl_per_cu, main_hot_cus, nmain, partition, flag_sync;
+    int32_t per_xcd[XL_SLOTS], tile_first[3][XL_SLOTS + 1], tile_most[3];
+    int32_t n_ladder, ladder_form[4], ladder_nbg[4];
+};
+
+// shape = {n, rows, chains, p, q, rsr_dim, wmax, dia}.  The plan with the masked pair `granted` or not, settled on the
+// ladder's first form (every form resident).  0, or -1 with the planner's error in err.
+int occ_plan_eval(const int32_t shape[8], int32_t ncu, const PlanOptions *opt, int32_t granted, OccPlanOut *out, char *err, int32_t errlen)
+{
+    PlanShape sh;
+    sh.n = shape[0]; sh.rows = shape[1]; sh.chains = shape[2]; sh.p = shape[3]; sh.q = shape[4];
+    sh.rsr_dim = shape[5]; sh.wmax = shape[6]; sh.dia = shape[7] != 0;
+    Plan P;
+    std::string why;
+    if (!plan_wanted(sh, ncu, *opt, &P, &why)) {
+        std::snprintf(err, (size_t)errlen, "%s", why.c_str());
+        return -1;
+    }
+    plan_granted(P, granted != 0);
+    plan_settle(P, P.ladder.front().form);
+    *out = OccPlanOut{};
+    out->form = P.form; out->main_cus = P.main_cus; out->tpb = P.tpb; out->nb_n = P.nb_n; out->nb_r = P.nb_r;
+    out->beta_split = P.beta_split; out->share_on = P.share_on; out->surplus_last = P.surplus_last;
+    out->iter_window = P.iter_window; out->generic = P.generic; out->nbg = P.nbg;
+    out->tiles_T = P.tiles_T; out->tiles_G = P.tiles_G; out->xl_wide = P.xl_wide; out->xl_nbg = P.xl_nbg;
+    out->xl_per_cu = P.xl_per_cu; out->main_hot_cus = P.main_hot_cus; out->nmain = P.nmain; out->partition = P.partition;
+    out->flag_sync = P.flag_sync;
+    for (int x = 0; x < XL_SLOTS; ++x) out->per_xcd[x] = P.per_xcd[x];
+    for (int k = 0; k < 3; ++k) {
+        for (int x = 0; x <= XL_SLOTS; ++x) out->tile_first[k][x] = P.tile_first[k][x];
+        out->tile_most[k] = P.tile_most[k];
+    }
+    out->n_ladder = (int32_t)P.ladder.size();
+    for (size_t i = 0; i < P.ladder.size() && i < 4; ++i) { out->ladder_form[i] = P.ladder[i].form; out->ladder_nbg[i] = P.ladder[i].nbg; }
+    return 0;
+}
+
+}  // extern "C"

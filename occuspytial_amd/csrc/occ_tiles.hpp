@@ -34,13 +34,9 @@
 
 namespace occ {
 
-constexpr int TILE = 256;
 constexpr int TILE_VECS = 4;  // in LDS: p (two by parity), w (two by parity); g and x live in registers
 enum : int { TV_P = 0, TV_W = 2 };
 __host__ __device__ constexpr size_t tiles_lds_bytes(int T) { return (size_t)T * TILE_VECS * TILE * sizeof(double2); }
-// Workgroups per CU by tiles per workgroup: registers (512 per lane and SIMD: 128 / 168 / 256 per wave at 4 / 3 / 2 workgroups
-// of four waves) and LDS (16 KB per tile of the CU's 160 KB).  Tiles per CU: 4, 6, 9, 8.
-__host__ __device__ constexpr int tiles_wg_per_cu(int T) { return T == 1 ? 4 : (T == 4 ? 2 : 3); }
 
 // The invariant between launches: every group record and every band record of record buffer 1 holds the canary (step 1
 // of the next solve polls them).  k_tiles restores it at its end; this kernel establishes it at creation and after
