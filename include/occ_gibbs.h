@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OCC_ABI_VERSION 6
+#define OCC_ABI_VERSION 7
 #define OCC_MAX_COVARIATES 32 /* p and q limit.  Up to 8 of each: kernels with the p x p / q x q accumulators in registers and the
                                 fused iteration kernel; 9 to 32: generic kernels (run-time p and q, terms reduced one at a time,
                                 Cholesky factor in LDS) on the launch-per-step path */
@@ -78,6 +78,21 @@ typedef struct occ_problem {
      * bytes per iteration, but ANY symmetric positive semi-definite singular Q is accepted (positive off-diagonals too). */
     const double *prior_factor;
     int64_t prior_factor_cols;
+    /* ABI 7: the link function.  0: logit (everything above).  1: probit with reduced-rank spatial effects (ProbitRSRGibbs,
+     * reference gibbs/probit.py): rsr_dim = m (1 to 4096) and rsr_K (n x m) as for the logit model, p and q at most 8, and the
+     * generalized eigenvectors of (K'QK, K'K) that make the eta update factor-free: pb_G (m x m, row-major) with
+     * K'QK pb_G = K'K pb_G diag(pb_lam) and pb_G' K'K pb_G = I, pb_lam (m, >= 0), pb_Phi = K pb_G (n x m, row-major).
+     * State names of a probit handle: alpha beta tau iter z k exists omega_b omega_a, eta (= K theta), eps (n), theta (m, = G c;
+     * setting it sets c and eta), c (m, the engine's coordinates: theta = pb_G c), link (read-only, 1).  Its Philox streams
+     * (sub-stream index in brackets; block 0 for uniforms and normals): omega_b uniform 1 [site], eps normal 11 [site],
+     * xi normal 12 [column], tau gamma 2 [0, cursor], beta normals 5 [component], omega_a uniform 6 [visit row],
+     * alpha normals 7 [component], z uniform 8 [site].  occ_profile counts its kernels under the existing kinds by role:
+     * omega_b (k_pb_site), eta_init (k_pb_proj), minres (k_pb_coef: tau and c), beta_partial (k_pb_eta), omega_a
+     * (k_pb_omega_a), alpha_draw (k_pb_alpha: beta and alpha), z_ob (k_pb_z + k_pb_tail); the chains' counters are restored
+ * afterwards, their vectors are not.  The occ_cond_* entry points, occ_create_group and
+     * occ_create_distributed reject it (OCC_E_BADARG). */
+    int32_t link;
+    const double *pb_Phi, *pb_G, *pb_lam;
 } occ_problem;
 
 typedef struct occ_sampler occ_sampler;
@@ -247,6 +262,8 @@ int occ_cond_z(occ_sampler *s, int32_t chain, const double *u, double *z_out);
  * sub-stream (key, index i, iteration, stream) exactly as a kernel of the iteration would draw it.
  * kind 0: PG(1, param[i]);  1: standard gamma of shape param[i];  2: standard normal;  3: uniform on (0, 1)
  * (param is ignored for kinds 2 and 3).  Host pointers (or device pointers of `device`); n < 2^31.
+ * kind 5: N(param[i], 1) truncated to (0, inf), kind 6: to (-inf, 0) -- the probit model's truncated normal at the uniform of
+ * kind 3 from the same sub-stream (one uniform per draw, the inverse CDF).
  * kind 4 is a device self-test, not a variate: n (a multiple of 64) values in param, out[i] = the wave sum of one of four
  * quantities derived from them, NaN where the three forms of the engine's wave sum (plain, four at once, transposed)
  * disagree in a bit (tests/test_gpu_rng.py).

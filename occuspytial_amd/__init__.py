@@ -5,8 +5,8 @@ posterior API, the per-iteration work done by hand-written HIP kernels for gfx95
 (``include/occ_gibbs.h``).  See DESIGN.md.
 """
 from .data import Data
-from .gibbs import LogitICARGibbs, LogitRSRGibbs
+from .gibbs import LogitICARGibbs, LogitRSRGibbs, ProbitRSRGibbs
 
 __version__ = '0.2.0'
 
-__all__ = ('LogitICARGibbs', 'LogitRSRGibbs', 'Data', '__version__')
+__all__ = ('LogitICARGibbs', 'LogitRSRGibbs', 'ProbitRSRGibbs', 'Data', '__version__')

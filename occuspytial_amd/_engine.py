@@ -36,6 +36,10 @@ def problem_struct(prob):
     if rsr is not None:   # LogitRSRGibbs: eta = K theta
         pb.rsr_dim = int(rsr['dim'])
         pb.rsr_K, pb.rsr_Q, pb.rsr_E = _ptr(rsr['K']), _ptr(rsr['Q']), _ptr(rsr['E'])
+        probit = getattr(prob, 'probit', None)
+        if probit is not None:   # ProbitRSRGibbs: the same basis, plus the eigenvectors of the factor-free theta update
+            pb.link = 1
+            pb.pb_Phi, pb.pb_G, pb.pb_lam = _ptr(probit['Phi']), _ptr(probit['G']), _ptr(probit['lam'])
     elif getattr(prob, 'prior_factor', None) is not None:   # the reference's form of the prior draw: u = E eps
         k['prior_factor'] = np.ascontiguousarray(prob.prior_factor, dtype=np.float64)
         pb.prior_factor = _ptr(k['prior_factor'])
@@ -91,12 +95,22 @@ class Engine:
         _lib.raise_for(code, None)
         self._adopt(lib, h, prob, keys, device)
         del keep
+        if self.probit is not None:
+            # a library that does not know the probit model (an older build, or the CPU oracle's C ABI, which ignores
+            # `link`) would run the logit model on this problem without a word: it must say that it runs the probit one
+            ln = C.c_int64(0)
+            out = np.zeros(1)
+            code = lib.occ_get_state(h, 0, b'link', _ptr(out), 1, C.byref(ln))
+            if code != _lib.OCC_OK or ln.value != 1 or out[0] != 1.0:
+                self.close()
+                raise _lib.EngineUnavailable(f'{_lib.LIB_PATH} does not implement the probit model')
 
     def _adopt(self, lib, handle, prob, keys, device):
         self._h = handle
         self._lib = lib
         self.prob = prob
         self.rsr = getattr(prob, 'rsr', None)
+        self.probit = getattr(prob, 'probit', None)
         self.n_chains = len(keys)
         self.device = int(device)
         self.keys = [int(v) & (2 ** 64 - 1) for v in keys]
@@ -181,6 +195,8 @@ class Engine:
                'iter': np.array([int(self.get('iter', c)) for c in range(self.n_chains)], dtype=np.int64),
                'shape': np.array([self.prob.n, self.prob.p, self.prob.q, self.prob.R], dtype=np.int64)}
         fields = self.CHECKPOINT_FIELDS if self.rsr is None else ('alpha', 'beta', 'tau', 'theta', 'z')
+        if self.probit is not None:   # the engine's own coordinates c and the eta it computed from them: bit-exact continuation
+            fields = ('alpha', 'beta', 'tau', 'theta', 'z', 'c', 'eta', 'eps')
         for name in fields:
             out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
         return out
@@ -196,6 +212,9 @@ class Engine:
         for c in range(self.n_chains):
             self.set_start(c, ckpt['alpha'][c], ckpt['beta'][c], float(np.asarray(ckpt['tau'][c]).ravel()[0]), ckpt[spatial][c])
             self.set('z', ckpt['z'][c], c)
+            if self.probit is not None:
+                for name in ('c', 'eta', 'eps'):
+                    self.set(name, ckpt[name][c], c)
             if self.rsr is None:
                 self.set('xz', ckpt['xz'][c], c)
             self.set('iter', float(ckpt['iter'][c]), c)
@@ -283,17 +302,18 @@ class Engine:
                 for i, k in enumerate(_lib.KERNEL_KINDS)}
 
 
-DRAW_KINDS = {'pg1': 0, 'std_gamma': 1, 'normal': 2, 'uniform': 3, 'wave_sum_check': 4}
+DRAW_KINDS = {'pg1': 0, 'std_gamma': 1, 'normal': 2, 'uniform': 3, 'wave_sum_check': 4, 'truncnorm_pos': 5, 'truncnorm_neg': 6}
 
 
 def device_draw(kind, param=None, n=None, key=1, it=0, stream=1, device=0):
     """Variates of the engine's own generators drawn on the device (``occ_draw``): element ``i`` comes from the
     sub-stream ``(key, i, it, stream)`` exactly as the kernels draw it.  ``kind``: ``'pg1'`` (``param`` = z),
-    ``'std_gamma'`` (``param`` = shape), ``'normal'``, ``'uniform'`` (``n`` draws); ``'wave_sum_check'``: a device self-test
+    ``'std_gamma'`` (``param`` = shape), ``'normal'``, ``'uniform'`` (``n`` draws), ``'truncnorm_pos'`` / ``'truncnorm_neg'``
+    (``param`` = loc: N(loc, 1) truncated to (0, inf) / (-inf, 0) at the uniform of ``'uniform'``); ``'wave_sum_check'``: a device self-test
     (tests/test_gpu_rng.py), NaN where the forms of the engine's wave sum disagree."""
     lib = _lib.load()
     par = None
-    if kind in ('pg1', 'std_gamma', 'wave_sum_check'):
+    if kind in ('pg1', 'std_gamma', 'wave_sum_check', 'truncnorm_pos', 'truncnorm_neg'):
         par = np.ascontiguousarray(param, dtype=np.float64).ravel()
         n = par.size
     out = np.empty(int(n))

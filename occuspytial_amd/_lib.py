@@ -27,6 +27,7 @@ class OccProblem(C.Structure):
         ('tau_rate', C.c_double), ('tau_shape', C.c_double),
         ('rsr_dim', C.c_int32), ('rsr_K', C.c_void_p), ('rsr_Q', C.c_void_p), ('rsr_E', C.c_void_p),
         ('prior_factor', C.c_void_p), ('prior_factor_cols', C.c_int64),
+        ('link', C.c_int32), ('pb_Phi', C.c_void_p), ('pb_G', C.c_void_p), ('pb_lam', C.c_void_p),   # ABI 7
     ]
 
 
@@ -92,7 +93,7 @@ class EngineUnavailable(RuntimeError):
     """The HIP engine cannot be used (library not built, or no usable gfx950 device)."""
 
 
-ABI_VERSION = 6  # OCC_ABI_VERSION of include/occ_gibbs.h this binding was written against
+ABI_VERSION = 7  # OCC_ABI_VERSION of include/occ_gibbs.h this binding was written against
 
 
 def load():

@@ -94,6 +94,7 @@ class FlatProblem:
 
         self._set_hyperparams(hparams)
         self.rsr = None   # set by enable_rsr(): the reduced-rank model of LogitRSRGibbs
+        self.probit = None   # set by enable_probit(): ProbitRSRGibbs (the reduced-rank basis plus its eigenvectors)
 
     # ---- reduced-rank spatial effects (reference gibbs/logit.py:413-460) --------------------------------
     def enable_rsr(self, r=0.5, q=None, default_tau_shape=True):
@@ -125,10 +126,27 @@ class FlatProblem:
         s, u = np.linalg.eigh(Qr)
         E = np.ascontiguousarray(u * np.sqrt(np.clip(s, 0.0, None)))
         self.rsr = {'K': K, 'Q': Qr, 'E': E, 'dim': m}
+        self.probit = None
         if default_tau_shape:
             self.tau_shape = 0.5 + 0.5 * m          # logit.py:448-451 (only when no hyper-parameters were given)
             self.hparams['tau_shape'] = self.tau_shape
         return self.rsr
+
+    def enable_probit(self, r=0.5, q=None, default_tau_shape=True):
+        """The probit model's basis (ProbitRSRGibbs): the reference's K, ``Qr = K'QK`` and ``KTK = K'K`` -- its
+        ``_configure`` computes the same K as ``LogitRSRGibbs`` -- plus what makes the device's theta update factor-free:
+        the generalized eigenvectors ``G`` of ``Qr G = KTK G diag(lam)`` with ``G' KTK G = I`` (``lam < 0`` from rounding
+        clamped to 0) and ``Phi = K G``.  Then ``(KTK + tau Qr)^-1 = G diag(1 / (1 + tau lam)) G'``."""
+        from scipy.linalg import eigh
+        rsr = self.enable_rsr(r=r, q=q, default_tau_shape=default_tau_shape)
+        K = rsr['K']
+        KTK = K.T @ K
+        lam, G = eigh(rsr['Q'], KTK)
+        lam = np.clip(lam, 0.0, None)
+        G = np.ascontiguousarray(G)
+        self.probit = {'K': K, 'Q': rsr['Q'], 'KTK': KTK, 'G': G, 'lam': np.ascontiguousarray(lam),
+                       'Phi': np.ascontiguousarray(K @ G), 'dim': rsr['dim']}
+        return self.probit
 
     # ---- plain-array round trip (what a multi-GPU launch broadcasts; see occuspytial_amd.distributed)
     _ARRAY_FIELDS = ('X', 'site_id', 'site_ptr', 'W', 'y', 'obs_site', 'z0', 'a_mu', 'a_prec', 'b_mu', 'b_prec')

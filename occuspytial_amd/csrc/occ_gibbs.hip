@@ -22,6 +22,7 @@
 #include "occ_comm.hpp"
 #include "occ_tiles.hpp"
 #include "occ_rsr.hpp"
+#include "occ_probit.hpp"
 
 using namespace occ;
 
@@ -185,6 +186,13 @@ struct occ_sampler {
     // host mirrors
     std::vector<int32_t> site_id, site_ptr;
     std::vector<uint8_t> obs_site;
+    // probit model (ProbitRSRGibbs, occ_probit.hpp; occ_problem::link == 1): its own kernels on the main stream, nothing above
+    // but the streams, `allocs`, ev0 / ev1, rec_buf and the statistics is used
+    bool probit = false;
+    PbArgs pb{};
+    std::vector<double> pb_K, pb_Phi, pb_G;  // host copies: theta = G c, and c / eta of a theta the host sets
+    hipGraph_t pb_graph = nullptr;
+    hipGraphExec_t pb_exec = nullptr;
 };
 
 namespace {
@@ -1194,6 +1202,434 @@ int residency_probe(occ_sampler *s, bool *ok)
 
 }  // namespace
 
+// ---- probit model (ProbitRSRGibbs): creation, one iteration, occ_run, state -------------------------------------------
+namespace {
+
+constexpr int PB_GRAPH_SEQ = 8;  // iterations per captured graph of occ_run (one linear chain of 8 launches each)
+
+// The kernels of one iteration by role, in their order (pb_launch_iteration; occ_profile times them one role at a time)
+enum PbRole { PB_SITE = 0, PB_PROJ, PB_COEF, PB_ETA, PB_OMEGA_A, PB_ALPHA, PB_Z, PB_TAIL, PB_N_ROLES };
+static const int kPbKindOfRole[PB_N_ROLES] = {K_OMEGA_B, K_ETA_INIT, K_MINRES, K_BETA_PARTIAL, K_OMEGA_A, K_ALPHA_DRAW, K_Z_OB, K_Z_OB};
+
+int pb_launch_role(occ_sampler *s, hipStream_t st, int role)
+{
+    const PbArgs &A = s->pb;
+    auto blocks = [](long long work, int per) { return dim3((unsigned)((work + per - 1) / per)); };
+    switch (role) {
+        case PB_SITE: hipLaunchKernelGGL(k_pb_site, blocks((long long)A.C * A.n, PB_WG), dim3(PB_WG), 0, st, A); break;
+        case PB_PROJ: hipLaunchKernelGGL(k_pb_proj, dim3((unsigned)A.ntile, (unsigned)((A.m + PB_WG - 1) / PB_WG)), dim3(PB_WG), 0, st, A); break;
+        case PB_COEF: hipLaunchKernelGGL(k_pb_coef, dim3((unsigned)A.C), dim3(PB_WG), 0, st, A); break;
+        case PB_ETA: hipLaunchKernelGGL(k_pb_eta, dim3((unsigned)A.ntile_eta), dim3(PB_WG), 0, st, A); break;
+        case PB_OMEGA_A: hipLaunchKernelGGL(k_pb_omega_a, blocks((long long)A.C * A.R, PB_WG), dim3(PB_WG), 0, st, A); break;
+        case PB_ALPHA:
+            switch (A.q) {
+#define OCC_PB_ALPHA(Q) case Q: hipLaunchKernelGGL(k_pb_alpha<Q>, dim3((unsigned)A.C), dim3(PB_WG), 0, st, A); break;
+                OCC_PB_ALPHA(1) OCC_PB_ALPHA(2) OCC_PB_ALPHA(3) OCC_PB_ALPHA(4) OCC_PB_ALPHA(5) OCC_PB_ALPHA(6) OCC_PB_ALPHA(7) OCC_PB_ALPHA(8)
+#undef OCC_PB_ALPHA
+                default: return set_error(s, OCC_E_BADARG, "the probit model takes 1 to 8 detection covariates");
+            }
+            break;
+        case PB_Z: hipLaunchKernelGGL(k_pb_z, blocks((long long)A.C * A.n, PB_WG), dim3(PB_WG), 0, st, A); break;
+        default: hipLaunchKernelGGL(k_pb_tail, blocks(A.C, 64), dim3(64), 0, st, A); break;
+    }
+    return OCC_OK;
+}
+
+int pb_launch_iteration(occ_sampler *s, hipStream_t st)
+{
+    for (int role = 0; role < PB_N_ROLES; ++role) {
+        const int rc = pb_launch_role(s, st, role);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    return OCC_OK;
+}
+
+int pb_read_chains(occ_sampler *s, std::vector<PbChain> &h)
+{
+    h.resize((size_t)s->pb.C);
+    HIP_TRY(copy_on(s, h.data(), s->pb.ch, sizeof(PbChain) * h.size(), hipMemcpyDeviceToHost));
+    return OCC_OK;
+}
+int pb_write_chains(occ_sampler *s, const std::vector<PbChain> &h)
+{
+    HIP_TRY(copy_on(s, s->pb.ch, h.data(), sizeof(PbChain) * h.size(), hipMemcpyHostToDevice));
+    return OCC_OK;
+}
+int pb_check(occ_sampler *s, const std::vector<PbChain> &h)
+{
+    for (const PbChain &c : h)
+        if (c.err) return set_error(s, OCC_E_CHOLESKY, "Cholesky factorization/solver failed!");
+    return OCC_OK;
+}
+
+// theta of one chain (caller pointer): eta = K theta and c = Phi' eta (= G^-1 theta, since G'K'K G = I), on the host
+int pb_set_theta(occ_sampler *s, int chain, const double *theta_in)
+{
+    const int n = s->pb.n, m = s->pb.m;
+    std::vector<double> th;
+    int rc = fetch(s, th, theta_in, (size_t)m);
+    if (rc) return rc;
+    std::vector<double> eta((size_t)n, 0.0), cc((size_t)m, 0.0);
+    for (int i = 0; i < n; ++i) {
+        double t = 0.0;
+        for (int a = 0; a < m; ++a) t = std::fma(s->pb_K[(size_t)i * m + a], th[a], t);
+        eta[i] = t;
+    }
+    for (int i = 0; i < n; ++i)
+        for (int a = 0; a < m; ++a) cc[a] = std::fma(s->pb_Phi[(size_t)i * m + a], eta[i], cc[a]);
+    HIP_TRY(copy_on(s, s->pb.c + (size_t)chain * m, cc.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+    HIP_TRY(copy_on(s, s->pb.eta + (size_t)chain * n, eta.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    return OCC_OK;
+}
+
+int pb_create(occ_sampler *s, const occ_problem *pb, int32_t C, const uint64_t *keys)
+{
+    if (!keys || C < 1) return set_error(s, OCC_E_BADARG, "bad keys / n_chains");
+    if (pb->n < 1 || pb->n > 0x7fffffff || pb->n_rows < 1 || pb->n_rows > 0x7fffffff || pb->n_surveyed < 1 || pb->n_surveyed > pb->n)
+        return set_error(s, OCC_E_BADARG, "problem sizes out of range");
+    if (pb->p < 1 || pb->p > MAXC || pb->q < 1 || pb->q > MAXC) return set_error(s, OCC_E_BADARG, "the probit model takes 1 to 8 covariates of each kind");
+    if (pb->rsr_dim < 1 || pb->rsr_dim > PB_MAX_DIM || !pb->rsr_K || !pb->pb_Phi || !pb->pb_G || !pb->pb_lam)
+        return set_error(s, OCC_E_BADARG, "the probit model needs 1 to 4096 basis columns (rsr_K, pb_Phi, pb_G, pb_lam)");
+    if (!(pb->tau_rate > 0.0) || !(pb->tau_shape > 0.0)) return set_error(s, OCC_E_BADARG, "tau_rate and tau_shape must be positive");
+    DeviceLease lease = lease_device(s->device);
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (s->device < 0 || s->device >= ndev) return set_error(s, OCC_E_HIP, "no such HIP device");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipEventCreate(&s->ev0));
+    HIP_TRY(hipEventCreate(&s->ev1));
+    int rc;
+    if ((rc = create_plain_streams(s))) return rc;
+    const int n = (int)pb->n, S = (int)pb->n_surveyed, R = (int)pb->n_rows, p = pb->p, q = pb->q, m = pb->rsr_dim;
+    std::vector<double> X, W, y, a_mu, a_prec, b_mu, b_prec, lam;
+    if ((rc = fetch(s, X, pb->X, (size_t)n * p))) return rc;
+    if ((rc = fetch(s, s->site_id, pb->site_id, (size_t)S))) return rc;
+    if ((rc = fetch(s, s->site_ptr, pb->site_ptr, (size_t)S + 1))) return rc;
+    if ((rc = fetch(s, W, pb->W, (size_t)R * q))) return rc;
+    if ((rc = fetch(s, y, pb->y, (size_t)R))) return rc;
+    if ((rc = fetch(s, a_mu, pb->a_mu, (size_t)q))) return rc;
+    if ((rc = fetch(s, a_prec, pb->a_prec, (size_t)q * q))) return rc;
+    if ((rc = fetch(s, b_mu, pb->b_mu, (size_t)p))) return rc;
+    if ((rc = fetch(s, b_prec, pb->b_prec, (size_t)p * p))) return rc;
+    if ((rc = fetch(s, s->pb_K, pb->rsr_K, (size_t)n * m))) return rc;
+    if ((rc = fetch(s, s->pb_Phi, pb->pb_Phi, (size_t)n * m))) return rc;
+    if ((rc = fetch(s, s->pb_G, pb->pb_G, (size_t)m * m))) return rc;
+    if ((rc = fetch(s, lam, pb->pb_lam, (size_t)m))) return rc;
+    for (double v : lam)
+        if (!(v >= 0.0) || !std::isfinite(v)) return set_error(s, OCC_E_BADARG, "pb_lam must be finite and non-negative");
+    // index sets (base.py:112-152): surveyed index of every site and row, sites with a detection
+    std::vector<int> sidx((size_t)n, -1), row_t((size_t)R, 0);
+    std::vector<uint8_t> yrow((size_t)R, 0);
+    s->obs_site.assign((size_t)S, 0);
+    if (s->site_ptr[0] != 0 || s->site_ptr[S] != R) return set_error(s, OCC_E_BADARG, "site_ptr must run from 0 to n_rows");
+    for (int t = 0; t < S; ++t) {
+        const int site = s->site_id[t];
+        if (site < 0 || site >= n || sidx[site] != -1) return set_error(s, OCC_E_BADARG, "site_id entries must be unique and in [0, n)");
+        if (s->site_ptr[t + 1] < s->site_ptr[t]) return set_error(s, OCC_E_BADARG, "site_ptr must not decrease");
+        sidx[site] = t;
+        for (int r = s->site_ptr[t]; r < s->site_ptr[t + 1]; ++r) {
+            row_t[r] = t;
+            yrow[r] = y[r] != 0.0;
+            s->obs_site[t] |= yrow[r];
+        }
+    }
+    std::vector<double> Xt((size_t)p * n), Wt((size_t)q * R);
+    for (int i = 0; i < n; ++i)
+        for (int a = 0; a < p; ++a) Xt[(size_t)a * n + i] = X[(size_t)i * p + a];
+    for (int r = 0; r < R; ++r)
+        for (int a = 0; a < q; ++a) Wt[(size_t)a * R + r] = W[(size_t)r * q + a];
+    // beta's precision X'X + b_prec, factored once (upper, M = U'U); the reference overwrote it with its factor
+    std::vector<double> U((size_t)p * p, 0.0), b_pbm((size_t)p, 0.0), a_pbm((size_t)q, 0.0);
+    for (int a = 0; a < p; ++a)
+        for (int b = a; b < p; ++b) {
+            double t = b_prec[(size_t)a * p + b];
+            for (int i = 0; i < n; ++i) t = std::fma(X[(size_t)i * p + a], X[(size_t)i * p + b], t);
+            U[(size_t)a * p + b] = t;
+        }
+    for (int j = 0; j < p; ++j) {
+        double sj = U[(size_t)j * p + j];
+        for (int k = 0; k < j; ++k) sj -= U[(size_t)k * p + j] * U[(size_t)k * p + j];
+        if (!(sj > 0.0)) return set_error(s, OCC_E_CHOLESKY, "Cholesky factorization/solver failed!");
+        const double ujj = std::sqrt(sj);
+        U[(size_t)j * p + j] = ujj;
+        for (int i = j + 1; i < p; ++i) {
+            double v = U[(size_t)j * p + i];
+            for (int k = 0; k < j; ++k) v -= U[(size_t)k * p + j] * U[(size_t)k * p + i];
+            U[(size_t)j * p + i] = v / ujj;
+        }
+    }
+    for (int a = 0; a < p; ++a)
+        for (int b = 0; b < p; ++b) b_pbm[a] += b_prec[(size_t)a * p + b] * b_mu[b];
+    for (int a = 0; a < q; ++a)
+        for (int b = 0; b < q; ++b) a_pbm[a] += a_prec[(size_t)a * q + b] * a_mu[b];
+    PbArgs &A = s->pb;
+    A.n = n; A.m = m; A.p = p; A.q = q; A.R = R; A.S = S; A.C = C;
+    A.ldm = 16 * ((m + 15) / 16);  // rows on whole 128-byte lines
+    A.ntile = (n + PB_TS - 1) / PB_TS;
+    A.ntile_eta = (n + PB_TS_ETA - 1) / PB_TS_ETA;
+    A.tau_rate = pb->tau_rate; A.tau_shape = pb->tau_shape;
+    std::vector<double> Phip((size_t)n * A.ldm, 0.0);
+    for (int i = 0; i < n; ++i) std::copy(s->pb_Phi.begin() + (size_t)i * m, s->pb_Phi.begin() + (size_t)(i + 1) * m, Phip.begin() + (size_t)i * A.ldm);
+    if ((rc = upload(s, &A.Phi, Phip, "pb_Phi"))) return rc;
+    if ((rc = upload(s, &A.lam, lam, "pb_lam"))) return rc;
+    if ((rc = upload(s, &A.Xt, Xt, "Xt"))) return rc;
+    if ((rc = upload(s, &A.Wt, Wt, "Wt"))) return rc;
+    if ((rc = upload(s, &A.bU, U, "pb_bU"))) return rc;
+    if ((rc = upload(s, &A.b_pbm, b_pbm, "b_pbm"))) return rc;
+    if ((rc = upload(s, &A.a_prec, a_prec, "a_prec"))) return rc;
+    if ((rc = upload(s, &A.a_pbm, a_pbm, "a_pbm"))) return rc;
+    if ((rc = upload(s, &A.yrow, yrow, "yrow"))) return rc;
+    if ((rc = upload(s, &A.obs_site, s->obs_site, "obs_site"))) return rc;
+    if ((rc = upload(s, &A.site_id, s->site_id, "site_id"))) return rc;
+    if ((rc = upload(s, &A.site_ptr, s->site_ptr, "site_ptr"))) return rc;
+    if ((rc = upload(s, &A.sidx, sidx, "sidx"))) return rc;
+    if ((rc = upload(s, &A.row_t, row_t, "row_t"))) return rc;
+    const size_t Cn = (size_t)C * n;
+    if ((rc = dev_alloc(s, &A.omega_b, Cn)) || (rc = dev_alloc(s, &A.eps, Cn)) || (rc = dev_alloc(s, &A.eta, Cn)) ||
+        (rc = dev_alloc(s, &A.s, Cn)) || (rc = dev_alloc(s, &A.z, Cn)) || (rc = dev_alloc(s, &A.omega_a, (size_t)C * R)) ||
+        (rc = dev_alloc(s, &A.c, (size_t)C * m)) || (rc = dev_alloc(s, &A.upart, (size_t)A.ntile * C * m)) ||
+        (rc = dev_alloc(s, &A.bpart, (size_t)A.ntile_eta * C * p)) || (rc = dev_alloc(s, &A.ch, (size_t)C)) || (rc = dev_alloc(s, &A.rec, 1)))
+        return rc;
+    std::vector<PbChain> h((size_t)C);
+    for (int c = 0; c < C; ++c) {
+        std::memset(&h[c], 0, sizeof(PbChain));
+        h[c].key = keys[c];
+        h[c].tau = 1.0;
+    }
+    if ((rc = pb_write_chains(s, h))) return rc;
+    std::vector<uint8_t> z0(Cn, 1);  // base.py:113-119
+    for (int c = 0; c < C; ++c)
+        for (int t = 0; t < S; ++t) z0[(size_t)c * n + s->site_id[t]] = s->obs_site[t];
+    HIP_TRY(copy_on(s, A.z, z0.data(), Cn, hipMemcpyHostToDevice));
+    Ctx &cx = s->ctx;  // (sizes only: the entry points' chain checks)
+    cx.n = n; cx.S = S; cx.R = R; cx.p = p; cx.q = q; cx.C = C;
+    s->probit = true;
+    s->plan.tpb = PB_WG;
+    WAIT_TRY(s->stream);
+    return OCC_OK;
+}
+
+int pb_step(occ_sampler *s)
+{
+    int rc = pb_launch_iteration(s, s->stream);
+    if (rc) return rc;
+    std::vector<PbChain> h;
+    if ((rc = pb_read_chains(s, h))) return rc;
+    s->iterations = h[0].it;
+    ++s->eager_iterations;
+    return pb_check(s, h);
+}
+
+int pb_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, double *out_beta, double *out_tau)
+{
+    const PbArgs &A = s->pb;
+    const int64_t keep = n_iter - burnin;
+    const int w = A.q + A.p + 1;
+    const size_t need = (size_t)A.C * keep * w;
+    if (need > s->rec_cap) {
+        if (s->rec_buf) HIP_TRY(hipFree(s->rec_buf));
+        s->rec_buf = nullptr;
+        s->rec_cap = 0;
+        HIP_TRY(hipMalloc(&s->rec_buf, sizeof(double) * need));
+        s->rec_cap = need;
+    }
+    std::vector<PbChain> h;
+    int rc = pb_read_chains(s, h);
+    if (rc) return rc;
+    for (PbChain &c : h) { c.rec_first = c.it + (uint32_t)burnin; c.rec_keep = (uint32_t)keep; }
+    if ((rc = pb_write_chains(s, h))) return rc;
+    HIP_TRY(copy_on(s, A.rec, &s->rec_buf, sizeof(double *), hipMemcpyHostToDevice));
+    if (!s->pb_exec) {  // one linear graph of PB_GRAPH_SEQ iterations, captured once (the kernels take nothing that changes)
+        HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
+        for (int k = 0; k < PB_GRAPH_SEQ && rc == OCC_OK; ++k) rc = pb_launch_iteration(s, s->stream);
+        hipGraph_t g = nullptr;
+        const hipError_t e = hipStreamEndCapture(s->stream, &g);
+        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+        HIP_TRY(e);
+        s->pb_graph = g;
+        HIP_TRY(hipGraphInstantiate(&s->pb_exec, s->pb_graph, nullptr, nullptr, 0));
+    }
+    HIP_TRY(hipEventRecord(s->ev0, s->stream));
+    const int64_t full = n_iter / PB_GRAPH_SEQ;
+    for (int64_t b = 0; b < full; ++b) {
+        HIP_TRY(hipGraphLaunch(s->pb_exec, s->stream));
+        ++s->graph_launches;
+        if ((b + 1) % 32 == 0) WAIT_TRY(s->stream);  // (every host wait stays far below its deadline)
+    }
+    for (int64_t k = full * PB_GRAPH_SEQ; k < n_iter; ++k) {
+        if ((rc = pb_launch_iteration(s, s->stream))) return rc;
+        ++s->eager_iterations;
+    }
+    HIP_TRY(hipEventRecord(s->ev1, s->stream));
+    WAIT_TRY(s->stream);
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    s->last_run_ms = ms;
+    double *none = nullptr;
+    HIP_TRY(copy_on(s, A.rec, &none, sizeof(double *), hipMemcpyHostToDevice));
+    std::vector<double> rec(need);
+    if (need) HIP_TRY(copy_on(s, rec.data(), s->rec_buf, sizeof(double) * need, hipMemcpyDeviceToHost));
+    for (int c = 0; c < A.C; ++c)
+        for (int64_t r = 0; r < keep; ++r) {
+            const double *row = rec.data() + ((size_t)c * keep + r) * w;
+            std::copy(row, row + A.q, out_alpha + ((size_t)c * keep + r) * A.q);
+            std::copy(row + A.q, row + A.q + A.p, out_beta + ((size_t)c * keep + r) * A.p);
+            out_tau[(size_t)c * keep + r] = row[A.q + A.p];
+        }
+    if ((rc = pb_read_chains(s, h))) return rc;
+    s->iterations = h[0].it;
+    return pb_check(s, h);
+}
+
+int pb_set_start(occ_sampler *s, int chain, const double *alpha, const double *beta, double tau, const double *theta)
+{
+    std::vector<PbChain> h;
+    std::vector<double> a, b;
+    int rc;
+    if ((rc = pb_read_chains(s, h))) return rc;
+    if ((rc = fetch(s, a, alpha, (size_t)s->pb.q))) return rc;
+    if ((rc = fetch(s, b, beta, (size_t)s->pb.p))) return rc;
+    PbChain &c = h[chain];
+    std::memset(c.alpha, 0, sizeof(c.alpha));
+    std::memset(c.beta, 0, sizeof(c.beta));
+    std::copy(a.begin(), a.end(), c.alpha);
+    std::copy(b.begin(), b.end(), c.beta);
+    c.tau = tau;
+    c.it = 0; c.err = 0; c.rec_first = 0; c.rec_keep = 0;
+    if ((rc = pb_write_chains(s, h))) return rc;
+    return pb_set_theta(s, chain, theta);
+}
+
+int pb_get_state(occ_sampler *s, int chain, const std::string &nm, std::vector<double> &v)
+{
+    const PbArgs &A = s->pb;
+    const size_t n = (size_t)A.n, R = (size_t)A.R, m = (size_t)A.m;
+    auto pull = [&](const double *src, size_t count) -> int {
+        v.resize(count);
+        if (count) HIP_TRY(copy_on(s, v.data(), src, sizeof(double) * count, hipMemcpyDeviceToHost));
+        return OCC_OK;
+    };
+    std::vector<PbChain> h;
+    int rc = pb_read_chains(s, h);
+    if (rc) return rc;
+    const PbChain &c = h[chain];
+    if (nm == "eta") return pull(A.eta + chain * n, n);
+    if (nm == "eps") return pull(A.eps + chain * n, n);
+    if (nm == "omega_b") return pull(A.omega_b + chain * n, n);
+    if (nm == "omega_a") return pull(A.omega_a + chain * R, R);
+    if (nm == "c") return pull(A.c + chain * m, m);
+    if (nm == "theta") {
+        std::vector<double> cc;
+        if ((rc = pull(A.c + chain * m, m))) return rc;
+        cc.swap(v);
+        v.assign(m, 0.0);
+        for (size_t i = 0; i < m; ++i) {
+            double t = 0.0;
+            for (size_t j = 0; j < m; ++j) t = std::fma(s->pb_G[i * m + j], cc[j], t);
+            v[i] = t;
+        }
+        return OCC_OK;
+    }
+    if (nm == "z" || nm == "k" || nm == "exists") {
+        std::vector<uint8_t> z(n);
+        HIP_TRY(copy_on(s, z.data(), A.z + chain * n, n, hipMemcpyDeviceToHost));
+        if (nm == "exists") {
+            v.resize((size_t)A.S);
+            for (int t = 0; t < A.S; ++t) v[t] = (s->obs_site[t] || z[s->site_id[t]]) ? 1.0 : 0.0;
+        } else {
+            v.resize(n);
+            for (size_t i = 0; i < n; ++i) v[i] = (nm == "z") ? (double)z[i] : (double)z[i] - 0.5;
+        }
+        return OCC_OK;
+    }
+    if (nm == "alpha") v.assign(c.alpha, c.alpha + A.q);
+    else if (nm == "beta") v.assign(c.beta, c.beta + A.p);
+    else if (nm == "tau") v.assign(1, c.tau);
+    else if (nm == "iter") v.assign(1, (double)c.it);
+    else if (nm == "link") v.assign(1, 1.0);
+    else return set_error(s, OCC_E_STATE, "unknown state name");
+    return OCC_OK;
+}
+
+int pb_set_state(occ_sampler *s, int chain, const std::string &nm, const double *in, int64_t len)
+{
+    const PbArgs &A = s->pb;
+    const size_t n = (size_t)A.n, R = (size_t)A.R, m = (size_t)A.m;
+    auto need = [&](size_t want) { return (size_t)len == want; };
+    auto push = [&](double *dst, size_t count) -> int {
+        if (!need(count)) return set_error(s, OCC_E_STATE, "wrong length");
+        HIP_TRY(copy_on(s, dst, in, sizeof(double) * count, hipMemcpyHostToDevice));
+        return OCC_OK;
+    };
+    if (nm == "eta") return push(A.eta + chain * n, n);
+    if (nm == "eps") return push(A.eps + chain * n, n);
+    if (nm == "omega_a") return push(A.omega_a + chain * R, R);
+    if (nm == "c") return push(A.c + chain * m, m);
+    if (nm == "theta") {
+        if (!need(m)) return set_error(s, OCC_E_STATE, "wrong length");
+        return pb_set_theta(s, chain, in);
+    }
+    if (nm == "z") {
+        if (!need(n)) return set_error(s, OCC_E_STATE, "wrong length");
+        std::vector<uint8_t> z(n);
+        for (size_t i = 0; i < n; ++i) z[i] = in[i] != 0.0;
+        HIP_TRY(copy_on(s, A.z + chain * n, z.data(), n, hipMemcpyHostToDevice));
+        return OCC_OK;
+    }
+    std::vector<PbChain> h;
+    int rc = pb_read_chains(s, h);
+    if (rc) return rc;
+    PbChain &c = h[chain];
+    if (nm == "alpha" && need((size_t)A.q)) std::copy(in, in + A.q, c.alpha);
+    else if (nm == "beta" && need((size_t)A.p)) std::copy(in, in + A.p, c.beta);
+    else if (nm == "tau" && need(1)) c.tau = in[0];
+    else if (nm == "iter" && need(1)) c.it = (uint32_t)in[0];
+    else return set_error(s, OCC_E_STATE, "unknown state name or wrong length");
+    return pb_write_chains(s, h);
+}
+
+// occ_profile of a probit handle: `reps` launches of each kernel in a captured graph between two events, role by role.
+// The chains' scalars (iteration counters, keys, records) are restored afterwards; their vectors are left as the repeated
+// launches made them (the header's contract: occ_set_start before sampling again).
+int pb_profile(occ_sampler *s, int reps, int64_t counts[OCC_N_KERNEL_KINDS], double total_us[OCC_N_KERNEL_KINDS])
+{
+    for (int k = 0; k < OCC_N_KERNEL_KINDS; ++k) { counts[k] = 0; total_us[k] = 0.0; }
+    std::vector<PbChain> saved;
+    int rc = pb_read_chains(s, saved);
+    if (rc) return rc;
+    for (int role = 0; role < PB_N_ROLES; ++role) {
+        hipGraph_t g = nullptr;
+        hipGraphExec_t ge = nullptr;
+        HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
+        for (int r = 0; r < reps && rc == OCC_OK; ++r) rc = pb_launch_role(s, s->stream, role);
+        const hipError_t le = hipGetLastError();
+        const hipError_t e = hipStreamEndCapture(s->stream, &g);
+        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+        HIP_TRY(le);
+        HIP_TRY(e);
+        const hipError_t ie = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+        if (ie != hipSuccess) { (void)hipGraphDestroy(g); HIP_TRY(ie); }
+        float ms = 0.0f;
+        hipError_t re = hipGraphLaunch(ge, s->stream);  // (warm-up)
+        if (re == hipSuccess) re = hipEventRecord(s->ev0, s->stream);
+        if (re == hipSuccess) re = hipGraphLaunch(ge, s->stream);
+        if (re == hipSuccess) re = hipEventRecord(s->ev1, s->stream);
+        const int wr = re == hipSuccess ? wait_on(s, s->stream, __func__, __LINE__) : OCC_OK;
+        if (re == hipSuccess && wr == OCC_OK) re = hipEventElapsedTime(&ms, s->ev0, s->ev1);
+        (void)hipGraphExecDestroy(ge);
+        (void)hipGraphDestroy(g);
+        if (wr) return wr;
+        HIP_TRY(re);
+        counts[kPbKindOfRole[role]] += reps;
+        total_us[kPbKindOfRole[role]] += 1000.0 * ms;
+    }
+    return pb_write_chains(s, saved);
+}
+
+}  // namespace
+
+
 // =================================================================================================
 extern "C" {
 
@@ -1225,6 +1661,8 @@ int occ_destroy(occ_sampler *s)
             std::fprintf(stderr, "[occ] an engine whose streams never drained is closed without freeing its device memory (%s)\n", s->err.c_str());
         } else {
             destroy_graph(s);
+            if (s->pb_exec) (void)hipGraphExecDestroy(s->pb_exec);
+            if (s->pb_graph) (void)hipGraphDestroy(s->pb_graph);
             for (void *p : s->allocs) (void)hipFree(p);
             if (s->rec_buf) (void)hipFree(s->rec_buf);
             if (s->pin_sc) (void)hipHostFree(s->pin_sc);
@@ -1714,8 +2152,12 @@ int occ_create(const occ_problem *problem, int32_t n_chains, const uint64_t *key
     s->device = device;
     HostLayout L;
     int rc = hipSetDevice(device) == hipSuccess ? OCC_OK : set_error(s, OCC_E_HIP, "no such HIP device");
-    if (rc == OCC_OK) rc = build_layout(s, problem, L);
-    if (rc == OCC_OK) rc = create_impl(s, L, n_chains, keys);
+    if (rc == OCC_OK && problem && problem->link == 1) rc = pb_create(s, problem, n_chains, keys);  // probit model
+    else if (rc == OCC_OK && problem && problem->link != 0) rc = set_error(s, OCC_E_BADARG, "link must be 0 (logit) or 1 (probit)");
+    else {
+        if (rc == OCC_OK) rc = build_layout(s, problem, L);
+        if (rc == OCC_OK) rc = create_impl(s, L, n_chains, keys);
+    }
     if (rc != OCC_OK) {
         g_create_error = s->err;
         occ_destroy(s);
@@ -1953,6 +2395,10 @@ int occ_create_distributed(const occ_problem *problem, occ_comm *cm, int32_t roo
 {
     if (!out || !cm || root < 0 || root >= cm->world) return OCC_E_BADARG;
     *out = nullptr;
+    if (problem && problem->link != 0) {
+        g_create_error = "multi-GPU sampling covers the logit model";
+        return OCC_E_BADARG;
+    }
     occ_sampler *s = new occ_sampler();
     s->device = cm->device;
     auto fail = [&](int rc) { g_create_error = s->err.empty() ? cm->err : s->err; occ_destroy(s); return rc; };
@@ -2040,6 +2486,10 @@ int occ_create_group(const occ_problem *problem, int32_t n_devices, const int32_
 {
     if (!out || !devices || !chains_per_device || !keys || n_devices < 1) return OCC_E_BADARG;
     for (int g = 0; g < n_devices; ++g) out[g] = nullptr;
+    if (problem && problem->link != 0) {
+        g_create_error = "multi-GPU sampling covers the logit model";
+        return OCC_E_BADARG;
+    }
     std::vector<occ_sampler *> ss((size_t)n_devices, nullptr);
     auto fail = [&](int rc, const std::string &msg) {
         g_create_error = msg;
@@ -2169,6 +2619,7 @@ int occ_set_start(occ_sampler *s, int32_t chain, const double *alpha, const doub
     if (chain < 0 || chain >= c.C || !alpha || !beta || !eta) return set_error(s, OCC_E_BADARG, "bad chain / null start pointer");
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
+    if (s->probit) return pb_set_start(s, chain, alpha, beta, tau, eta);
     std::vector<ChainScalars> h;
     int rc = read_scalars(s, h);
     if (rc) return rc;
@@ -2200,6 +2651,13 @@ int occ_set_keys(occ_sampler *s, const uint64_t *keys)
     if (!s || !keys) return OCC_E_BADARG;
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
+    if (s->probit) {
+        std::vector<PbChain> hp;
+        int rc = pb_read_chains(s, hp);
+        if (rc) return rc;
+        for (size_t c = 0; c < hp.size(); ++c) hp[c].key = keys[c];
+        return pb_write_chains(s, hp);
+    }
     std::vector<ChainScalars> h;
     int rc = read_scalars(s, h);
     if (rc) return rc;
@@ -2535,6 +2993,7 @@ int occ_step(occ_sampler *s)
     if (!s) return OCC_E_BADARG;
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
+    if (s->probit) return pb_step(s);
     int rc;
     if ((rc = refresh_paths(s))) return rc;
     const bool fused = (s->fused() && s->rsr.m == 0) || s->run.flag_sync;  // paths with device-side waits: re-run without them if one gives up
@@ -2554,6 +3013,7 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
     if (!out_alpha || !out_beta || !out_tau) return set_error(s, OCC_E_BADARG, "null output buffer");
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
+    if (s->probit) return pb_run(s, n_iter, burnin, out_alpha, out_beta, out_tau);
     int rc;
     if ((rc = refresh_paths(s))) return rc;
     const bool fused = (s->fused() && s->rsr.m == 0) || s->run.flag_sync;
@@ -2577,6 +3037,16 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     const std::string nm(name);
     const size_t n = (size_t)c.n, R = (size_t)c.R;
     std::vector<double> v;
+    if (s->probit) {
+        const int prc = pb_get_state(s, chain, nm, v);
+        if (prc) return prc;
+        *len = (int64_t)v.size();
+        if (out) {
+            if (cap < (int64_t)v.size()) return set_error(s, OCC_E_STATE, "output buffer too small");
+            std::copy(v.begin(), v.end(), out);
+        }
+        return OCC_OK;
+    }
     auto pull = [&](const double *src, size_t count) -> int {
         v.resize(count);
         if (count) HIP_TRY(copy_on(s, v.data(), src, sizeof(double) * count, hipMemcpyDeviceToHost));
@@ -2642,6 +3112,7 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     HIP_TRY(hipSetDevice(s->device));
     WAIT_TRY(s->stream);
     const std::string nm(name);
+    if (s->probit) return pb_set_state(s, chain, nm, in, len);
     const size_t n = (size_t)c.n, R = (size_t)c.R;
     auto need = [&](size_t want) { return (size_t)len == want; };
     if (nm == "eta") {
@@ -2703,6 +3174,28 @@ int occ_get_stats(occ_sampler *s, occ_stats *out)
     if (!s || !out) return OCC_E_BADARG;
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
+    if (s->probit) {  // no Krylov solve, no fused kernel, no CU partition: those fields stay 0
+        std::memset(out, 0, sizeof(*out));
+        std::vector<PbChain> hp;
+        int prc = pb_read_chains(s, hp);
+        if (prc) return prc;
+        out->iterations = hp[0].it;
+        out->graph_launches = s->graph_launches;
+        out->eager_iterations = s->eager_iterations;
+        out->last_run_ms = s->last_run_ms;
+        out->n_blocks_sites = (int32_t)(((long long)s->pb.C * s->pb.n + PB_WG - 1) / PB_WG);
+        out->n_blocks_rows = s->pb.ntile;
+        out->threads_per_block = PB_WG;
+        out->n_chains = s->pb.C;
+        out->handover_mode = 1;
+        int masked = 0, plain = 0, idle = 0;
+        count_pairs(s->device, &masked, &plain, &idle);
+        out->stream_pairs_masked = masked;
+        out->stream_pairs_plain = plain;
+        out->stream_pairs_idle = idle;
+        out->stream_pairs_evicted = (int32_t)g_pairs_evicted.load();
+        return OCC_OK;
+    }
     std::vector<ChainScalars> h;
     int rc = read_scalars(s, h);
     if (rc) return rc;
@@ -2784,6 +3277,7 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     if (!s || reps < 1 || !counts || !total_us) return OCC_E_BADARG;
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
+    if (s->probit) return pb_profile(s, reps, counts, total_us);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops
     if (rc) return rc;
     // The fused iteration kernel first, IN SITU: `reps` real iterations continue the chains from where they are
@@ -2918,7 +3412,7 @@ int cond_begin(occ_sampler *s, int chain, const Inject &inj, uint32_t *it_out)
 {
     Ctx &c = s->ctx;
     if (chain < 0 || chain >= c.C) return set_error(s, OCC_E_BADARG, "bad chain index");
-    if (s->rsr.m > 0) return set_error(s, OCC_E_BADARG, "the per-conditional entry points cover the ICAR model");
+    if (s->rsr.m > 0 || s->probit) return set_error(s, OCC_E_BADARG, "the per-conditional entry points cover the ICAR model");
     HIP_TRY(hipSetDevice(s->device));
     int rc;
     if (!s->inj_dev) {
@@ -3117,7 +3611,7 @@ int occ_cond_z(occ_sampler *s, int32_t chain, const double *u, double *z_out)
 // Device draws of the engine's own variate generators (see the header).
 int occ_draw(int32_t device, int32_t kind, uint64_t key, uint32_t iteration, uint32_t stream, int64_t n, const double *param, double *out)
 {
-    if (n < 0 || n > 0x7fffffffLL || !out || kind < 0 || kind > 4 || ((kind == 0 || kind == 1 || kind == 4) && !param && n > 0) || (kind == 4 && n % 64 != 0)) {
+    if (n < 0 || n > 0x7fffffffLL || !out || kind < 0 || kind > 6 || ((kind == 0 || kind == 1 || kind >= 4) && !param && n > 0) || (kind == 4 && n % 64 != 0)) {
         g_create_error = "occ_draw: bad arguments";
         return OCC_E_BADARG;
     }
@@ -3131,8 +3625,12 @@ int occ_draw(int32_t device, int32_t kind, uint64_t key, uint32_t iteration, uin
         if (e == hipSuccess) e = hipMemcpy(d_par, param, sizeof(double) * (size_t)n, hipMemcpyDefault);
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_draw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (int)kind, key, iteration, stream, (long long)n,
-                           (const double *)d_par, d_out);
+        if (kind >= 5)  // the probit model's truncated normals
+            hipLaunchKernelGGL(k_pb_draw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (int)(kind == 6), key, iteration, stream,
+                               (long long)n, (const double *)d_par, d_out);
+        else
+            hipLaunchKernelGGL(k_draw, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (int)kind, key, iteration, stream, (long long)n,
+                               (const double *)d_par, d_out);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);

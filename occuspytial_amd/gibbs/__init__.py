@@ -1,3 +1,4 @@
 from .logit import LogitICARGibbs, LogitRSRGibbs
+from .probit import ProbitRSRGibbs
 
-__all__ = ('LogitICARGibbs', 'LogitRSRGibbs')
+__all__ = ('LogitICARGibbs', 'LogitRSRGibbs', 'ProbitRSRGibbs')
