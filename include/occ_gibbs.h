@@ -133,7 +133,25 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  *   the factor U (Lam = U'U) right of each 32-row panel's diagonal block (the rest is working storage)
  * occ_get_state copies into out (capacity cap doubles) and stores the length in *len.
  * occ_set_state accepts alpha beta tau eta z omega_a xz iter theta (theta also sets eta = K theta); omega_b of
- * the coming iteration is then redrawn from the new state. */
+ * the coming iteration is then redrawn from the new state.
+ *
+ * Per-site posterior summaries (logit models; ICAR and reduced rank), accumulated on the device by the z update of every
+ * KEPT iteration of a chain whose switch is on: an iteration `it` of a call counts when it - (first iteration of the
+ * call) >= the call's burnin (occ_step: every step) and it completes.  Five float64 sums per site and one count per chain:
+ *   site_psi(n)   sum of psi_i = expit(x_i beta + eta_i), every site            -> / count: posterior mean occupancy probability
+ *   site_occ(n)   sum of P(z_i = 1 | alpha, beta, eta, y) of the z update (logit.py:234-252), exactly 1 per iteration at a
+ *                 site with a detection                                          -> P(z_i = 1 | data), Rao-Blackwellised
+ *   site_z(n)     sum of the new z_i                                             -> raw frequency of occupancy
+ *   site_eta(n)   sum of eta_i (reduced rank: (K theta)_i)   site_eta2(n)  sum of eta_i^2   -> mean and sd of the spatial effect
+ *   site_count(1) iterations accumulated                     site_stats(1) the chain's switch, 0 / 1
+ * occ_set_state "site_stats" 1: allocates at first use (40 n bytes per chain of the handle), ZEROES the chain's sums and
+ * count, switches on; 0: switches off, the sums stay readable.  occ_set_state also accepts site_count and the five sums
+ * (checkpoint restore), only while the chain's switch is on.  occ_get_state of any of the seven names before the handle's
+ * first switch-on: OCC_E_STATE.  The names do not touch the chain's state (nothing is redrawn); occ_set_start and
+ * occ_set_keys touch neither switch nor sums; a call that is re-run after a device-side wait gave up (occ_stats::
+ * fused_fallbacks) counts no iteration twice; occ_profile and the occ_cond_* entry points never accumulate.  alpha, beta,
+ * tau, eta, z are bit-identical with the switch on or off.  A probit handle (link = 1) answers every one of these names
+ * with OCC_E_STATE, "site summaries are not available for the probit model". */
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len);
 int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double *in, int64_t len);
 

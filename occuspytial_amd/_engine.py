@@ -114,6 +114,7 @@ class Engine:
         self.n_chains = len(keys)
         self.device = int(device)
         self.keys = [int(v) & (2 ** 64 - 1) for v in keys]
+        self._site_on = False   # per-site posterior sums switched on (site_stats); off: no call about them reaches the library
         _LIVE.add(self)
         return self
 
@@ -199,6 +200,10 @@ class Engine:
             fields = ('alpha', 'beta', 'tau', 'theta', 'z', 'c', 'eta', 'eps')
         for name in fields:
             out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
+        if self._site_on:   # switch, count and the five per-site sums: a resumed run ends with the sums of the uninterrupted one
+            out['site_stats'] = np.ones(self.n_chains)
+            for name in _lib.SITE_FIELDS[1:]:
+                out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
         return out
 
     def restore(self, ckpt):
@@ -218,6 +223,28 @@ class Engine:
             if self.rsr is None:
                 self.set('xz', ckpt['xz'][c], c)
             self.set('iter', float(ckpt['iter'][c]), c)
+        if 'site_stats' in ckpt and np.all(np.asarray(ckpt['site_stats']) != 0):
+            self.site_stats(True)
+            for c in range(self.n_chains):
+                for name in _lib.SITE_FIELDS[1:]:
+                    self.set(name, ckpt[name][c], c)
+        elif self._site_on:
+            self.site_stats(False)
+
+    # ---- per-site posterior sums accumulated on the device (state names site_*, include/occ_gibbs.h) ----
+    def site_stats(self, on):
+        """Switch the per-site sums of every chain on (which ZEROES them and their counts) or off (they stay readable).
+        While on, the z update of every kept iteration adds psi, P(z = 1 | rest), z, eta and eta^2 of every site."""
+        for c in range(self.n_chains):
+            self.set('site_stats', 1.0 if on else 0.0, c)
+        self._site_on = bool(on)
+
+    def site_sums(self, chain=0):
+        """``{'count', 'psi', 'occ', 'z', 'eta', 'eta2'}`` of one chain: the iterations accumulated and the five sums (n)."""
+        out = {'count': int(self.get('site_count', chain)[0])}
+        for name in _lib.SITE_FIELDS[2:]:
+            out[name[len('site_'):]] = self.get(name, chain)
+        return out
 
     def set_start(self, chain, alpha, beta, tau, eta):
         a = np.ascontiguousarray(alpha, dtype=np.float64)
@@ -380,6 +407,18 @@ class EngineGroup:
     def set(self, name, value, chain=0):
         g, i = self.where[chain]
         self.engines[g].set(name, value, i)
+
+    @property
+    def _site_on(self):
+        return any(getattr(e, '_site_on', False) for e in self.engines)
+
+    def site_stats(self, on):
+        for e in self.engines:
+            e.site_stats(on)
+
+    def site_sums(self, chain=0):
+        g, i = self.where[chain]
+        return self.engines[g].site_sums(i)
 
     def step(self):
         self._each(lambda e: e.step())

@@ -13,6 +13,9 @@ LIB_PATH = os.path.join(_HERE, 'libocc_gibbs.so')
 OCC_OK = 0
 OCC_E_BADARG, OCC_E_HIP, OCC_E_MINRES, OCC_E_CHOLESKY, OCC_E_STATE = -1, -2, -3, -4, -5
 N_KERNEL_KINDS = 9
+# state names of the per-site posterior sums (occ_get_state / occ_set_state, see the header): the chain's switch, its count
+# of accumulated iterations, and the five sums of length n
+SITE_FIELDS = ('site_stats', 'site_count', 'site_psi', 'site_occ', 'site_z', 'site_eta', 'site_eta2')
 KERNEL_KINDS = ('omega_b', 'noise', 'eta_init', 'minres', 'beta_partial', 'omega_a', 'alpha_draw', 'z_ob', 'iter')
 
 

@@ -113,6 +113,11 @@ struct occ_sampler {
     uint8_t *snap_z = nullptr;
     double2 *snap_x = nullptr;
     double *snap_theta = nullptr;  // reduced-rank model: the basis coefficients
+    // per-site posterior sums (Ctx::site_acc / site_count; state names site_*).  site_launch: a chain has its switch on, so
+    // launch_kind() launches k_z_ob_stats where k_z_ob stands (baked into captured graphs: a change drops them).  The sums are
+    // part of what a call is re-run from: snap_site ([5 C n] sums, then [C] counts), site_snapped: taken for the running call.
+    bool site_launch = false, site_snapped = false;
+    double *snap_site = nullptr;
     std::vector<ChainScalars> snap_sc;
     // fixed problem arrays on the device, in upload order: what a group broadcasts from its root (occ_create_group /
     // occ_create_distributed); defer_fixed: allocate only, the bytes arrive by broadcast
@@ -398,6 +403,7 @@ KernelRsr pick_rsr_solve(int m)
     }
 }
 KernelEI pick_z_ob(int p) { return OCC_PICK_P(k_z_ob, p); }
+KernelEI pick_z_ob_stats(int p) { return OCC_PICK_P(k_z_ob_stats, p); }
 KernelEI pick_omega_a(int q)
 {
     switch (q) {
@@ -439,6 +445,7 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
     const dim3 blk((unsigned)P.tpb), gs((unsigned)c.nb_n, (unsigned)c.C), gr((unsigned)c.nb_r, (unsigned)c.C);
     const int tp = P.generic ? 0 : c.p, tq = P.generic ? 0 : c.q;  // template arguments: 0 = the generic (run-time) instantiation
     const size_t lds_p = P.generic ? generic_lds_bytes(nacc(c.p), P.tpb) : 0, lds_q = P.generic ? generic_lds_bytes(nacc(c.q), P.tpb) : 0;
+    const KernelEI z_ob = s->site_launch ? pick_z_ob_stats(tp) : pick_z_ob(tp);  // (the twin that keeps the per-site sums)
     switch (kind) {
         case K_OMEGA_B: hipLaunchKernelGGL(pick_omega_b(tp), gs, blk, 0, st, OCC_ARGS); break;
         case K_NOISE:
@@ -521,12 +528,12 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
             if (P.tpb == 64) {  // 64-site slices (fused paths): 256-thread blocks, beta once per block, partial sums still per slice
                 const unsigned nb4 = (unsigned)((c.n + 255) / 256);
                 if (P.generic) hipLaunchKernelGGL((k_beta_draw<0, 0>), dim3((unsigned)c.C), dim3(256), 0, st, OCC_ARGS);
-                hipLaunchKernelGGL(pick_z_ob(tp), P.generic ? dim3(nb4 * 2, (unsigned)c.C) : shared_grid(c, 0, (int)nb4 * 2), dim3(256), 0, st, OCC_ARGS,
+                hipLaunchKernelGGL(z_ob, P.generic ? dim3(nb4 * 2, (unsigned)c.C) : shared_grid(c, 0, (int)nb4 * 2), dim3(256), 0, st, OCC_ARGS,
                                    (s->launch_sync ? 1 : 0) | 2 | P.zob_flags);
             } else {
                 if (P.generic) hipLaunchKernelGGL((k_beta_draw<0, 0>), dim3((unsigned)c.C), dim3(256), 0, st, OCC_ARGS);
                 else if (P.beta_split) hipLaunchKernelGGL(OCC_PICK_P(k_beta_draw, c.p), dim3((unsigned)c.C), dim3(64), 0, st, OCC_ARGS);
-                hipLaunchKernelGGL(pick_z_ob(tp), dim3((unsigned)c.nb_n * 2, (unsigned)c.C), blk, 0, st, OCC_ARGS,
+                hipLaunchKernelGGL(z_ob, dim3((unsigned)c.nb_n * 2, (unsigned)c.C), blk, 0, st, OCC_ARGS,
                                    (s->launch_sync ? 1 : 0) | P.zob_flags | (P.beta_split ? 4 : 0));
             }
             break;
@@ -898,6 +905,12 @@ int open_window(occ_sampler *s, int64_t n_iter, int64_t burnin, int64_t keep, bo
         }
         s->snap_sc = h;
         s->snap_parity = s->parity;
+        s->site_snapped = s->site_launch;
+        if (s->site_snapped) {  // the per-site sums are part of what the call is re-run from: no iteration is counted twice
+            if (!s->snap_site && (rc = dev_alloc(s, &s->snap_site, SITE_NACC * Cn + (size_t)c.C, false))) return rc;
+            HIP_TRY(hipMemcpyAsync(s->snap_site, c.site_acc, sizeof(double) * SITE_NACC * Cn, hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(s->snap_site + SITE_NACC * Cn, c.site_count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
+        }
         hipLaunchKernelGGL(k_snapshot, dim3((unsigned)std::min<size_t>((Cn + 255) / 256, 2048)), dim3(256), 0, s->stream, c.eta, s->snap_eta, c.z, s->snap_z, c.Xv, s->snap_x,
                            (unsigned long long)Cn, s->rsr.m > 0 ? s->rsr.theta : nullptr, s->snap_theta, (unsigned long long)c.C * (unsigned long long)std::max(s->rsr.m, 0),
                            run ? c.iter_clock : nullptr, c.sc, c.C, s->parity, dev_n, (uint32_t)burnin, (uint32_t)keep);
@@ -2908,6 +2921,10 @@ static int fallback_to_launch_per_step(occ_sampler *s)
     HIP_TRY(copy_on(s, c.z, s->snap_z, Cn, hipMemcpyDeviceToDevice));
     HIP_TRY(copy_on(s, c.Xv, s->snap_x, sizeof(double2) * Cn, hipMemcpyDeviceToDevice));
     if (s->rsr.m > 0) HIP_TRY(copy_on(s, s->rsr.theta, s->snap_theta, sizeof(double) * (size_t)c.C * s->rsr.m, hipMemcpyDeviceToDevice));
+    if (s->site_snapped) {
+        HIP_TRY(copy_on(s, c.site_acc, s->snap_site, sizeof(double) * SITE_NACC * Cn, hipMemcpyDeviceToDevice));
+        HIP_TRY(copy_on(s, c.site_count, s->snap_site + SITE_NACC * Cn, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
+    }
     for (auto &sc : s->snap_sc) sc.err = 0;
     if ((rc = write_scalars(s, s->snap_sc))) return rc;
     s->parity = s->snap_parity;
@@ -3026,6 +3043,68 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
     return rc;
 }
 
+// The state names of the per-site posterior sums: -> 0..4 the sum's place in Ctx::site_acc, SITE_COUNT, SITE_SWITCH; SITE_NONE.
+enum : int { SITE_NONE = -1, SITE_COUNT = -2, SITE_SWITCH = -3 };
+static int site_field(const std::string &nm)
+{
+    if (nm.compare(0, 5, "site_") != 0) return SITE_NONE;
+    if (nm == "site_stats") return SITE_SWITCH;
+    if (nm == "site_count") return SITE_COUNT;
+    if (nm == "site_psi") return SITE_PSI;
+    if (nm == "site_occ") return SITE_OCC;
+    if (nm == "site_z") return SITE_Z;
+    if (nm == "site_eta") return SITE_ETA;
+    if (nm == "site_eta2") return SITE_ETA2;
+    return SITE_NONE;
+}
+
+// occ_set_state of those names.  site_stats = 1: allocate at first use, zero the chain's sums and count, switch on;
+// 0: switch off (the sums stay readable).  The sums and the count themselves (checkpoint restore): only while the switch is on.
+// Which z kernel is launched follows "is any chain on"; a change drops the captured graphs (rebuilt by the next occ_run).
+// Nothing of the chain's state changes: omega_b of the coming iteration is NOT redrawn.
+static int set_site_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+{
+    if (s->probit) return set_error(s, OCC_E_STATE, "site summaries are not available for the probit model");
+    Ctx &c = s->ctx;
+    const size_t n = (size_t)c.n, Cn = (size_t)c.C * n;
+    int rc;
+    std::vector<ChainScalars> h;
+    if ((rc = read_scalars(s, h))) return rc;
+    if (field != SITE_SWITCH) {
+        if (!c.site_acc || !h[chain].site_on) return set_error(s, OCC_E_STATE, "site summaries are switched off for this chain (set site_stats to 1 first)");
+        if ((size_t)len != (field == SITE_COUNT ? (size_t)1 : n)) return set_error(s, OCC_E_STATE, "wrong length");
+        if (field == SITE_COUNT) {
+            if (!(in[0] >= 0.0) || in[0] != std::floor(in[0])) return set_error(s, OCC_E_STATE, "site_count is a whole number of iterations");
+            HIP_TRY(copy_on(s, c.site_count + chain, in, sizeof(double), hipMemcpyHostToDevice));
+        } else {
+            HIP_TRY(copy_on(s, c.site_acc + (size_t)field * Cn + chain * n, in, sizeof(double) * n, hipMemcpyHostToDevice));
+        }
+        return OCC_OK;
+    }
+    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
+    const bool on = in[0] != 0.0;
+    if (!on && !c.site_acc) return OCC_OK;  // never switched on: nothing to switch off
+    WAIT_TRY(s->side);
+    if (on && !c.site_acc) {
+        if ((rc = dev_alloc(s, &c.site_acc, SITE_NACC * Cn))) return rc;
+        if ((rc = dev_alloc(s, &c.site_count, (size_t)c.C))) return rc;
+        HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
+    }
+    if (on) {
+        for (int q = 0; q < SITE_NACC; ++q) HIP_TRY(fill_on(s, c.site_acc + (size_t)q * Cn + chain * n, 0, sizeof(double) * n));
+        HIP_TRY(fill_on(s, c.site_count + chain, 0, sizeof(double)));
+    }
+    h[chain].site_on = on ? 1u : 0u;
+    if ((rc = write_scalars(s, h))) return rc;
+    bool any = false;
+    for (const auto &sc : h) any = any || sc.site_on != 0u;
+    if (any != s->site_launch) {
+        destroy_graph(s);
+        s->site_launch = any;
+    }
+    return OCC_OK;
+}
+
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len)
 {
     if (!s || !name || !len) return OCC_E_BADARG;
@@ -3037,6 +3116,11 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     const std::string nm(name);
     const size_t n = (size_t)c.n, R = (size_t)c.R;
     std::vector<double> v;
+    const int site_q = site_field(nm);
+    if (site_q != SITE_NONE) {
+        if (s->probit) return set_error(s, OCC_E_STATE, "site summaries are not available for the probit model");
+        if (!c.site_acc) return set_error(s, OCC_E_STATE, "site summaries have not been switched on for this handle (set site_stats to 1 first)");
+    }
     if (s->probit) {
         const int prc = pb_get_state(s, chain, nm, v);
         if (prc) return prc;
@@ -3081,6 +3165,9 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     else if (nm == "tau") v.assign(1, sc.tau);
     else if (nm == "minres_itn") v.assign(1, (double)sc.minres_itn_last);
     else if (nm == "iter") v.assign(1, (double)it);
+    else if (site_q == SITE_SWITCH) v.assign(1, sc.site_on ? 1.0 : 0.0);
+    else if (site_q == SITE_COUNT) rc = pull(c.site_count + chain, 1);
+    else if (site_q >= 0) rc = pull(c.site_acc + (size_t)site_q * c.C * n + chain * n, n);
     else if (nm == "rsr_gram" && s->rsr.m > 0) {
         // tests only, m x m row-major, of the last theta update.  m <= RSR_MAX_DIM: K' diag(omega_b) K (upper 16 x 16 tiles).
         // m > RSR_MAX_DIM: k_rsrb_assemble adds tau Qr in place and k_rsrb_step overwrites each 32-row panel's rows right of
@@ -3112,6 +3199,7 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     HIP_TRY(hipSetDevice(s->device));
     WAIT_TRY(s->stream);
     const std::string nm(name);
+    if (site_field(nm) != SITE_NONE) return set_site_state(s, chain, site_field(nm), in, len);
     if (s->probit) return pb_set_state(s, chain, nm, in, len);
     const size_t n = (size_t)c.n, R = (size_t)c.R;
     auto need = [&](size_t want) { return (size_t)len == want; };
@@ -3278,6 +3366,9 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
     if (s->probit) return pb_profile(s, reps, counts, total_us);
+    // (the timing loops always launch k_z_ob itself, never the twin that keeps the per-site sums; no captured graph of the
+    // handle is replayed here)
+    struct PlainZob { occ_sampler *s; bool old; explicit PlainZob(occ_sampler *p) : s(p), old(p->site_launch) { s->site_launch = false; } ~PlainZob() { s->site_launch = old; } } plain_z_ob(s);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops
     if (rc) return rc;
     // The fused iteration kernel first, IN SITU: `reps` real iterations continue the chains from where they are

@@ -107,8 +107,11 @@ struct ChainScalars {
     uint32_t bar_base;         // arrivals counted so far by the chain's barrier counter (occ_iter.hpp), never reset
     int32_t err;               // OCC_E_* raised on device
     int32_t minres_itn_last;
+    uint32_t site_on;          // per-site posterior sums (Ctx::site_acc) are kept for this chain; sits where the layout had padding
     unsigned long long krylov_total, krylov_sq_total, solves, carries;
 };
+
+static_assert(sizeof(ChainScalars) == 640, "ChainScalars: the layout every kernel was compiled against");
 
 // Variates handed in by the caller instead of the chain's Philox streams: the per-conditional entry points of the C ABI
 // (occ_cond_*, include/occ_gibbs.h) run the kernels below in their INJ instantiation, which take the standard gamma variate
@@ -183,6 +186,10 @@ struct Ctx {
     int share_on;
     int tile_first[3][9], tile_most[3];
     int surplus_last;  // bit k: kernel k's surplus workgroups come last (see tile_of_block_shared)
+    // Per-site posterior sums (state names site_*; null until a chain is first switched on): five quantities, each [C][n] --
+    // psi, P(z = 1 | rest), z, eta, eta^2 -- added to by the z update of k_z_ob_stats, and the iterations added per chain.
+    double *site_acc;
+    double *site_count;  // [C]
 };
 
 // ---- reductions ----------------------------------------------------------------------------------
@@ -1975,13 +1982,39 @@ __global__ void __launch_bounds__(512) k_alpha_draw(OCC_KARGS, int sync_on)
 // roles, so the two run concurrently without a second stream.
 // The z update of one site (logit.py:234-252) and the record of one iteration (base.py:238-239): shared by k_z_ob
 // and by the last phase of k_iter (occ_iter.hpp), contractions explicit so that both evaluate the same operations.
-template <int P, int INJ = 0>
+// One iteration's terms of the per-site sums (Ctx::site_acc): the site's own thread, plain read-modify-writes in iteration
+// order -- the sums do not depend on block size, path or placement.  (eta^2 enters by one fused multiply-add, stated.)
+enum : int { SITE_PSI = 0, SITE_OCC = 1, SITE_Z = 2, SITE_ETA = 3, SITE_ETA2 = 4, SITE_NACC = 5 };
+__device__ __forceinline__ void site_add(const Ctx &c, int chain, int i, double psi, double occ, double z, double eta)
+{
+    const size_t Cn = (size_t)c.C * c.n;
+    double *a = c.site_acc + (size_t)chain * c.n + i;
+    a[SITE_PSI * Cn] += psi;
+    a[SITE_OCC * Cn] += occ;
+    a[SITE_Z * Cn] += z;
+    a[SITE_ETA * Cn] += eta;
+    a[SITE_ETA2 * Cn] = fma(eta, eta, a[SITE_ETA2 * Cn]);
+}
+
+// STATS (k_z_ob_stats only; `stats_on`: this chain, this iteration): the site's psi, P(z = 1 | rest), new z, eta and eta^2 go
+// into the per-site sums -- at a site with a detection (psi, 1, 1, eta, eta^2).
+template <int P, int INJ = 0, int STATS = 0>
 __device__ __forceinline__ void z_update_site(const Ctx &c, uint64_t key, int chain, int i, uint32_t it, const double (&beta)[P],
-                                              const double (&alpha)[MAXC], double eta_i)
+                                              const double (&alpha)[MAXC], double eta_i, bool stats_on = false)
 {
     const int sidx = c.site_sidx[i];
     const bool not_surveyed = sidx < 0;
-    if (!not_surveyed && c.obs_site[sidx]) return;  // detection seen: z stays 1 (base.py:116-118)
+    if (!not_surveyed && c.obs_site[sidx]) {  // detection seen: z stays 1 (base.py:116-118)
+        if constexpr (STATS) {
+            if (stats_on) {
+                double xb = 0.0;
+#pragma unroll
+                for (int a = 0; a < P; ++a) xb = fma(c.Xt[(size_t)a * c.n + i], beta[a], xb);
+                site_add(c, chain, i, expit(xb + eta_i), 1.0, 1.0, eta_i);
+            }
+        }
+        return;
+    }
     const int n = c.n, Q = c.q;
     double xb = 0.0;
 #pragma unroll
@@ -2004,6 +2037,9 @@ __device__ __forceinline__ void z_update_site(const Ctx &c, uint64_t key, int ch
     }
     const double u = INJ ? c.inj->z_u[i] : block_uniform(key, (uint32_t)i, 0, it, STREAM_Z);
     c.z[(size_t)chain * n + i] = (u < pr) ? 1 : 0;
+    if constexpr (STATS) {
+        if (stats_on) site_add(c, chain, i, num1, pr, (u < pr) ? 1.0 : 0.0, eta_i);
+    }
 }
 template <int P>
 __device__ __forceinline__ void record_draws(const Ctx &c, const ChainScalars &sc, int chain, uint32_t it, const double (&alpha)[MAXC],
@@ -2021,7 +2057,7 @@ __device__ __forceinline__ void record_draws(const Ctx &c, const ChainScalars &s
     row[Q + P] = tau;
 }
 
-template <int P>
+template <int P, int STATS = 0>
 __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict__ scs, int chain_base, int e, bool synced, unsigned seq,
                                           bool per_wave, int debug_skip = 0,  // debug_skip (timing experiments): 1 = no z update, 2 = no omega_b draw
                                           bool beta_ready = false)            // beta was drawn by k_beta_draw, the previous kernel of the stream
@@ -2109,18 +2145,36 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
     }
     if (writer) record_draws<P>(c, sc, chain, it, alpha, beta, sc.tau);
     const int n = c.n, i = (blk >> 1) * blockDim.x + threadIdx.x;
+    if constexpr (STATS) {
+        // a kept iteration of a chain whose switch is on (the window's upper end does not matter); this pass completes it
+        const bool stats_on = sc.site_on != 0u && it - sc.it_base >= sc.burnin;
+        if (writer && stats_on && !(debug_skip & 1)) c.site_count[chain] += 1.0;
+        if (i >= n || (debug_skip & 1)) return;
+        z_update_site<P, 0, 1>(c, sc.key, chain, i, it, beta, alpha, c.eta[(size_t)chain * n + i], stats_on);
+    } else {
     if (i >= n || (debug_skip & 1)) return;
     z_update_site<P>(c, sc.key, chain, i, it, beta, alpha, c.eta[(size_t)chain * n + i]);
+    }
 }
 
 // The z update of one site with run-time numbers of covariates (generic path); alpha and beta come from the chain's
 // scalars.  Same operations as z_update_site.
-template <int INJ>
-__device__ __forceinline__ void z_update_site_g(const Ctx &c, const ChainScalars &sc, int chain, int i, uint32_t it, double eta_i)
+template <int INJ, int STATS = 0>
+__device__ __forceinline__ void z_update_site_g(const Ctx &c, const ChainScalars &sc, int chain, int i, uint32_t it, double eta_i,
+                                                bool stats_on = false)
 {
     const int sidx = c.site_sidx[i];
     const bool not_surveyed = sidx < 0;
-    if (!not_surveyed && c.obs_site[sidx]) return;
+    if (!not_surveyed && c.obs_site[sidx]) {
+        if constexpr (STATS) {
+            if (stats_on) {
+                double xb = 0.0;
+                for (int a = 0; a < c.p; ++a) xb = fma(c.Xt[(size_t)a * c.n + i], sc.beta[a], xb);
+                site_add(c, chain, i, expit(xb + eta_i), 1.0, 1.0, eta_i);
+            }
+        }
+        return;
+    }
     const int n = c.n, P = c.p, Q = c.q;
     double xb = 0.0;
     for (int a = 0; a < P; ++a) xb = fma(c.Xt[(size_t)a * n + i], sc.beta[a], xb);
@@ -2140,10 +2194,14 @@ __device__ __forceinline__ void z_update_site_g(const Ctx &c, const ChainScalars
     }
     const double u = INJ ? c.inj->z_u[i] : block_uniform(sc.key, (uint32_t)i, 0, it, STREAM_Z);
     c.z[(size_t)chain * n + i] = (u < pr) ? 1 : 0;
+    if constexpr (STATS) {
+        if (stats_on) site_add(c, chain, i, num1, pr, (u < pr) ? 1.0 : 0.0, eta_i);
+    }
 }
 
 // k_z_ob of the generic path: beta has been drawn by k_beta_draw<0> (the previous kernel of the stream); this path never
 // runs with the device-counter hand-overs (it is not taken by the fused kernel nor by the reduced-rank model).
+template <int STATS = 0>
 __device__ __forceinline__ void z_ob_body_g(const Ctx &c, ChainScalars *__restrict__ scs, int chain_base, int e, bool per_wave, int debug_skip)
 {
     const Tile tile = tile_of_block(chain_base);
@@ -2174,8 +2232,15 @@ __device__ __forceinline__ void z_ob_body_g(const Ctx &c, ChainScalars *__restri
         }
     }
     const int n = c.n, i = (blk >> 1) * blockDim.x + threadIdx.x;
+    if constexpr (STATS) {
+        const bool stats_on = sc.site_on != 0u && it - sc.it_base >= sc.burnin;
+        if (writer && stats_on && !(debug_skip & 1)) c.site_count[chain] += 1.0;
+        if (i >= n || (debug_skip & 1)) return;
+        z_update_site_g<0, 1>(c, sc, chain, i, it, c.eta[(size_t)chain * n + i], stats_on);
+    } else {
     if (i >= n || (debug_skip & 1)) return;
     z_update_site_g<0>(c, sc, chain, i, it, c.eta[(size_t)chain * n + i]);
+    }
 }
 
 // beta ~ N(A^-1 r, A^-1) of every chain by ONE wave per chain, for problems with so many partial sums (blocks) that
@@ -2233,6 +2298,21 @@ __global__ void __launch_bounds__(256, 3) k_z_ob(OCC_KARGS, int flags)  // bit 0
     }
 }
 
+// k_z_ob with the per-site posterior sums (Ctx::site_acc): launched in k_z_ob's place while a chain of the handle has its
+// switch on.  A kernel of its own, so that k_z_ob itself -- register-sensitive, see above -- stays the code it was.
+template <int P>
+__global__ void __launch_bounds__(256, 3) k_z_ob_stats(OCC_KARGS, int flags)  // flags: k_z_ob's
+{
+    __builtin_amdgcn_s_setprio(3);
+    const Ctx &c = *cp;
+    if constexpr (P == 0) {
+        z_ob_body_g<1>(c, scs, chain_base, e, (flags & 2) != 0, (flags >> 3) & 3);
+    } else {
+        const bool synced = (flags & 1) && c.sync != nullptr;
+        const unsigned seq = synced ? c.sync[SYNC_MAIN] : 0u;
+        z_ob_body<P, 1>(c, scs, chain_base, e, synced, seq, (flags & 2) != 0, (flags >> 3) & 3, (flags & 4) != 0);
+    }
+}
 
 // beta draw and / or z update of one chain with INJECTED variates (occ_cond_beta, occ_cond_z): the arithmetic is k_z_ob's,
 // through the same device functions (reduce_partials in the same order, precision_mvnorm_reg, z_update_site); nothing is

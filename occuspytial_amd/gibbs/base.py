@@ -113,20 +113,37 @@ class GibbsBase:
                 self.chain.append(self.state.posteriors)
         return self.chain
 
-    def sample(self, size, burnin=0, start=None, chains=2, progressbar=True):
+    def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False):
         """Draw ``size`` iterations per chain and return the kept ``alpha``, ``beta``, ``tau`` draws.
 
         Same contract as the reference (``base.py:243-291``): ``burnin < size`` else ``ValueError``;
         ``chains >= 1`` else ``ValueError``; ``start`` may give ``alpha``, ``beta``, ``tau``, ``eta``;
         the result indexes as ``out['alpha'] -> (chains, size - burnin, q)`` etc.
+
+        ``site_summaries=True`` (samplers that run on the engine; logit link) additionally accumulates the per-site
+        posterior map on the device over the kept iterations -- occupancy probability, P(z = 1 | data), the spatial effect
+        and its sd -- and returns it as ``out.sites``, a :class:`~occuspytial_amd.sites.SiteSummary` (``None`` otherwise).
         """
         if burnin >= size:
             raise ValueError('burnin value cannot be larger than sample size')
         if chains < 1:
             raise ValueError('chains must a positive integer.')
+        extra = {}
+        if site_summaries:
+            self._check_site_summaries()
+            extra['site_summaries'] = True
         samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start,
-                                  progressbar=progressbar)
-        return PosteriorParameter(*samples)
+                                  progressbar=progressbar, **extra)
+        out = PosteriorParameter(*samples)
+        if site_summaries:
+            out.sites = self.__dict__.pop('_sites')
+        return out
+
+    def _check_site_summaries(self):
+        """Per-site summaries are accumulated by the engine's z update: a sampler with a Python ``step`` has none."""
+        if not hasattr(self, '_run_chains'):
+            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: site summaries are accumulated by the '
+                                      'device engine only')
 
     def copy(self):
         """A shallow copy with its own generator spawned from this one's seed sequence

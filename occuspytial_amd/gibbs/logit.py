@@ -121,11 +121,19 @@ class LogitICARGibbs(GibbsBase):
             np.savez(path, **ckpt)
         return ckpt
 
-    def resume(self, checkpoint, size, progressbar=True):
+    def _site_switch(self, eng, on):
+        try:
+            eng.site_stats(on)
+        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
+            raise ValueError(f'the loaded engine library has no site summaries ({exc}): rebuild it') from None
+
+    def resume(self, checkpoint, size, progressbar=True, site_summaries=False):
         """Continue the chains of ``checkpoint`` (a dict from :meth:`checkpoint` or the path of its ``.npz``)
         for ``size`` more iterations on this sampler's problem.  Returns a ``PosteriorParameter`` of the new
         draws; every chain's ``Chain`` is the continuation (use ``Chain.expand`` / ``append`` to join them to
-        earlier draws).  The result equals the tail of an uninterrupted run bit for bit."""
+        earlier draws).  The result equals the tail of an uninterrupted run bit for bit.  ``site_summaries=True``: the
+        per-site sums go on from those the checkpoint holds (from zero if it holds none); the result's ``sites`` covers
+        every iteration accumulated so far, those before the checkpoint included."""
         from ..posterior import PosteriorParameter
         from tqdm.auto import tqdm
         if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, '__fspath__'):
@@ -137,6 +145,10 @@ class LogitICARGibbs(GibbsBase):
         self.__dict__['_stepping'] = False
         eng = self._get_engine([int(k) for k in np.asarray(checkpoint['keys'])])
         eng.restore(checkpoint)
+        if site_summaries:
+            self._check_site_summaries()
+            if 'site_stats' not in checkpoint:
+                self._site_switch(eng, True)
         alpha = np.zeros((C, size, self._problem.q))
         beta = np.zeros((C, size, self._problem.p))
         tau = np.zeros((C, size))
@@ -152,14 +164,21 @@ class LogitICARGibbs(GibbsBase):
         chains = [Chain._from_arrays({'alpha': alpha[c], 'beta': beta[c], 'tau': tau[c]}) for c in range(C)]
         self.chain = chains[0]
         self._pull_state(eng, 0)
-        return PosteriorParameter(*chains)
+        out = PosteriorParameter(*chains)
+        if site_summaries:
+            from ..sites import SiteSummary
+            out.sites = SiteSummary.from_engine(eng)
+        return out
 
     # ------------------------------------------------------------------ batched chains
-    def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True):
+    def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False):
         """All chains of one ``sample`` call as one device batch.
 
         Mirrors ``GibbsBase._run`` (base.py:214-241) per chain: start values from the chain's own
         generator (or the ``start`` dict), then ``size`` iterations keeping those ``>= burnin``.
+        ``site_summaries``: burn-in chunks run with the engine's per-site sums switched off; the switch goes on (which
+        zeroes them) right before the first chunk that keeps a draw, and inside that chunk the engine itself counts
+        only the iterations past the chunk's burn-in.  With the default no call about them reaches the engine.
         """
         from tqdm.auto import tqdm
 
@@ -174,6 +193,9 @@ class LogitICARGibbs(GibbsBase):
         for c, s in enumerate(samplers):
             self._push_start(eng, c, s.state)
             eng.set('z', z0, c)
+        if site_summaries or getattr(eng, '_site_on', False):   # (a reused engine that an earlier call left switched on)
+            self._site_switch(eng, False)   # (also the early answer of a library that does not know site summaries)
+        sites_on = False
 
         C = len(samplers)
         keep = size - burnin
@@ -189,6 +211,9 @@ class LogitICARGibbs(GibbsBase):
             if b == step:  # the whole chunk is burn-in: run it, keep only its last draw, drop it
                 eng.run(step, step - 1)
             else:
+                if site_summaries and not sites_on:
+                    self._site_switch(eng, True)
+                    sites_on = True
                 a_, b_, t_ = eng.run(step, b)
                 m = step - b
                 alpha[:, kept:kept + m], beta[:, kept:kept + m], tau[:, kept:kept + m] = a_, b_, t_
@@ -205,6 +230,9 @@ class LogitICARGibbs(GibbsBase):
             s.chain = ch
             chains.append(ch)
         self._pull_state(eng, 0)
+        if site_summaries:
+            from ..sites import SiteSummary
+            self.__dict__['_sites'] = SiteSummary.from_engine(eng)
         return chains
 
 

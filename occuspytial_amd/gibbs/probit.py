@@ -97,6 +97,10 @@ class ProbitRSRGibbs(GibbsBase):
         st = self.state
         st.eps = eng.get('eps', chain)
 
+    def _check_site_summaries(self):
+        # (its z update conditions on the auxiliary eps: what "psi" should mean there is a modelling decision not yet made)
+        raise NotImplementedError('site summaries are not available for the probit model')
+
     step = LogitICARGibbs.step
     checkpoint = LogitICARGibbs.checkpoint
     resume = LogitICARGibbs.resume

@@ -38,6 +38,8 @@ class PosteriorParameter:
     ``post['alpha']`` is an ndarray ``(chains, draws, q)``, ``post['tau']`` is ``(chains, draws)``.
     """
 
+    sites = None   # a SiteSummary when sample(..., site_summaries=True) asked for the per-site posterior map
+
     def __init__(self, *chains):
         self.data = self._create_inference_data(chains)
 
