@@ -21,7 +21,8 @@
 //                  the second role of k_z_ob
 //   k_noise        the alpha draw of this iteration (logit.py:224; first block of every chain), then the variates of the
 //                  eta right-hand side that depend on nothing but the iteration number, one iteration ahead: site
-//                  normals and the edge form of the ICAR prior term (logit.py:75-77), tau's gamma variate
+//                  normals and the edge form of the ICAR prior term (logit.py:75-77), tau's gamma variate, the standard
+//                  normals of beta's draw
 //   k_eta_init     tau ~ Gamma (logit.py:206-209); rhs y (logit.py:213, 78); r1 = [y;1] - Lambda x0
 //   k_minres       one Lanczos/MINRES iteration of the joint 2n system per launch
 //                  (scipy _isolve/minres.py as called at logit.py:87)
@@ -29,7 +30,7 @@
 //   k_omega_a      omega_a ~ PG(1, w'alpha) for rows of existing sites; W' Omega W, W'(y - 1/2)
 //                  (logit.py:180-193, 219-223)
 //   k_alpha_draw   alpha draw (logit.py:224) as a kernel of its own: occ_cond_alpha (injected variates) and occ_profile
-//   k_z_ob         beta draw (logit.py:232, every wave); role 0: z update (logit.py:234-252), record
+//   k_z_ob         beta draw (logit.py:232, every wave, with the normals k_noise drew ahead); role 0: z update (logit.py:234-252), record
 //                  (alpha, beta, tau) (base.py:238-239), advance the iteration; role 1 (other half of the
 //                  grid): omega_b of the NEXT iteration
 //   k_gate         head of a side-stream sequence when the streams hand over through device counters
@@ -101,6 +102,9 @@ struct ChainScalars {
     double tau;
     double tau_gamma[2];       // the standard gamma variate of tau's draw of iteration t in [t & 1] (logit.py:209): it depends on
                                // nothing but (key, t), so k_noise draws it one iteration ahead, off the critical path
+    double beta_eps[2][MAXG];  // likewise the p standard normals of beta's draw of iteration t in [t & 1] (distributions.pyx:95-96):
+                               // block_normal(key, k, 0, t, STREAM_BETA), drawn by k_noise beside tau_gamma, read by every beta
+                               // draw of a running chain (k_z_ob, k_z_ob_stats, k_beta_draw); the INJ kernels keep their own
     uint64_t key;
     Ctl ctl[2], mid[2];
     uint32_t it_stop, it_base, burnin, keep;
@@ -111,7 +115,7 @@ struct ChainScalars {
     unsigned long long krylov_total, krylov_sq_total, solves, carries;
 };
 
-static_assert(sizeof(ChainScalars) == 640, "ChainScalars: the layout every kernel was compiled against");
+static_assert(sizeof(ChainScalars) == 640 + 2 * MAXG * 8, "ChainScalars: the layout every kernel was compiled against");
 
 // Variates handed in by the caller instead of the chain's Philox streams: the per-conditional entry points of the C ABI
 // (occ_cond_*, include/occ_gibbs.h) run the kernels below in their INJ instantiation, which take the standard gamma variate
@@ -403,6 +407,52 @@ __device__ __forceinline__ void block_partials(const double (&v)[NQ], double *ou
 
 // Every block reduces all nb partials of NQ quantities in the same fixed order (registers only when the
 // block is one wave; otherwise wave 0 reduces and broadcasts through LDS).
+// Several rounds of loads are in flight at a time (a plain "load, add" loop waits for every round trip in
+// turn); the sums are accumulated in the same order as ever, rounds past the end add an exact 0.
+template <int NQ>
+struct PartialRounds {
+    static constexpr int R = NQ <= 8 ? 4 : (NQ <= 20 ? 2 : 1);  // registers: R * NQ doubles
+};
+// One batch of rounds: lane l its slices b0 + l, b0 + l + 64, ... of each quantity, clamped to the last slice (and counted
+// as zero past it where they are added).  Nothing but loads -- no use of a loaded value, hence no wait: a caller may issue the first batch (b0 = 0) long before it adds it (reduce_partials_wave<NQ, true>).
+template <int NQ>
+__device__ __forceinline__ void partials_load(const double *part, int nb, int b0, double (&v)[PartialRounds<NQ>::R][NQ])
+{
+    constexpr int R = PartialRounds<NQ>::R;
+    const int lane = threadIdx.x & 63;
+    // (a pointer read from Ctx is a generic one to the compiler, and generic loads are counted with the scalar and LDS
+    // traffic as well: a wait for a control word would wait for these.  They are in global memory: said so.)
+    const __attribute__((address_space(1))) double *gpart = (const __attribute__((address_space(1))) double *)part;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int b = b0 + lane + 64 * r;
+        const int bc = min(b, nb - 1);
+#pragma unroll
+        for (int qi = 0; qi < NQ; ++qi) v[r][qi] = gpart[qi * nb + bc];
+    }
+}
+// The reducing wave's sums: the additions of every batch in turn, rounds then quantities.  PRE: the first batch has been
+// loaded by the caller (partials_load(part, nb, 0, v)).  The loop is uniform -- a lane whose slices are all past the end
+// adds exact zeros to a sum that is +0 or was formed from +0: the same bits as not adding at all.
+template <int NQ, bool PRE>
+__device__ __forceinline__ void reduce_partials_wave(const double *part, int nb, double (&v)[PartialRounds<NQ>::R][NQ], double (&out)[NQ])
+{
+    constexpr int R = PartialRounds<NQ>::R;
+    double acc[NQ];
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) acc[qi] = 0.0;
+    for (int b0 = 0; b0 < nb; b0 += 64 * R) {
+        if (!PRE || b0 > 0) partials_load<NQ>(part, nb, b0, v);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const bool in = b0 + (int)(threadIdx.x & 63) + 64 * r < nb;
+#pragma unroll
+            for (int qi = 0; qi < NQ; ++qi) acc[qi] += in ? v[r][qi] : 0.0;
+        }
+    }
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) out[qi] = wave_sum(acc[qi]);
+}
 template <int NQ>
 __device__ __forceinline__ void reduce_partials(const double *part, int nb, double (&out)[NQ])
 {
@@ -410,32 +460,8 @@ __device__ __forceinline__ void reduce_partials(const double *part, int nb, doub
     const int lane = threadIdx.x & 63;
     const bool one_wave = blockDim.x == 64;
     if (one_wave || threadIdx.x < 64) {
-        double acc[NQ];
-#pragma unroll
-        for (int qi = 0; qi < NQ; ++qi) acc[qi] = 0.0;
-        // several rounds of loads in flight at a time (a plain "load, add" loop waits for every round trip in
-        // turn); the sums are accumulated in the same order as ever, rounds past the end add an exact 0
-        constexpr int R = NQ <= 8 ? 4 : (NQ <= 20 ? 2 : 1);  // registers: R * NQ doubles
-        for (int b0 = lane; b0 < nb; b0 += 64 * R) {
-            double v[R][NQ];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int b = b0 + 64 * r;
-                const int bc = min(b, nb - 1);
-#pragma unroll
-                for (int qi = 0; qi < NQ; ++qi) {
-                    const double t = part[qi * nb + bc];
-                    v[r][qi] = (b < nb) ? t : 0.0;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-#pragma unroll
-                for (int qi = 0; qi < NQ; ++qi) acc[qi] += v[r][qi];
-            }
-        }
-#pragma unroll
-        for (int qi = 0; qi < NQ; ++qi) out[qi] = wave_sum(acc[qi]);
+        double v[PartialRounds<NQ>::R][NQ];
+        reduce_partials_wave<NQ, false>(part, nb, v, out);
         if (!one_wave && lane == 0) {
 #pragma unroll
             for (int qi = 0; qi < NQ; ++qi) s_tot[qi] = out[qi];
@@ -591,10 +617,10 @@ __device__ inline bool precision_mvnorm_dev(int d, const double *acc /* nacc(d):
 
 // Same draw with the dimension known at compile time, entirely in registers; executed redundantly by
 // every lane (uniform inputs, uniform control flow), so no broadcast is needed afterwards.
-template <int D>
-__device__ __forceinline__ bool precision_mvnorm_reg(const double (&acc)[nacc(D)], const double *prec0, const double *pbm,
-                                                     uint64_t key, uint32_t it, uint32_t stream, double (&out)[D],
-                                                     const double *eps_inj = nullptr)
+// `normal(k)`: the k-th standard normal of the draw, asked for once each, in order.
+template <int D, class Normal>
+__device__ __forceinline__ bool precision_mvnorm_with(const double (&acc)[nacc(D)], const double *prec0, const double *pbm, double (&out)[D],
+                                                      Normal normal)
 {
     double U[D][D], r[D], o[D];
     int t = 0;
@@ -625,7 +651,7 @@ __device__ __forceinline__ bool precision_mvnorm_reg(const double (&acc)[nacc(D)
     for (int i = 0; i < D; ++i) o[i] = 0.0;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
-        const double e = eps_inj ? eps_inj[k] : block_normal(key, (uint32_t)k, 0, it, stream);
+        const double e = normal(k);
 #pragma unroll
         for (int i = k; i < D; ++i) o[i] += U[k][i] * e;
     }
@@ -650,6 +676,16 @@ __device__ __forceinline__ bool precision_mvnorm_reg(const double (&acc)[nacc(D)
     return ok;
 }
 
+// ... with the normals of the sub-streams (key, k, 0, it, stream), or the caller's from memory
+template <int D>
+__device__ __forceinline__ bool precision_mvnorm_reg(const double (&acc)[nacc(D)], const double *prec0, const double *pbm,
+                                                     uint64_t key, uint32_t it, uint32_t stream, double (&out)[D],
+                                                     const double *eps_inj = nullptr)
+{
+    return precision_mvnorm_with<D>(acc, prec0, pbm, out,
+                                    [=](int k) { return eps_inj ? eps_inj[k] : block_normal(key, (uint32_t)k, 0, it, stream); });
+}
+
 
 // ---- Stream hand-overs without events ---------------------------------------------------------------
 // Launch sequence number j (one Gibbs iteration of every chain) is  k_iter(j), k_z_ob(j)  on the main stream
@@ -659,6 +695,10 @@ __device__ __forceinline__ bool precision_mvnorm_reg(const double (&acc)[nacc(D)
 //   sync[SYNC_MAIN]   = j  set by k_iter(j):  k_z_ob(j-1) is complete     k_gate(j) waits for >= j   (z, control words)
 //   sync[SYNC_NOISE]  = j  set by k_gate(j):  k_noise(j-1) is complete    k_iter(j) waits for >= j   (noise of j)
 //   sync[SYNC_ALPHA] += 1 per chain by k_noise(j) once alpha of j is stored       k_z_ob(j) waits for >= (j+1) C (alpha of j)
+// The normals of beta's draw of iteration t (ChainScalars::beta_eps, written by k_noise(j-1) beside tau's gamma variate) need
+// no word of their own: k_iter(j) has waited for k_noise(j-1) (SYNC_NOISE) and k_z_ob(j), which reads them, follows k_iter(j)
+// in stream order; k_noise(j) writes the slot of the other parity, and k_noise(j+1) cannot start before k_z_ob(j) is
+// complete (its sequence's head waits for SYNC_MAIN >= j+1, set by k_iter(j+1)).
 // Every kernel sets before it waits, so the two streams cannot wait for each other.  Each stream counts its
 // own sequences in words only it touches (SYNC_MAIN_SEQ + parity of the sequence: the last kernel of a main-stream
 // sequence writes the word of the NEXT sequence's parity, so no kernel reads a word that is written while it runs;
@@ -699,6 +739,15 @@ __device__ __forceinline__ double load_agent(const double *p)
 {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// A wave-uniform value pinned to scalar registers ("Rules"): what arrives through LDS, through a load the
+// compiler cannot prove unclobbered or through a merge with such a value is otherwise kept once per lane -- and everything
+// derived from it (Philox's key schedule: twenty words) with it.
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t v)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ double uniform_f64(double v) { return __longlong_as_double((long long)uniform_u64((uint64_t)__double_as_longlong(v))); }
 
 // Do the two streams run beside each other?  The hand-overs above presume it.  k_stream_probe_wait (side stream, launched
 // first) looks for the word k_stream_probe_set (main stream, launched second) writes: streams that share a hardware queue
@@ -801,20 +850,32 @@ __device__ __forceinline__ double quad_site(const Ctx &c, const double *eta, int
 // omega_b ~ PG(1, x_i'beta + eta_i) of iteration `it` into omega_b[it & 1], and the partials of eta'Q eta
 // (logit.py:195-204, 208).  `blk` is the block index within the role's own grid.
 template <int P>
-__device__ __forceinline__ void omega_b_body(const Ctx &c, const ChainScalars &sc, const double (&beta)[P], int chain, uint32_t it, int blk,
+__device__ __forceinline__ void omega_b_body(const Ctx &c, uint64_t key, const double (&beta)[P], int chain, uint32_t it, int blk,
                                              bool per_wave = false)
 {
-    const int n = c.n, i = blk * blockDim.x + threadIdx.x;
+    const int n = c.n;
+    const double *eta = c.eta + (size_t)chain * n;
+    double om = 0.0;
+    {
+        const int i = blk * blockDim.x + threadIdx.x;
+        if (i < n) {
+            double xb = 0.0;
+#pragma unroll
+            for (int a = 0; a < P; ++a) xb += c.Xt[(size_t)a * n + i] * beta[a];
+            om = pg1_draw(key, (uint32_t)i, it, STREAM_OMEGA_B, xb + eta[i]);
+        }
+    }
+    // The draw leaves no vector register to spare at three workgroups per CU (its own constants and state: ~ 160 of 168), so
+    // nothing per lane is carried across it but its result: the site's number is formed again from the thread's (the empty
+    // statement keeps the compiler from recognising the same value and holding it, 64 bits wide, through the draw) and
+    // eta_i is read again beside its neighbours for eta'Q eta -- from the cache, not from scratch.
+    int t = (int)threadIdx.x;
+    asm volatile("" : "+v"(t));
+    const int i = blk * (int)blockDim.x + t;
     double quad[1] = {0.0};
     if (i < n) {
-        const size_t ci = (size_t)chain * n + i;
-        const double *eta = c.eta + (size_t)chain * n;
-        double xb = 0.0;
-#pragma unroll
-        for (int a = 0; a < P; ++a) xb += c.Xt[(size_t)a * n + i] * beta[a];
-        const double eta_i = eta[i];
-        c.omega_b[it & 1][ci] = pg1_draw(sc.key, (uint32_t)i, it, STREAM_OMEGA_B, xb + eta_i);
-        quad[0] = quad_site(c, eta, i, eta_i);
+        c.omega_b[it & 1][(size_t)chain * n + i] = om;
+        quad[0] = quad_site(c, eta, i, eta[i]);
     }
     if (per_wave) {  // several waves per block, partial sums still per 64-site slice (c.nb_n counts slices)
         const double t = wave_sum(quad[0]);
@@ -865,7 +926,7 @@ __global__ void __launch_bounds__(256) k_omega_b(OCC_KARGS)
         double beta[P];
 #pragma unroll
         for (int a = 0; a < P; ++a) beta[a] = sc.beta[a];
-        omega_b_body<P>(c, sc, beta, chain, ctl.it, blk);
+        omega_b_body<P>(c, sc.key, beta, chain, ctl.it, blk);
     }
 }
 
@@ -996,6 +1057,12 @@ __global__ void __launch_bounds__(256) k_noise(OCC_KARGS, int ahead, int sync_on
     if (blk == 0 && threadIdx.x == 0) {  // tau's standard gamma variate of that iteration (the rate comes later)
         Cursor g(sc.key, 0u, it_for, STREAM_TAU);
         sc.tau_gamma[it_for & 1] = std_gamma(g, c.tau_shape);
+    }
+    // ... and the standard normals of beta's draw of that iteration, lane k of the block's second wave normal k (beside the
+    // gamma variate and alpha's factorisation on the first wave, not behind them: late in a run this block's head is on the cycle)
+    if (blk == 0 && threadIdx.x >= 64 && (int)threadIdx.x - 64 < c.p) {
+        const uint32_t k = threadIdx.x - 64u;
+        sc.beta_eps[it_for & 1][k] = block_normal(sc.key, k, 0, it_for, STREAM_BETA);
     }
     const int i = blk * blockDim.x + threadIdx.x;
     if (i >= c.n) return;
@@ -2068,8 +2135,34 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
     const int chain = tile.chain, blk = tile.blk;
     if (chain < 0) return;
     ChainScalars &sc = scs[chain];
+    // per_wave: what beta's draw reads is on its way before the control words are looked at -- the first rounds of the
+    // partial sums of its system (k_iter's, written a moment ago on other XCDs: cold) and its normals of either parity
+    // (k_noise's, drawn one iteration ahead): their addresses need the chain number only.  The control words -- as cold, and
+    // in front of everything else -- then cost one round trip beside these instead of one before them (k_iter's phase A
+    // does the same with quad_pre).  Only the wave that draws loads; a chain that idles drops what it loaded.
+    constexpr int NQB = nacc(P);
+    const bool draws = per_wave && !beta_ready && threadIdx.x < 64;
+    const double *part_b = c.part_beta + (size_t)chain * NQB * c.nb_n;
+    // (P > 4: a round of 20 .. 44 sums held over the head, and as many totals kept by the drawing wave instead of handed
+    // round through LDS, are paid for in scratch at three workgroups per CU -- reduce_partials as before; P > 2: the normals
+    // are read where they are used, not 4 P registers held for them)
+    constexpr bool SUMS_PRE = P <= 4, EPS_PRE = P <= 2;
+    double pre[PartialRounds<NQB>::R][NQB], eps2[2][P];
+    if (draws) {
+        if constexpr (SUMS_PRE) partials_load<NQB>(part_b, c.nb_n, 0, pre);
+        if constexpr (EPS_PRE) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int a = 0; a < P; ++a) eps2[h][a] = load_agent(&sc.beta_eps[h][a]);  // (past the L1 whether the hand-overs need it or not: one path, no merge to wait at)
+        }
+    }
+    const uint64_t key = uniform_u64(sc.key);  // (read before this kernel's own stores to the chain's scalars: a scalar load)
     const Ctl ctl = sc.mid[e];
-    const bool skip = ctl.koff || ctl.it >= sc.it_stop || sc.err != 0;
+    const uint32_t it_stop = sc.it_stop;  // (all three asked for at once: behind `||` each would wait for the one before it)
+    const int err0 = sc.err;
+    asm volatile("" ::"s"(ctl.it), "s"(ctl.koff), "s"(it_stop), "s"(err0));  // (here, together: not each where `||` first needs it)
+    const bool skip = ctl.koff || ctl.it >= it_stop || err0 != 0;
     // per_wave: 256-thread blocks over 64-site slices (c.nb_n of them): beta is formed by wave 0 for the block
     const int nb = per_wave ? (c.n + (int)blockDim.x - 1) / (int)blockDim.x : c.nb_n;
     const uint32_t it = ctl.it;
@@ -2097,19 +2190,42 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
 #pragma unroll
         for (int a = 0; a < P; ++a) beta[a] = sc.beta[a];
     } else {
-        double sums[nacc(P)];
-        reduce_partials<nacc(P)>(c.part_beta + (size_t)chain * nacc(P) * c.nb_n, c.nb_n, sums);  // several waves: wave 0 + LDS
+        double sums[NQB];
+        if (!per_wave || !SUMS_PRE) reduce_partials<NQB>(part_b, c.nb_n, sums);  // (one wave per block; several: wave 0 + LDS)
+        else if (draws) {
+            // (what was loaded at entry is first touched HERE: without the empty statements the compiler moves the first
+            // additions -- and the wait for the loads with them -- up to the loads, in front of the control words)
+#pragma unroll
+            for (int r = 0; r < PartialRounds<NQB>::R; ++r)
+#pragma unroll
+                for (int qi = 0; qi < NQB; ++qi) asm volatile("" : "+v"(pre[r][qi]));
+            if constexpr (EPS_PRE) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int a = 0; a < P; ++a) asm volatile("" : "+v"(eps2[h][a]));
+            }
+            reduce_partials_wave<NQB, true>(part_b, c.nb_n, pre, sums);
+        }
         const double *b_prec = c.hyp + c.q * c.q + c.q, *b_pbm = b_prec + P * P;
         bool ok = true;
-        if (!per_wave || threadIdx.x < 64) {
-            ok = precision_mvnorm_reg<P>(sums, b_prec, b_pbm, sc.key, it, STREAM_BETA, beta);
+        if (!per_wave || threadIdx.x < 64) {  // with the normals k_noise drew for this iteration
+            if (EPS_PRE && per_wave) {
+                ok = precision_mvnorm_with<P>(sums, b_prec, b_pbm, beta, [&](int k) {
+                    const double odd = eps2[1][k], even = eps2[0][k];  // (both read, then chosen: a choice between two reads becomes one read
+                    return (it & 1u) ? odd : even;                     // through a chosen address, and the array then lives in memory)
+                });
+            } else {
+                const double *eps = sc.beta_eps[it & 1];
+                ok = precision_mvnorm_with<P>(sums, b_prec, b_pbm, beta, [=](int k) { return load_agent(eps + k); });
+            }
             if (per_wave && threadIdx.x == 0) {
                 s_beta_ok = ok ? 1 : 0;
 #pragma unroll
                 for (int a = 0; a < P; ++a) s_beta[a] = beta[a];
             }
         }
-        if (per_wave) {  // the draw (a Cholesky factor and Box-Muller normals) once per block, not once per wave
+        if (per_wave) {  // the draw (a Cholesky factor and two triangular solves) once per block, not once per wave
             __syncthreads();
             ok = s_beta_ok != 0;
 #pragma unroll
@@ -2125,9 +2241,12 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
     // waves (latency-bound on the visit rows) then share SIMDs from the start -- with the z blocks dealt first the
     // omega_b blocks of a large problem only got onto the device once those had drained (500x500: 22 + 30 us in a row)
     (void)nb;
+    // beta came through LDS (or through a merge with that path): back into scalar registers, as k_omega_b holds it
+#pragma unroll
+    for (int a = 0; a < P; ++a) beta[a] = uniform_f64(beta[a]);
     if (blk & 1) {  // role 1
         if (debug_skip & 2) return;
-        omega_b_body<P>(c, sc, beta, chain, it + 1u, blk >> 1, per_wave);
+        omega_b_body<P>(c, key, beta, chain, it + 1u, blk >> 1, per_wave);
         return;
     }
     // role 0 needs alpha of THIS iteration, drawn on the side stream
@@ -2150,10 +2269,10 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
         const bool stats_on = sc.site_on != 0u && it - sc.it_base >= sc.burnin;
         if (writer && stats_on && !(debug_skip & 1)) c.site_count[chain] += 1.0;
         if (i >= n || (debug_skip & 1)) return;
-        z_update_site<P, 0, 1>(c, sc.key, chain, i, it, beta, alpha, c.eta[(size_t)chain * n + i], stats_on);
+        z_update_site<P, 0, 1>(c, key, chain, i, it, beta, alpha, c.eta[(size_t)chain * n + i], stats_on);
     } else {
     if (i >= n || (debug_skip & 1)) return;
-    z_update_site<P>(c, sc.key, chain, i, it, beta, alpha, c.eta[(size_t)chain * n + i]);
+    z_update_site<P>(c, key, chain, i, it, beta, alpha, c.eta[(size_t)chain * n + i]);
     }
 }
 
@@ -2264,7 +2383,7 @@ __global__ void __launch_bounds__(256) k_beta_draw(OCC_KARGS)
         if (threadIdx.x == 0) {
             const double *b_prec = c.hyp + c.q * c.q + c.q, *b_pbm = b_prec + p * p;
             const bool ok = precision_mvnorm_dev(p, s_red, b_prec, b_pbm, sc.key, ctl.it, STREAM_BETA, s_U, s_work, sc.beta,
-                                                 INJ ? c.inj->beta_eps : nullptr);
+                                                 INJ ? c.inj->beta_eps : sc.beta_eps[ctl.it & 1]);  // (k_noise's, one iteration ahead)
             if (!ok) sc.err = -4;  // OCC_E_CHOLESKY
         }
         return;
@@ -2272,7 +2391,7 @@ __global__ void __launch_bounds__(256) k_beta_draw(OCC_KARGS)
     double sums[nacc(P)], beta[P];
     reduce_partials<nacc(P)>(c.part_beta + (size_t)chain * nacc(P) * c.nb_n, c.nb_n, sums);
     const double *b_prec = c.hyp + c.q * c.q + c.q, *b_pbm = b_prec + P * P;
-    const bool ok = precision_mvnorm_reg<P>(sums, b_prec, b_pbm, sc.key, ctl.it, STREAM_BETA, beta, INJ ? c.inj->beta_eps : nullptr);
+    const bool ok = precision_mvnorm_reg<P>(sums, b_prec, b_pbm, sc.key, ctl.it, STREAM_BETA, beta, INJ ? c.inj->beta_eps : sc.beta_eps[ctl.it & 1]);
     if (threadIdx.x == 0) {
         if (!ok) sc.err = -4;  // OCC_E_CHOLESKY
 #pragma unroll
@@ -2293,7 +2412,7 @@ __global__ void __launch_bounds__(256, 3) k_z_ob(OCC_KARGS, int flags)  // bit 0
     } else {
         const bool synced = (flags & 1) && c.sync != nullptr;
         // this sequence's number: k_iter, the previous kernel of the stream, left it in SYNC_MAIN
-        const unsigned seq = synced ? c.sync[SYNC_MAIN] : 0u;
+        const unsigned seq = synced ? (unsigned)__builtin_amdgcn_readfirstlane((int)c.sync[SYNC_MAIN]) : 0u;  // (uniform: a scalar register)
         z_ob_body<P>(c, scs, chain_base, e, synced, seq, (flags & 2) != 0, (flags >> 3) & 3, (flags & 4) != 0);
     }
 }
@@ -2309,7 +2428,7 @@ __global__ void __launch_bounds__(256, 3) k_z_ob_stats(OCC_KARGS, int flags)  //
         z_ob_body_g<1>(c, scs, chain_base, e, (flags & 2) != 0, (flags >> 3) & 3);
     } else {
         const bool synced = (flags & 1) && c.sync != nullptr;
-        const unsigned seq = synced ? c.sync[SYNC_MAIN] : 0u;
+        const unsigned seq = synced ? (unsigned)__builtin_amdgcn_readfirstlane((int)c.sync[SYNC_MAIN]) : 0u;  // (uniform: a scalar register)
         z_ob_body<P, 1>(c, scs, chain_base, e, synced, seq, (flags & 2) != 0, (flags >> 3) & 3, (flags & 4) != 0);
     }
 }
