@@ -151,7 +151,24 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  * occ_set_keys touch neither switch nor sums; a call that is re-run after a device-side wait gave up (occ_stats::
  * fused_fallbacks) counts no iteration twice; occ_profile and the occ_cond_* entry points never accumulate.  alpha, beta,
  * tau, eta, z are bit-identical with the switch on or off.  A probit handle (link = 1) answers every one of these names
- * with OCC_E_STATE, "site summaries are not available for the probit model". */
+ * with OCC_E_STATE, "site summaries are not available for the probit model".
+ *
+ * Per-site log-likelihood sums of streaming WAIC (logit models; ICAR and reduced rank), accumulated by the z update over the
+ * SAME iterations as the sums above, at the SURVEYED sites only (an unsurveyed site's sums stay exactly 0).  The likelihood
+ * is the site's marginal one, z integrated out.  With lsig(a) = min(a, 0) - log1p(exp(-|a|)) and r the site's visit rows:
+ *   no detection at the site:  L = D = (1 - psi) + psi prod_r expit(-w_r alpha), the very D the z update divides by; l = log D
+ *   a detection at the site:   l = lsig(x_i beta + eta_i) + sum_r lsig(+- w_r alpha), + where y_r = 1, rows in row order; L = exp(l)
+ * Three float64 sums per site and one count per chain:
+ *   ll_lik(n)    sum of L      -> log(ll_lik / count): the site's log pointwise predictive density
+ *   ll_log(n)    sum of l      ll_log2(n)  sum of l^2      -> the variance of l: the site's effective number of parameters
+ *   ll_count(1)  iterations accumulated                    ll_stats(1) the chain's switch, 0 / 1
+ * The semantics are those of the site_* names, word for word: occ_set_state "ll_stats" 1 allocates at first use (24 n bytes
+ * per chain of the handle), ZEROES the chain's three sums and count and switches on; 0 switches off, the sums stay readable;
+ * ll_count and the three sums are writable only while on; occ_get_state of any of the five names before the handle's first
+ * switch-on: OCC_E_STATE; nothing is redrawn, a re-run call counts nothing twice, occ_profile and occ_cond_* never accumulate;
+ * alpha, beta, tau, eta, z are bit-identical with the switch on or off; a probit handle answers every one of the names with
+ * OCC_E_STATE.  ll_stats and site_stats are independent of each other: either, both or neither may be on for a chain, and
+ * the site_* sums are the same bits with ll_stats on or off. */
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len);
 int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double *in, int64_t len);
 

@@ -115,6 +115,7 @@ class Engine:
         self.device = int(device)
         self.keys = [int(v) & (2 ** 64 - 1) for v in keys]
         self._site_on = False   # per-site posterior sums switched on (site_stats); off: no call about them reaches the library
+        self._ll_on = False     # likewise the log-likelihood sums of streaming WAIC (ll_stats)
         _LIVE.add(self)
         return self
 
@@ -204,6 +205,10 @@ class Engine:
             out['site_stats'] = np.ones(self.n_chains)
             for name in _lib.SITE_FIELDS[1:]:
                 out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
+        if self._ll_on:   # and the same of the log-likelihood sums
+            out['ll_stats'] = np.ones(self.n_chains)
+            for name in _lib.LOGLIK_FIELDS[1:]:
+                out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
         return out
 
     def restore(self, ckpt):
@@ -230,6 +235,13 @@ class Engine:
                     self.set(name, ckpt[name][c], c)
         elif self._site_on:
             self.site_stats(False)
+        if 'll_stats' in ckpt and np.all(np.asarray(ckpt['ll_stats']) != 0):
+            self.loglik_stats(True)
+            for c in range(self.n_chains):
+                for name in _lib.LOGLIK_FIELDS[1:]:
+                    self.set(name, ckpt[name][c], c)
+        elif self._ll_on:
+            self.loglik_stats(False)
 
     # ---- per-site posterior sums accumulated on the device (state names site_*, include/occ_gibbs.h) ----
     def site_stats(self, on):
@@ -244,6 +256,23 @@ class Engine:
         out = {'count': int(self.get('site_count', chain)[0])}
         for name in _lib.SITE_FIELDS[2:]:
             out[name[len('site_'):]] = self.get(name, chain)
+        return out
+
+    # ---- per-site log-likelihood sums of streaming WAIC (state names ll_*, include/occ_gibbs.h) ----
+    def loglik_stats(self, on):
+        """Switch the log-likelihood sums of every chain on (which ZEROES them and their counts) or off (they stay
+        readable).  While on, the z update of every kept iteration adds, at every surveyed site, the site's marginal
+        likelihood L (z integrated out), log L and (log L)^2.  Independent of :meth:`site_stats`."""
+        for c in range(self.n_chains):
+            self.set('ll_stats', 1.0 if on else 0.0, c)
+        self._ll_on = bool(on)
+
+    def loglik_sums(self, chain=0):
+        """``{'count', 'lik', 'log', 'log2'}`` of one chain: the iterations accumulated and the three sums (n; exactly 0
+        at a site that was not surveyed)."""
+        out = {'count': int(self.get('ll_count', chain)[0])}
+        for name in _lib.LOGLIK_FIELDS[2:]:
+            out[name[len('ll_'):]] = self.get(name, chain)
         return out
 
     def set_start(self, chain, alpha, beta, tau, eta):
@@ -419,6 +448,18 @@ class EngineGroup:
     def site_sums(self, chain=0):
         g, i = self.where[chain]
         return self.engines[g].site_sums(i)
+
+    @property
+    def _ll_on(self):
+        return any(getattr(e, '_ll_on', False) for e in self.engines)
+
+    def loglik_stats(self, on):
+        for e in self.engines:
+            e.loglik_stats(on)
+
+    def loglik_sums(self, chain=0):
+        g, i = self.where[chain]
+        return self.engines[g].loglik_sums(i)
 
     def step(self):
         self._each(lambda e: e.step())

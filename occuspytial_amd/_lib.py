@@ -16,6 +16,8 @@ N_KERNEL_KINDS = 9
 # state names of the per-site posterior sums (occ_get_state / occ_set_state, see the header): the chain's switch, its count
 # of accumulated iterations, and the five sums of length n
 SITE_FIELDS = ('site_stats', 'site_count', 'site_psi', 'site_occ', 'site_z', 'site_eta', 'site_eta2')
+# likewise the per-site log-likelihood sums of streaming WAIC: switch, count, and the three sums of length n
+LOGLIK_FIELDS = ('ll_stats', 'll_count', 'll_lik', 'll_log', 'll_log2')
 KERNEL_KINDS = ('omega_b', 'noise', 'eta_init', 'minres', 'beta_partial', 'omega_a', 'alpha_draw', 'z_ob', 'iter')
 
 

@@ -118,6 +118,11 @@ struct occ_sampler {
     // part of what a call is re-run from: snap_site ([5 C n] sums, then [C] counts), site_snapped: taken for the running call.
     bool site_launch = false, site_snapped = false;
     double *snap_site = nullptr;
+    // likewise the log-likelihood sums of streaming WAIC (Ctx::ll_acc / ll_count; state names ll_*).  ll_launch: a chain has
+    // that switch on, so launch_kind() launches k_z_ob_ll, which serves both kinds of sums and goes before k_z_ob_stats;
+    // snap_ll ([3 C n] sums, then [C] counts), ll_snapped: taken for the running call.
+    bool ll_launch = false, ll_snapped = false;
+    double *snap_ll = nullptr;
     std::vector<ChainScalars> snap_sc;
     // fixed problem arrays on the device, in upload order: what a group broadcasts from its root (occ_create_group /
     // occ_create_distributed); defer_fixed: allocate only, the bytes arrive by broadcast
@@ -404,6 +409,7 @@ KernelRsr pick_rsr_solve(int m)
 }
 KernelEI pick_z_ob(int p) { return OCC_PICK_P(k_z_ob, p); }
 KernelEI pick_z_ob_stats(int p) { return OCC_PICK_P(k_z_ob_stats, p); }
+KernelEI pick_z_ob_ll(int p) { return OCC_PICK_P(k_z_ob_ll, p); }
 KernelEI pick_omega_a(int q)
 {
     switch (q) {
@@ -445,7 +451,8 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
     const dim3 blk((unsigned)P.tpb), gs((unsigned)c.nb_n, (unsigned)c.C), gr((unsigned)c.nb_r, (unsigned)c.C);
     const int tp = P.generic ? 0 : c.p, tq = P.generic ? 0 : c.q;  // template arguments: 0 = the generic (run-time) instantiation
     const size_t lds_p = P.generic ? generic_lds_bytes(nacc(c.p), P.tpb) : 0, lds_q = P.generic ? generic_lds_bytes(nacc(c.q), P.tpb) : 0;
-    const KernelEI z_ob = s->site_launch ? pick_z_ob_stats(tp) : pick_z_ob(tp);  // (the twin that keeps the per-site sums)
+    // (the twin that keeps the per-site sums; the third family, which also keeps the log-likelihood sums)
+    const KernelEI z_ob = s->ll_launch ? pick_z_ob_ll(tp) : s->site_launch ? pick_z_ob_stats(tp) : pick_z_ob(tp);
     switch (kind) {
         case K_OMEGA_B: hipLaunchKernelGGL(pick_omega_b(tp), gs, blk, 0, st, OCC_ARGS); break;
         case K_NOISE:
@@ -910,6 +917,12 @@ int open_window(occ_sampler *s, int64_t n_iter, int64_t burnin, int64_t keep, bo
             if (!s->snap_site && (rc = dev_alloc(s, &s->snap_site, SITE_NACC * Cn + (size_t)c.C, false))) return rc;
             HIP_TRY(hipMemcpyAsync(s->snap_site, c.site_acc, sizeof(double) * SITE_NACC * Cn, hipMemcpyDeviceToDevice, s->stream));
             HIP_TRY(hipMemcpyAsync(s->snap_site + SITE_NACC * Cn, c.site_count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
+        }
+        s->ll_snapped = s->ll_launch;
+        if (s->ll_snapped) {
+            if (!s->snap_ll && (rc = dev_alloc(s, &s->snap_ll, LL_NACC * Cn + (size_t)c.C, false))) return rc;
+            HIP_TRY(hipMemcpyAsync(s->snap_ll, c.ll_acc, sizeof(double) * LL_NACC * Cn, hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(s->snap_ll + LL_NACC * Cn, c.ll_count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
         }
         hipLaunchKernelGGL(k_snapshot, dim3((unsigned)std::min<size_t>((Cn + 255) / 256, 2048)), dim3(256), 0, s->stream, c.eta, s->snap_eta, c.z, s->snap_z, c.Xv, s->snap_x,
                            (unsigned long long)Cn, s->rsr.m > 0 ? s->rsr.theta : nullptr, s->snap_theta, (unsigned long long)c.C * (unsigned long long)std::max(s->rsr.m, 0),
@@ -2925,6 +2938,10 @@ static int fallback_to_launch_per_step(occ_sampler *s)
         HIP_TRY(copy_on(s, c.site_acc, s->snap_site, sizeof(double) * SITE_NACC * Cn, hipMemcpyDeviceToDevice));
         HIP_TRY(copy_on(s, c.site_count, s->snap_site + SITE_NACC * Cn, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
     }
+    if (s->ll_snapped) {
+        HIP_TRY(copy_on(s, c.ll_acc, s->snap_ll, sizeof(double) * LL_NACC * Cn, hipMemcpyDeviceToDevice));
+        HIP_TRY(copy_on(s, c.ll_count, s->snap_ll + LL_NACC * Cn, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
+    }
     for (auto &sc : s->snap_sc) sc.err = 0;
     if ((rc = write_scalars(s, s->snap_sc))) return rc;
     s->parity = s->snap_parity;
@@ -3043,65 +3060,92 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
     return rc;
 }
 
-// The state names of the per-site posterior sums: -> 0..4 the sum's place in Ctx::site_acc, SITE_COUNT, SITE_SWITCH; SITE_NONE.
+// The state names of the per-site sums, of either kind (SUMS_SITE: the posterior summaries, site_*; SUMS_LL: the
+// log-likelihood sums of streaming WAIC, ll_*): -> kind and 0.. the sum's place in the kind's array, SITE_COUNT, SITE_SWITCH;
+// SITE_NONE.
 enum : int { SITE_NONE = -1, SITE_COUNT = -2, SITE_SWITCH = -3 };
-static int site_field(const std::string &nm)
+enum : int { SUMS_SITE = 0, SUMS_LL = 1 };
+struct SumsKind {
+    uint32_t bit;  // of ChainScalars::site_on
+    int nacc;
+    double *Ctx::*acc, *Ctx::*count;
+    const char *what, *sw, *cnt;
+};
+static const SumsKind SUMS[2] = {{1u, SITE_NACC, &Ctx::site_acc, &Ctx::site_count, "site summaries", "site_stats", "site_count"},
+                                 {2u, LL_NACC, &Ctx::ll_acc, &Ctx::ll_count, "log-likelihood sums", "ll_stats", "ll_count"}};
+static int site_field(const std::string &nm, int *kind)
 {
-    if (nm.compare(0, 5, "site_") != 0) return SITE_NONE;
-    if (nm == "site_stats") return SITE_SWITCH;
-    if (nm == "site_count") return SITE_COUNT;
-    if (nm == "site_psi") return SITE_PSI;
-    if (nm == "site_occ") return SITE_OCC;
-    if (nm == "site_z") return SITE_Z;
-    if (nm == "site_eta") return SITE_ETA;
-    if (nm == "site_eta2") return SITE_ETA2;
+    if (nm.compare(0, 5, "site_") == 0) {
+        *kind = SUMS_SITE;
+        if (nm == "site_stats") return SITE_SWITCH;
+        if (nm == "site_count") return SITE_COUNT;
+        if (nm == "site_psi") return SITE_PSI;
+        if (nm == "site_occ") return SITE_OCC;
+        if (nm == "site_z") return SITE_Z;
+        if (nm == "site_eta") return SITE_ETA;
+        if (nm == "site_eta2") return SITE_ETA2;
+    } else if (nm.compare(0, 3, "ll_") == 0) {
+        *kind = SUMS_LL;
+        if (nm == "ll_stats") return SITE_SWITCH;
+        if (nm == "ll_count") return SITE_COUNT;
+        if (nm == "ll_lik") return LL_LIK;
+        if (nm == "ll_log") return LL_LOG;
+        if (nm == "ll_log2") return LL_LOG2;
+    }
     return SITE_NONE;
 }
-
-// occ_set_state of those names.  site_stats = 1: allocate at first use, zero the chain's sums and count, switch on;
-// 0: switch off (the sums stay readable).  The sums and the count themselves (checkpoint restore): only while the switch is on.
-// Which z kernel is launched follows "is any chain on"; a change drops the captured graphs (rebuilt by the next occ_run).
-// Nothing of the chain's state changes: omega_b of the coming iteration is NOT redrawn.
-static int set_site_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+static int sums_refused(occ_sampler *s, const SumsKind &k)
 {
-    if (s->probit) return set_error(s, OCC_E_STATE, "site summaries are not available for the probit model");
+    return set_error(s, OCC_E_STATE, (std::string(k.what) + " are not available for the probit model").c_str());
+}
+
+// occ_set_state of those names.  The switch = 1: allocate at first use, zero the chain's sums and count, switch on;
+// 0: switch off (the sums stay readable).  The sums and the count themselves (checkpoint restore): only while the switch is on.
+// Which z kernel is launched follows "is any chain on", the log-likelihood sums first (k_z_ob_ll serves both kinds); a change
+// of kernel drops the captured graphs (rebuilt by the next occ_run).  The two switches are independent of each other.
+// Nothing of the chain's state changes: omega_b of the coming iteration is NOT redrawn.
+static int set_site_state(occ_sampler *s, int chain, int kind, int field, const double *in, int64_t len)
+{
+    const SumsKind &k = SUMS[kind];
+    if (s->probit) return sums_refused(s, k);
     Ctx &c = s->ctx;
     const size_t n = (size_t)c.n, Cn = (size_t)c.C * n;
     int rc;
     std::vector<ChainScalars> h;
     if ((rc = read_scalars(s, h))) return rc;
     if (field != SITE_SWITCH) {
-        if (!c.site_acc || !h[chain].site_on) return set_error(s, OCC_E_STATE, "site summaries are switched off for this chain (set site_stats to 1 first)");
+        if (!(c.*k.acc) || !(h[chain].site_on & k.bit))
+            return set_error(s, OCC_E_STATE, (std::string(k.what) + " are switched off for this chain (set " + k.sw + " to 1 first)").c_str());
         if ((size_t)len != (field == SITE_COUNT ? (size_t)1 : n)) return set_error(s, OCC_E_STATE, "wrong length");
         if (field == SITE_COUNT) {
-            if (!(in[0] >= 0.0) || in[0] != std::floor(in[0])) return set_error(s, OCC_E_STATE, "site_count is a whole number of iterations");
-            HIP_TRY(copy_on(s, c.site_count + chain, in, sizeof(double), hipMemcpyHostToDevice));
+            if (!(in[0] >= 0.0) || in[0] != std::floor(in[0])) return set_error(s, OCC_E_STATE, (std::string(k.cnt) + " is a whole number of iterations").c_str());
+            HIP_TRY(copy_on(s, c.*k.count + chain, in, sizeof(double), hipMemcpyHostToDevice));
         } else {
-            HIP_TRY(copy_on(s, c.site_acc + (size_t)field * Cn + chain * n, in, sizeof(double) * n, hipMemcpyHostToDevice));
+            HIP_TRY(copy_on(s, c.*k.acc + (size_t)field * Cn + chain * n, in, sizeof(double) * n, hipMemcpyHostToDevice));
         }
         return OCC_OK;
     }
     if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
     const bool on = in[0] != 0.0;
-    if (!on && !c.site_acc) return OCC_OK;  // never switched on: nothing to switch off
+    if (!on && !(c.*k.acc)) return OCC_OK;  // never switched on: nothing to switch off
     WAIT_TRY(s->side);
-    if (on && !c.site_acc) {
-        if ((rc = dev_alloc(s, &c.site_acc, SITE_NACC * Cn))) return rc;
-        if ((rc = dev_alloc(s, &c.site_count, (size_t)c.C))) return rc;
+    if (on && !(c.*k.acc)) {
+        if ((rc = dev_alloc(s, &(c.*k.acc), (size_t)k.nacc * Cn))) return rc;
+        if ((rc = dev_alloc(s, &(c.*k.count), (size_t)c.C))) return rc;
         HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
     }
     if (on) {
-        for (int q = 0; q < SITE_NACC; ++q) HIP_TRY(fill_on(s, c.site_acc + (size_t)q * Cn + chain * n, 0, sizeof(double) * n));
-        HIP_TRY(fill_on(s, c.site_count + chain, 0, sizeof(double)));
+        for (int q = 0; q < k.nacc; ++q) HIP_TRY(fill_on(s, c.*k.acc + (size_t)q * Cn + chain * n, 0, sizeof(double) * n));
+        HIP_TRY(fill_on(s, c.*k.count + chain, 0, sizeof(double)));
     }
-    h[chain].site_on = on ? 1u : 0u;
+    h[chain].site_on = (h[chain].site_on & ~k.bit) | (on ? k.bit : 0u);
     if ((rc = write_scalars(s, h))) return rc;
-    bool any = false;
-    for (const auto &sc : h) any = any || sc.site_on != 0u;
-    if (any != s->site_launch) {
-        destroy_graph(s);
-        s->site_launch = any;
-    }
+    uint32_t any = 0u;
+    for (const auto &sc : h) any |= sc.site_on;
+    const bool site_any = (any & SUMS[SUMS_SITE].bit) != 0u, ll_any = (any & SUMS[SUMS_LL].bit) != 0u;
+    if ((ll_any ? 2 : site_any ? 1 : 0) != (s->ll_launch ? 2 : s->site_launch ? 1 : 0)) destroy_graph(s);
+    s->site_launch = site_any;
+    s->ll_launch = ll_any;
     return OCC_OK;
 }
 
@@ -3116,10 +3160,13 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     const std::string nm(name);
     const size_t n = (size_t)c.n, R = (size_t)c.R;
     std::vector<double> v;
-    const int site_q = site_field(nm);
+    int sums_kind = SUMS_SITE;
+    const int site_q = site_field(nm, &sums_kind);
+    const SumsKind &sk = SUMS[sums_kind];
     if (site_q != SITE_NONE) {
-        if (s->probit) return set_error(s, OCC_E_STATE, "site summaries are not available for the probit model");
-        if (!c.site_acc) return set_error(s, OCC_E_STATE, "site summaries have not been switched on for this handle (set site_stats to 1 first)");
+        if (s->probit) return sums_refused(s, sk);
+        if (!(c.*sk.acc))
+            return set_error(s, OCC_E_STATE, (std::string(sk.what) + " have not been switched on for this handle (set " + sk.sw + " to 1 first)").c_str());
     }
     if (s->probit) {
         const int prc = pb_get_state(s, chain, nm, v);
@@ -3165,9 +3212,9 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     else if (nm == "tau") v.assign(1, sc.tau);
     else if (nm == "minres_itn") v.assign(1, (double)sc.minres_itn_last);
     else if (nm == "iter") v.assign(1, (double)it);
-    else if (site_q == SITE_SWITCH) v.assign(1, sc.site_on ? 1.0 : 0.0);
-    else if (site_q == SITE_COUNT) rc = pull(c.site_count + chain, 1);
-    else if (site_q >= 0) rc = pull(c.site_acc + (size_t)site_q * c.C * n + chain * n, n);
+    else if (site_q == SITE_SWITCH) v.assign(1, (sc.site_on & sk.bit) ? 1.0 : 0.0);
+    else if (site_q == SITE_COUNT) rc = pull(c.*sk.count + chain, 1);
+    else if (site_q >= 0) rc = pull(c.*sk.acc + (size_t)site_q * c.C * n + chain * n, n);
     else if (nm == "rsr_gram" && s->rsr.m > 0) {
         // tests only, m x m row-major, of the last theta update.  m <= RSR_MAX_DIM: K' diag(omega_b) K (upper 16 x 16 tiles).
         // m > RSR_MAX_DIM: k_rsrb_assemble adds tau Qr in place and k_rsrb_step overwrites each 32-row panel's rows right of
@@ -3199,7 +3246,9 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     HIP_TRY(hipSetDevice(s->device));
     WAIT_TRY(s->stream);
     const std::string nm(name);
-    if (site_field(nm) != SITE_NONE) return set_site_state(s, chain, site_field(nm), in, len);
+    int sums_kind = SUMS_SITE;
+    const int sums_q = site_field(nm, &sums_kind);
+    if (sums_q != SITE_NONE) return set_site_state(s, chain, sums_kind, sums_q, in, len);
     if (s->probit) return pb_set_state(s, chain, nm, in, len);
     const size_t n = (size_t)c.n, R = (size_t)c.R;
     auto need = [&](size_t want) { return (size_t)len == want; };
@@ -3368,7 +3417,12 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     if (s->probit) return pb_profile(s, reps, counts, total_us);
     // (the timing loops always launch k_z_ob itself, never the twin that keeps the per-site sums; no captured graph of the
     // handle is replayed here)
-    struct PlainZob { occ_sampler *s; bool old; explicit PlainZob(occ_sampler *p) : s(p), old(p->site_launch) { s->site_launch = false; } ~PlainZob() { s->site_launch = old; } } plain_z_ob(s);
+    struct PlainZob {
+        occ_sampler *s;
+        bool old, old_ll;
+        explicit PlainZob(occ_sampler *p) : s(p), old(p->site_launch), old_ll(p->ll_launch) { s->site_launch = s->ll_launch = false; }
+        ~PlainZob() { s->site_launch = old, s->ll_launch = old_ll; }
+    } plain_z_ob(s);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops
     if (rc) return rc;
     // The fused iteration kernel first, IN SITU: `reps` real iterations continue the chains from where they are

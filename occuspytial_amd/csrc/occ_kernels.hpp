@@ -111,7 +111,8 @@ struct ChainScalars {
     uint32_t bar_base;         // arrivals counted so far by the chain's barrier counter (occ_iter.hpp), never reset
     int32_t err;               // OCC_E_* raised on device
     int32_t minres_itn_last;
-    uint32_t site_on;          // per-site posterior sums (Ctx::site_acc) are kept for this chain; sits where the layout had padding
+    uint32_t site_on;          // bit 0: per-site posterior sums (Ctx::site_acc) are kept for this chain; bit 1: the log-likelihood
+                               // sums (Ctx::ll_acc); sits where the layout had padding
     unsigned long long krylov_total, krylov_sq_total, solves, carries;
 };
 
@@ -194,6 +195,11 @@ struct Ctx {
     // psi, P(z = 1 | rest), z, eta, eta^2 -- added to by the z update of k_z_ob_stats, and the iterations added per chain.
     double *site_acc;
     double *site_count;  // [C]
+    // Per-site log-likelihood sums of streaming WAIC (state names ll_*; null until a chain is first switched on): three
+    // quantities, each [C][n] -- the site's marginal likelihood L, l = log L, l^2 -- added to by the z update of k_z_ob_ll at
+    // the surveyed sites, and the iterations added per chain.
+    double *ll_acc;
+    double *ll_count;  // [C]
 };
 
 // ---- reductions ----------------------------------------------------------------------------------
@@ -2063,12 +2069,96 @@ __device__ __forceinline__ void site_add(const Ctx &c, int chain, int i, double 
     a[SITE_ETA2 * Cn] = fma(eta, eta, a[SITE_ETA2 * Cn]);
 }
 
-// STATS (k_z_ob_stats only; `stats_on`: this chain, this iteration): the site's psi, P(z = 1 | rest), new z, eta and eta^2 go
-// into the per-site sums -- at a site with a detection (psi, 1, 1, eta, eta^2).
+// Streaming WAIC: one iteration's terms of a surveyed site's log-likelihood sums (Ctx::ll_acc) -- L, l and l^2 (the last by
+// one fused multiply-add, stated) -- by the site's own thread, as site_add.
+enum : int { LL_LIK = 0, LL_LOG = 1, LL_LOG2 = 2, LL_NACC = 3 };
+__device__ __forceinline__ void ll_add(const Ctx &c, int chain, int i, double lik, double ll)
+{
+    const size_t Cn = (size_t)c.C * c.n;
+    double *a = c.ll_acc + (size_t)chain * c.n + i;
+    a[LL_LIK * Cn] += lik;
+    a[LL_LOG * Cn] += ll;
+    a[LL_LOG2 * Cn] = fma(ll, ll, a[LL_LOG2 * Cn]);
+}
+// log expit(a) = min(a, 0) - log1p(exp(-|a|)), stable on both sides, and expit(a) itself, both from e = exp(-|a|): the
+// second performs the operations of expit() above (exp(a) for a < 0, exp(-a) otherwise), so it has its bits.
+__device__ __forceinline__ double lsig_e(double a, double e) { return fmin(a, 0.0) - log1p(e); }
+__device__ __forceinline__ double expit_e(double a, double e) { return a < 0.0 ? e / (1.0 + e) : 1.0 / (1.0 + e); }
+
+// The z update of one site of a chain that keeps the log-likelihood sums (k_z_ob_ll, `ll_on`): z_update_site with ONE loop
+// over the site's visit rows for both kinds of surveyed site.  A site with a detection needs lsig(+- w_r alpha) of every
+// row, a site without one expit(-w_r alpha): both come from the same load, the same dot product and the same exponential.
+// Two loops -- the update's, which sites with a detection skip, and a second one for those -- would be run one after the
+// other by every wave that holds both kinds of site, and the z waves are bound by the latency of exactly that loop.
+// psi, the product, D, the probability and z are formed by the operations of z_update_site: the same bits.
+// xb_of(): x_i beta; wa_of(r): -w_r alpha (the fixed and the run-time forms of the two dot products).
+template <int INJ, class XB, class WA>
+__device__ __forceinline__ void z_update_site_ll(const Ctx &c, uint64_t key, int chain, int i, uint32_t it, double eta_i, bool stats_on,
+                                                 XB xb_of, WA wa_of)
+{
+    const int sidx = c.site_sidx[i], n = c.n;
+    const bool not_surveyed = sidx < 0;
+    const bool seen = !not_surveyed && c.obs_site[sidx];  // detection seen: z stays 1 (base.py:116-118)
+    const double a0 = xb_of() + eta_i, e0 = exp(-fabs(a0));
+    const double num1 = expit_e(a0, e0);
+    double pr = num1;
+    if (!not_surveyed) {
+        double prod = 1.0, ll = seen ? lsig_e(a0, e0) : 0.0;
+        const int r0 = c.site_ptr[sidx], r1 = c.site_ptr[sidx + 1];
+        for (int r = r0; r < r1; ++r) {
+            const double wa = wa_of(r), e = exp(-fabs(wa));
+            if (seen) {
+                ll += lsig_e(c.yrow[r] ? -wa : wa, e);  // rows in row order
+            } else {
+                const double ex = expit_e(wa, e);
+                prod = (r == r0) ? ex : prod * ex;
+            }
+        }
+        if (seen) {
+            if (stats_on) site_add(c, chain, i, num1, 1.0, 1.0, eta_i);
+            ll_add(c, chain, i, exp(ll), ll);
+            return;
+        }
+        const double num = num1 * prod;
+        const double den = (1.0 - num1) + num;  // the site's likelihood: what the update divides by
+        pr = num / den;
+        ll_add(c, chain, i, den, log(den));
+    }
+    const double u = INJ ? c.inj->z_u[i] : block_uniform(key, (uint32_t)i, 0, it, STREAM_Z);
+    c.z[(size_t)chain * n + i] = (u < pr) ? 1 : 0;
+    if (stats_on) site_add(c, chain, i, num1, pr, (u < pr) ? 1.0 : 0.0, eta_i);
+}
+
+// STATS (k_z_ob_stats, k_z_ob_ll; `stats_on`: this chain, this iteration): the site's psi, P(z = 1 | rest), new z, eta and
+// eta^2 go into the per-site sums -- at a site with a detection (psi, 1, 1, eta, eta^2).
+// STATS = 2 (k_z_ob_ll only; `ll_on`: this chain, this iteration): a surveyed site's marginal likelihood, z integrated out,
+// goes into the log-likelihood sums.  No detection: the denominator D = (1 - psi) + psi prod_r expit(-w_r alpha) of the
+// update itself is the likelihood, l = log D.  A detection: l = lsig(x_i beta + eta_i) + sum_r lsig(+- w_r alpha), + where
+// y_r = 1, the rows added in row order, L = exp(l).  Such a chain's sites go through z_update_site_ll (above).
 template <int P, int INJ = 0, int STATS = 0>
 __device__ __forceinline__ void z_update_site(const Ctx &c, uint64_t key, int chain, int i, uint32_t it, const double (&beta)[P],
-                                              const double (&alpha)[MAXC], double eta_i, bool stats_on = false)
+                                              const double (&alpha)[MAXC], double eta_i, bool stats_on = false, bool ll_on = false)
 {
+    if constexpr (STATS == 2) {
+        if (ll_on) {  // (uniform over the workgroup: a chain's switch)
+            z_update_site_ll<INJ>(
+                c, key, chain, i, it, eta_i, stats_on,
+                [&]() {
+                    double xb = 0.0;
+#pragma unroll
+                    for (int a = 0; a < P; ++a) xb = fma(c.Xt[(size_t)a * c.n + i], beta[a], xb);
+                    return xb;
+                },
+                [&](int r) {
+                    double wa = 0.0;
+#pragma unroll
+                    for (int a = 0; a < MAXC; ++a)
+                        if (a < c.q) wa = fma(c.Wt[(size_t)a * c.R + r], -alpha[a], wa);
+                    return wa;
+                });
+            return;
+        }
+    }
     const int sidx = c.site_sidx[i];
     const bool not_surveyed = sidx < 0;
     if (!not_surveyed && c.obs_site[sidx]) {  // detection seen: z stays 1 (base.py:116-118)
@@ -2264,7 +2354,15 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
     }
     if (writer) record_draws<P>(c, sc, chain, it, alpha, beta, sc.tau);
     const int n = c.n, i = (blk >> 1) * blockDim.x + threadIdx.x;
-    if constexpr (STATS) {
+    if constexpr (STATS == 2) {
+        // both kinds of sums, each where the chain's bit is on: the same iterations count for either
+        const uint32_t on = sc.site_on;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        if (writer && stats_on && !(debug_skip & 1)) c.site_count[chain] += 1.0;
+        if (writer && ll_on && !(debug_skip & 1)) c.ll_count[chain] += 1.0;
+        if (i >= n || (debug_skip & 1)) return;
+        z_update_site<P, 0, 2>(c, key, chain, i, it, beta, alpha, c.eta[(size_t)chain * n + i], stats_on, ll_on);
+    } else if constexpr (STATS) {
         // a kept iteration of a chain whose switch is on (the window's upper end does not matter); this pass completes it
         const bool stats_on = sc.site_on != 0u && it - sc.it_base >= sc.burnin;
         if (writer && stats_on && !(debug_skip & 1)) c.site_count[chain] += 1.0;
@@ -2280,8 +2378,25 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
 // scalars.  Same operations as z_update_site.
 template <int INJ, int STATS = 0>
 __device__ __forceinline__ void z_update_site_g(const Ctx &c, const ChainScalars &sc, int chain, int i, uint32_t it, double eta_i,
-                                                bool stats_on = false)
+                                                bool stats_on = false, bool ll_on = false)
 {
+    if constexpr (STATS == 2) {
+        if (ll_on) {
+            z_update_site_ll<INJ>(
+                c, sc.key, chain, i, it, eta_i, stats_on,
+                [&]() {
+                    double xb = 0.0;
+                    for (int a = 0; a < c.p; ++a) xb = fma(c.Xt[(size_t)a * c.n + i], sc.beta[a], xb);
+                    return xb;
+                },
+                [&](int r) {
+                    double wa = 0.0;
+                    for (int a = 0; a < c.q; ++a) wa = fma(c.Wt[(size_t)a * c.R + r], -sc.alpha[a], wa);
+                    return wa;
+                });
+            return;
+        }
+    }
     const int sidx = c.site_sidx[i];
     const bool not_surveyed = sidx < 0;
     if (!not_surveyed && c.obs_site[sidx]) {
@@ -2351,7 +2466,14 @@ __device__ __forceinline__ void z_ob_body_g(const Ctx &c, ChainScalars *__restri
         }
     }
     const int n = c.n, i = (blk >> 1) * blockDim.x + threadIdx.x;
-    if constexpr (STATS) {
+    if constexpr (STATS == 2) {
+        const uint32_t on = sc.site_on;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        if (writer && stats_on && !(debug_skip & 1)) c.site_count[chain] += 1.0;
+        if (writer && ll_on && !(debug_skip & 1)) c.ll_count[chain] += 1.0;
+        if (i >= n || (debug_skip & 1)) return;
+        z_update_site_g<0, 2>(c, sc, chain, i, it, c.eta[(size_t)chain * n + i], stats_on, ll_on);
+    } else if constexpr (STATS) {
         const bool stats_on = sc.site_on != 0u && it - sc.it_base >= sc.burnin;
         if (writer && stats_on && !(debug_skip & 1)) c.site_count[chain] += 1.0;
         if (i >= n || (debug_skip & 1)) return;
@@ -2430,6 +2552,23 @@ __global__ void __launch_bounds__(256, 3) k_z_ob_stats(OCC_KARGS, int flags)  //
         const bool synced = (flags & 1) && c.sync != nullptr;
         const unsigned seq = synced ? (unsigned)__builtin_amdgcn_readfirstlane((int)c.sync[SYNC_MAIN]) : 0u;  // (uniform: a scalar register)
         z_ob_body<P, 1>(c, scs, chain_base, e, synced, seq, (flags & 2) != 0, (flags >> 3) & 3, (flags & 4) != 0);
+    }
+}
+
+// k_z_ob with the log-likelihood sums of streaming WAIC (Ctx::ll_acc) AND the per-site posterior sums, each for the chains
+// whose bit of ChainScalars::site_on is set: launched in k_z_ob's place while a chain of the handle has bit 1 on.  A third
+// kernel family, so that k_z_ob and k_z_ob_stats stay the code they were.
+template <int P>
+__global__ void __launch_bounds__(256, 3) k_z_ob_ll(OCC_KARGS, int flags)  // flags: k_z_ob's
+{
+    __builtin_amdgcn_s_setprio(3);
+    const Ctx &c = *cp;
+    if constexpr (P == 0) {
+        z_ob_body_g<2>(c, scs, chain_base, e, (flags & 2) != 0, (flags >> 3) & 3);
+    } else {
+        const bool synced = (flags & 1) && c.sync != nullptr;
+        const unsigned seq = synced ? (unsigned)__builtin_amdgcn_readfirstlane((int)c.sync[SYNC_MAIN]) : 0u;  // (uniform: a scalar register)
+        z_ob_body<P, 2>(c, scs, chain_base, e, synced, seq, (flags & 2) != 0, (flags >> 3) & 3, (flags & 4) != 0);
     }
 }
 

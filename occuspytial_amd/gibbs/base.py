@@ -113,7 +113,7 @@ class GibbsBase:
                 self.chain.append(self.state.posteriors)
         return self.chain
 
-    def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False):
+    def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False, waic=False):
         """Draw ``size`` iterations per chain and return the kept ``alpha``, ``beta``, ``tau`` draws.
 
         Same contract as the reference (``base.py:243-291``): ``burnin < size`` else ``ValueError``;
@@ -123,6 +123,10 @@ class GibbsBase:
         ``site_summaries=True`` (samplers that run on the engine; logit link) additionally accumulates the per-site
         posterior map on the device over the kept iterations -- occupancy probability, P(z = 1 | data), the spatial effect
         and its sd -- and returns it as ``out.sites``, a :class:`~occuspytial_amd.sites.SiteSummary` (``None`` otherwise).
+
+        ``waic=True`` (the same samplers) accumulates, over the same iterations, every surveyed site's marginal likelihood
+        and log-likelihood (z integrated out) on the device and returns ``out.waic``, a :class:`~occuspytial_amd.waic.WAIC`
+        (``None`` otherwise): compare two fits with :func:`occuspytial_amd.waic.compare`.
         """
         if burnin >= size:
             raise ValueError('burnin value cannot be larger than sample size')
@@ -132,11 +136,16 @@ class GibbsBase:
         if site_summaries:
             self._check_site_summaries()
             extra['site_summaries'] = True
+        if waic:
+            self._check_waic()
+            extra['waic'] = True
         samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start,
                                   progressbar=progressbar, **extra)
         out = PosteriorParameter(*samples)
         if site_summaries:
             out.sites = self.__dict__.pop('_sites')
+        if waic:
+            out.waic = self.__dict__.pop('_waic')
         return out
 
     def _check_site_summaries(self):
@@ -144,6 +153,12 @@ class GibbsBase:
         if not hasattr(self, '_run_chains'):
             raise NotImplementedError(f'{self.__class__.__name__} steps in Python: site summaries are accumulated by the '
                                       'device engine only')
+
+    def _check_waic(self):
+        """The log-likelihood sums are accumulated by the engine's z update: a sampler with a Python ``step`` has none."""
+        if not hasattr(self, '_run_chains'):
+            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: the log-likelihood sums of WAIC are '
+                                      'accumulated by the device engine only')
 
     def copy(self):
         """A shallow copy with its own generator spawned from this one's seed sequence

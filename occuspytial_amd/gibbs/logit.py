@@ -127,13 +127,20 @@ class LogitICARGibbs(GibbsBase):
         except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
             raise ValueError(f'the loaded engine library has no site summaries ({exc}): rebuild it') from None
 
-    def resume(self, checkpoint, size, progressbar=True, site_summaries=False):
+    def _ll_switch(self, eng, on):
+        try:
+            eng.loglik_stats(on)
+        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
+            raise ValueError(f'the loaded engine library has no log-likelihood sums ({exc}): rebuild it') from None
+
+    def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False):
         """Continue the chains of ``checkpoint`` (a dict from :meth:`checkpoint` or the path of its ``.npz``)
         for ``size`` more iterations on this sampler's problem.  Returns a ``PosteriorParameter`` of the new
         draws; every chain's ``Chain`` is the continuation (use ``Chain.expand`` / ``append`` to join them to
         earlier draws).  The result equals the tail of an uninterrupted run bit for bit.  ``site_summaries=True``: the
         per-site sums go on from those the checkpoint holds (from zero if it holds none); the result's ``sites`` covers
-        every iteration accumulated so far, those before the checkpoint included."""
+        every iteration accumulated so far, those before the checkpoint included.  ``waic=True``: the same for the
+        log-likelihood sums and the result's ``waic``."""
         from ..posterior import PosteriorParameter
         from tqdm.auto import tqdm
         if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, '__fspath__'):
@@ -149,6 +156,10 @@ class LogitICARGibbs(GibbsBase):
             self._check_site_summaries()
             if 'site_stats' not in checkpoint:
                 self._site_switch(eng, True)
+        if waic:
+            self._check_waic()
+            if 'll_stats' not in checkpoint:
+                self._ll_switch(eng, True)
         alpha = np.zeros((C, size, self._problem.q))
         beta = np.zeros((C, size, self._problem.p))
         tau = np.zeros((C, size))
@@ -168,10 +179,13 @@ class LogitICARGibbs(GibbsBase):
         if site_summaries:
             from ..sites import SiteSummary
             out.sites = SiteSummary.from_engine(eng)
+        if waic:
+            from ..waic import WAIC
+            out.waic = WAIC.from_engine(eng)
         return out
 
     # ------------------------------------------------------------------ batched chains
-    def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False):
+    def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False, waic=False):
         """All chains of one ``sample`` call as one device batch.
 
         Mirrors ``GibbsBase._run`` (base.py:214-241) per chain: start values from the chain's own
@@ -179,6 +193,7 @@ class LogitICARGibbs(GibbsBase):
         ``site_summaries``: burn-in chunks run with the engine's per-site sums switched off; the switch goes on (which
         zeroes them) right before the first chunk that keeps a draw, and inside that chunk the engine itself counts
         only the iterations past the chunk's burn-in.  With the default no call about them reaches the engine.
+        ``waic``: the log-likelihood sums, switched in exactly the same way.
         """
         from tqdm.auto import tqdm
 
@@ -195,7 +210,9 @@ class LogitICARGibbs(GibbsBase):
             eng.set('z', z0, c)
         if site_summaries or getattr(eng, '_site_on', False):   # (a reused engine that an earlier call left switched on)
             self._site_switch(eng, False)   # (also the early answer of a library that does not know site summaries)
-        sites_on = False
+        if waic or getattr(eng, '_ll_on', False):
+            self._ll_switch(eng, False)
+        sites_on = ll_on = False
 
         C = len(samplers)
         keep = size - burnin
@@ -214,6 +231,9 @@ class LogitICARGibbs(GibbsBase):
                 if site_summaries and not sites_on:
                     self._site_switch(eng, True)
                     sites_on = True
+                if waic and not ll_on:
+                    self._ll_switch(eng, True)
+                    ll_on = True
                 a_, b_, t_ = eng.run(step, b)
                 m = step - b
                 alpha[:, kept:kept + m], beta[:, kept:kept + m], tau[:, kept:kept + m] = a_, b_, t_
@@ -233,6 +253,9 @@ class LogitICARGibbs(GibbsBase):
         if site_summaries:
             from ..sites import SiteSummary
             self.__dict__['_sites'] = SiteSummary.from_engine(eng)
+        if waic:
+            from ..waic import WAIC
+            self.__dict__['_waic'] = WAIC.from_engine(eng)
         return chains
 
 

@@ -101,6 +101,10 @@ class ProbitRSRGibbs(GibbsBase):
         # (its z update conditions on the auxiliary eps: what "psi" should mean there is a modelling decision not yet made)
         raise NotImplementedError('site summaries are not available for the probit model')
 
+    def _check_waic(self):
+        # (the same decision: its z update conditions on eps, so the site's marginal likelihood is not what it forms)
+        raise NotImplementedError('WAIC is not available for the probit model')
+
     step = LogitICARGibbs.step
     checkpoint = LogitICARGibbs.checkpoint
     resume = LogitICARGibbs.resume

@@ -39,6 +39,7 @@ class PosteriorParameter:
     """
 
     sites = None   # a SiteSummary when sample(..., site_summaries=True) asked for the per-site posterior map
+    waic = None    # a WAIC when sample(..., waic=True) asked for the streaming log-likelihood sums
 
     def __init__(self, *chains):
         self.data = self._create_inference_data(chains)
