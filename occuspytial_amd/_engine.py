@@ -114,8 +114,8 @@ class Engine:
         self.n_chains = len(keys)
         self.device = int(device)
         self.keys = [int(v) & (2 ** 64 - 1) for v in keys]
-        self._site_on = False   # per-site posterior sums switched on (site_stats); off: no call about them reaches the library
-        self._ll_on = False     # likewise the log-likelihood sums of streaming WAIC (ll_stats)
+        # kind of per-site sums (_lib.SUMS_KINDS) -> switched on (sums_switch); off: no call about them reaches the library
+        self._sums_on = dict.fromkeys(_lib.SUMS_KINDS, False)
         _LIVE.add(self)
         return self
 
@@ -201,14 +201,12 @@ class Engine:
             fields = ('alpha', 'beta', 'tau', 'theta', 'z', 'c', 'eta', 'eps')
         for name in fields:
             out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
-        if self._site_on:   # switch, count and the five per-site sums: a resumed run ends with the sums of the uninterrupted one
-            out['site_stats'] = np.ones(self.n_chains)
-            for name in _lib.SITE_FIELDS[1:]:
-                out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
-        if self._ll_on:   # and the same of the log-likelihood sums
-            out['ll_stats'] = np.ones(self.n_chains)
-            for name in _lib.LOGLIK_FIELDS[1:]:
-                out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
+        for kind, on in self._sums_on.items():
+            if on:   # switch, count and the kind's per-site sums: a resumed run ends with the sums of the uninterrupted one
+                switch, *rest = _lib.SUMS_KINDS[kind].fields
+                out[switch] = np.ones(self.n_chains)
+                for name in rest:
+                    out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
         return out
 
     def restore(self, ckpt):
@@ -228,52 +226,50 @@ class Engine:
             if self.rsr is None:
                 self.set('xz', ckpt['xz'][c], c)
             self.set('iter', float(ckpt['iter'][c]), c)
-        if 'site_stats' in ckpt and np.all(np.asarray(ckpt['site_stats']) != 0):
-            self.site_stats(True)
-            for c in range(self.n_chains):
-                for name in _lib.SITE_FIELDS[1:]:
-                    self.set(name, ckpt[name][c], c)
-        elif self._site_on:
-            self.site_stats(False)
-        if 'll_stats' in ckpt and np.all(np.asarray(ckpt['ll_stats']) != 0):
-            self.loglik_stats(True)
-            for c in range(self.n_chains):
-                for name in _lib.LOGLIK_FIELDS[1:]:
-                    self.set(name, ckpt[name][c], c)
-        elif self._ll_on:
-            self.loglik_stats(False)
+        for kind, k in _lib.SUMS_KINDS.items():
+            switch, *rest = k.fields
+            if switch in ckpt and np.all(np.asarray(ckpt[switch]) != 0):
+                self.sums_switch(kind, True)
+                for c in range(self.n_chains):
+                    for name in rest:
+                        self.set(name, ckpt[name][c], c)
+            elif self._sums_on[kind]:
+                self.sums_switch(kind, False)
 
-    # ---- per-site posterior sums accumulated on the device (state names site_*, include/occ_gibbs.h) ----
-    def site_stats(self, on):
-        """Switch the per-site sums of every chain on (which ZEROES them and their counts) or off (they stay readable).
-        While on, the z update of every kept iteration adds psi, P(z = 1 | rest), z, eta and eta^2 of every site."""
+    # ---- per-site sums accumulated on the device (state names site_* and ll_*, include/occ_gibbs.h), by kind ----
+    def sums_switch(self, kind, on):
+        """Switch one kind of per-site sums of every chain on (which ZEROES them and their counts) or off (they stay
+        readable).  The kinds are independent of each other."""
         for c in range(self.n_chains):
-            self.set('site_stats', 1.0 if on else 0.0, c)
-        self._site_on = bool(on)
+            self.set(_lib.SUMS_KINDS[kind].fields[0], 1.0 if on else 0.0, c)
+        self._sums_on[kind] = bool(on)
+
+    def sums(self, kind, chain=0):
+        """``{'count': iterations accumulated, short name: sum (n), ...}`` of one kind and one chain."""
+        _, count, *names = _lib.SUMS_KINDS[kind].fields
+        out = {'count': int(self.get(count, chain)[0])}
+        for name in names:
+            out[name[len(kind) + 1:]] = self.get(name, chain)
+        return out
+
+    def site_stats(self, on):
+        """Switch the per-site posterior sums (:meth:`sums_switch`).  While on, the z update of every kept iteration adds
+        psi, P(z = 1 | rest), z, eta and eta^2 of every site."""
+        self.sums_switch('site', on)
 
     def site_sums(self, chain=0):
         """``{'count', 'psi', 'occ', 'z', 'eta', 'eta2'}`` of one chain: the iterations accumulated and the five sums (n)."""
-        out = {'count': int(self.get('site_count', chain)[0])}
-        for name in _lib.SITE_FIELDS[2:]:
-            out[name[len('site_'):]] = self.get(name, chain)
-        return out
+        return self.sums('site', chain)
 
-    # ---- per-site log-likelihood sums of streaming WAIC (state names ll_*, include/occ_gibbs.h) ----
     def loglik_stats(self, on):
-        """Switch the log-likelihood sums of every chain on (which ZEROES them and their counts) or off (they stay
-        readable).  While on, the z update of every kept iteration adds, at every surveyed site, the site's marginal
-        likelihood L (z integrated out), log L and (log L)^2.  Independent of :meth:`site_stats`."""
-        for c in range(self.n_chains):
-            self.set('ll_stats', 1.0 if on else 0.0, c)
-        self._ll_on = bool(on)
+        """Switch the log-likelihood sums of streaming WAIC (:meth:`sums_switch`).  While on, the z update of every kept
+        iteration adds, at every surveyed site, the site's marginal likelihood L (z integrated out), log L and (log L)^2."""
+        self.sums_switch('ll', on)
 
     def loglik_sums(self, chain=0):
         """``{'count', 'lik', 'log', 'log2'}`` of one chain: the iterations accumulated and the three sums (n; exactly 0
         at a site that was not surveyed)."""
-        out = {'count': int(self.get('ll_count', chain)[0])}
-        for name in _lib.LOGLIK_FIELDS[2:]:
-            out[name[len('ll_'):]] = self.get(name, chain)
-        return out
+        return self.sums('ll', chain)
 
     def set_start(self, chain, alpha, beta, tau, eta):
         a = np.ascontiguousarray(alpha, dtype=np.float64)
@@ -438,28 +434,19 @@ class EngineGroup:
         self.engines[g].set(name, value, i)
 
     @property
-    def _site_on(self):
-        return any(getattr(e, '_site_on', False) for e in self.engines)
+    def _sums_on(self):   # (a stand-in engine of the tests need not know the sums: it has none switched on)
+        return {kind: any(getattr(e, '_sums_on', {}).get(kind, False) for e in self.engines) for kind in _lib.SUMS_KINDS}
 
-    def site_stats(self, on):
+    def sums_switch(self, kind, on):
         for e in self.engines:
-            e.site_stats(on)
+            e.sums_switch(kind, on)
 
-    def site_sums(self, chain=0):
+    def sums(self, kind, chain=0):
         g, i = self.where[chain]
-        return self.engines[g].site_sums(i)
+        return self.engines[g].sums(kind, i)
 
-    @property
-    def _ll_on(self):
-        return any(getattr(e, '_ll_on', False) for e in self.engines)
-
-    def loglik_stats(self, on):
-        for e in self.engines:
-            e.loglik_stats(on)
-
-    def loglik_sums(self, chain=0):
-        g, i = self.where[chain]
-        return self.engines[g].loglik_sums(i)
+    # (the entry points by name are Engine's own: each only names its kind)
+    site_stats, site_sums, loglik_stats, loglik_sums = Engine.site_stats, Engine.site_sums, Engine.loglik_stats, Engine.loglik_sums
 
     def step(self):
         self._each(lambda e: e.step())

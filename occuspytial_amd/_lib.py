@@ -6,6 +6,7 @@ g.build()"`` or ``make -C occuspytial_amd/csrc``.
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libocc_gibbs.so')
@@ -19,6 +20,26 @@ SITE_FIELDS = ('site_stats', 'site_count', 'site_psi', 'site_occ', 'site_z', 'si
 # likewise the per-site log-likelihood sums of streaming WAIC: switch, count, and the three sums of length n
 LOGLIK_FIELDS = ('ll_stats', 'll_count', 'll_lik', 'll_log', 'll_log2')
 KERNEL_KINDS = ('omega_b', 'noise', 'eta_init', 'minres', 'beta_partial', 'omega_a', 'alpha_draw', 'z_ob', 'iter')
+
+
+class SumsKind(NamedTuple):
+    """One kind of per-site running sums the engine keeps on the device (``SUMS`` of csrc/occ_gibbs.hip), as Python sees it."""
+    fields: tuple       # its state names: switch, count, sums (a sum's short name drops the kind's prefix, 'site_' / 'll_')
+    what: str           # what messages call it
+    option: str         # the keyword of ``sample`` / ``resume`` that asks for it
+    result: str         # the attribute of their result that holds what is made of the sums
+    python_step: str    # why a sampler that steps in Python refuses it (after the class's name)
+    probit: str         # why the probit sampler refuses it
+
+
+SUMS_KINDS = {
+    'site': SumsKind(SITE_FIELDS, 'site summaries', 'site_summaries', 'sites',
+                     'steps in Python: site summaries are accumulated by the device engine only',
+                     'site summaries are not available for the probit model'),
+    'll': SumsKind(LOGLIK_FIELDS, 'log-likelihood sums', 'waic', 'waic',
+                   'steps in Python: the log-likelihood sums of WAIC are accumulated by the device engine only',
+                   'WAIC is not available for the probit model'),
+}
 
 
 class OccProblem(C.Structure):

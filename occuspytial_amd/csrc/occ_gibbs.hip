@@ -80,6 +80,29 @@ DeviceSlot &device_slot(int device)
 using DeviceLease = std::unique_lock<std::recursive_mutex>;
 inline DeviceLease lease_device(int device) { return DeviceLease(device_slot(device).busy); }
 
+// ---- the kinds of per-site running sums, described once --------------------------------------------------------------
+// SUMS_SITE: the posterior summaries (state names site_*); SUMS_LL: the log-likelihood sums of streaming WAIC (ll_*).  A kind
+// is switched per chain (its bit of ChainScalars::site_on), is kept in arrays of its own ([nacc C n] sums, [C] counts of
+// accumulated iterations) by a z-update kernel of its own that stands where k_z_ob stands, and is read and written through
+// occ_get_state / occ_set_state.  Whatever the host does for a kind -- names, snapshot and restore around a call that may
+// be re-run, the choice of kernel -- is a loop over this table.
+using KernelEI = void (*)(const Ctx *, ChainScalars *, Slot *, int, int, int);
+KernelEI pick_z_ob_stats(int p), pick_z_ob_ll(int p);  // (defined with the other choices of an instantiation, below)
+enum : int { SUMS_SITE = 0, SUMS_LL = 1, N_SUMS = 2 };
+struct SumsKind {
+    uint32_t bit;  // of ChainScalars::site_on
+    int nacc;
+    double *Ctx::*acc, *Ctx::*count;
+    const char *what, *sw, *cnt, *sum[SITE_NACC];  // in messages; state names: switch, count, the sums in their *_NACC order
+    KernelEI (*z_ob)(int p);  // the z-update kernel that keeps it ...
+    int rank;                 // ... launched when no kind of higher rank is on (a kernel also serves the kinds below its own)
+};
+const SumsKind SUMS[N_SUMS] = {
+    {1u, SITE_NACC, &Ctx::site_acc, &Ctx::site_count, "site summaries", "site_stats", "site_count",
+     {"site_psi", "site_occ", "site_z", "site_eta", "site_eta2"}, pick_z_ob_stats, 1},
+    {2u, LL_NACC, &Ctx::ll_acc, &Ctx::ll_count, "log-likelihood sums", "ll_stats", "ll_count",
+     {"ll_lik", "ll_log", "ll_log2"}, pick_z_ob_ll, 2}};
+
 }  // namespace
 
 struct occ_sampler {
@@ -113,16 +136,21 @@ struct occ_sampler {
     uint8_t *snap_z = nullptr;
     double2 *snap_x = nullptr;
     double *snap_theta = nullptr;  // reduced-rank model: the basis coefficients
-    // per-site posterior sums (Ctx::site_acc / site_count; state names site_*).  site_launch: a chain has its switch on, so
-    // launch_kind() launches k_z_ob_stats where k_z_ob stands (baked into captured graphs: a change drops them).  The sums are
-    // part of what a call is re-run from: snap_site ([5 C n] sums, then [C] counts), site_snapped: taken for the running call.
-    bool site_launch = false, site_snapped = false;
-    double *snap_site = nullptr;
-    // likewise the log-likelihood sums of streaming WAIC (Ctx::ll_acc / ll_count; state names ll_*).  ll_launch: a chain has
-    // that switch on, so launch_kind() launches k_z_ob_ll, which serves both kinds of sums and goes before k_z_ob_stats;
-    // snap_ll ([3 C n] sums, then [C] counts), ll_snapped: taken for the running call.
-    bool ll_launch = false, ll_snapped = false;
-    double *snap_ll = nullptr;
+    // per-site running sums, kind by kind (SUMS).  launch: a chain has the kind's switch on, so launch_kind() launches a
+    // kernel that keeps it where k_z_ob stands (z_ob_kind; baked into captured graphs: a change of kernel drops them).  The
+    // sums are part of what a call is re-run from: snap ([nacc C n] sums, then [C] counts), snapped: taken for the running call.
+    struct SumsRun {
+        bool launch = false, snapped = false;
+        double *snap = nullptr;
+    } sums[N_SUMS];
+    // the kind whose z-update kernel runs: of those with a chain switched on, the one of highest rank; -1: k_z_ob itself
+    int z_ob_kind() const
+    {
+        int top = -1;
+        for (int k = 0; k < N_SUMS; ++k)
+            if (sums[k].launch && (top < 0 || SUMS[k].rank > SUMS[top].rank)) top = k;
+        return top;
+    }
     std::vector<ChainScalars> snap_sc;
     // fixed problem arrays on the device, in upload order: what a group broadcasts from its root (occ_create_group /
     // occ_create_distributed); defer_fixed: allocate only, the bytes arrive by broadcast
@@ -369,7 +397,6 @@ int set_error(occ_sampler *s, int code, const char *msg)
 }
 
 using KernelE = void (*)(const Ctx *, ChainScalars *, Slot *, int, int);
-using KernelEI = void (*)(const Ctx *, ChainScalars *, Slot *, int, int, int);
 
 KernelEI pick_beta_partial(int p)
 {
@@ -451,8 +478,8 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
     const dim3 blk((unsigned)P.tpb), gs((unsigned)c.nb_n, (unsigned)c.C), gr((unsigned)c.nb_r, (unsigned)c.C);
     const int tp = P.generic ? 0 : c.p, tq = P.generic ? 0 : c.q;  // template arguments: 0 = the generic (run-time) instantiation
     const size_t lds_p = P.generic ? generic_lds_bytes(nacc(c.p), P.tpb) : 0, lds_q = P.generic ? generic_lds_bytes(nacc(c.q), P.tpb) : 0;
-    // (the twin that keeps the per-site sums; the third family, which also keeps the log-likelihood sums)
-    const KernelEI z_ob = s->ll_launch ? pick_z_ob_ll(tp) : s->site_launch ? pick_z_ob_stats(tp) : pick_z_ob(tp);
+    const int zk = s->z_ob_kind();  // (a kind of per-site sums is switched on: its kernel where k_z_ob stands)
+    const KernelEI z_ob = zk < 0 ? pick_z_ob(tp) : SUMS[zk].z_ob(tp);
     switch (kind) {
         case K_OMEGA_B: hipLaunchKernelGGL(pick_omega_b(tp), gs, blk, 0, st, OCC_ARGS); break;
         case K_NOISE:
@@ -912,17 +939,14 @@ int open_window(occ_sampler *s, int64_t n_iter, int64_t burnin, int64_t keep, bo
         }
         s->snap_sc = h;
         s->snap_parity = s->parity;
-        s->site_snapped = s->site_launch;
-        if (s->site_snapped) {  // the per-site sums are part of what the call is re-run from: no iteration is counted twice
-            if (!s->snap_site && (rc = dev_alloc(s, &s->snap_site, SITE_NACC * Cn + (size_t)c.C, false))) return rc;
-            HIP_TRY(hipMemcpyAsync(s->snap_site, c.site_acc, sizeof(double) * SITE_NACC * Cn, hipMemcpyDeviceToDevice, s->stream));
-            HIP_TRY(hipMemcpyAsync(s->snap_site + SITE_NACC * Cn, c.site_count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
-        }
-        s->ll_snapped = s->ll_launch;
-        if (s->ll_snapped) {
-            if (!s->snap_ll && (rc = dev_alloc(s, &s->snap_ll, LL_NACC * Cn + (size_t)c.C, false))) return rc;
-            HIP_TRY(hipMemcpyAsync(s->snap_ll, c.ll_acc, sizeof(double) * LL_NACC * Cn, hipMemcpyDeviceToDevice, s->stream));
-            HIP_TRY(hipMemcpyAsync(s->snap_ll + LL_NACC * Cn, c.ll_count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
+        for (int k = 0; k < N_SUMS; ++k) {  // the per-site sums are part of what the call is re-run from: no iteration is counted twice
+            occ_sampler::SumsRun &r = s->sums[k];
+            const size_t nsum = (size_t)SUMS[k].nacc * Cn;
+            r.snapped = r.launch;
+            if (!r.snapped) continue;
+            if (!r.snap && (rc = dev_alloc(s, &r.snap, nsum + (size_t)c.C, false))) return rc;
+            HIP_TRY(hipMemcpyAsync(r.snap, c.*SUMS[k].acc, sizeof(double) * nsum, hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(r.snap + nsum, c.*SUMS[k].count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
         }
         hipLaunchKernelGGL(k_snapshot, dim3((unsigned)std::min<size_t>((Cn + 255) / 256, 2048)), dim3(256), 0, s->stream, c.eta, s->snap_eta, c.z, s->snap_z, c.Xv, s->snap_x,
                            (unsigned long long)Cn, s->rsr.m > 0 ? s->rsr.theta : nullptr, s->snap_theta, (unsigned long long)c.C * (unsigned long long)std::max(s->rsr.m, 0),
@@ -1527,6 +1551,42 @@ int pb_set_start(occ_sampler *s, int chain, const double *alpha, const double *b
     return pb_set_theta(s, chain, theta);
 }
 
+// ---- pieces of occ_get_state / occ_set_state that the two models share ------------------------------------------------
+// "z" / "k" / "exists" of one chain, from its occupancy bytes on the device: z itself, z - 1/2, and per surveyed site
+// "detected there, or z = 1"
+int pull_z_view(occ_sampler *s, const std::string &nm, const uint8_t *z_dev, size_t n, int S, std::vector<double> &v)
+{
+    std::vector<uint8_t> z(n);
+    HIP_TRY(copy_on(s, z.data(), z_dev, n, hipMemcpyDeviceToHost));
+    if (nm == "exists") {
+        v.resize((size_t)S);
+        for (int t = 0; t < S; ++t) v[t] = (s->obs_site[t] || z[s->site_id[t]]) ? 1.0 : 0.0;
+    } else {
+        v.resize(n);
+        for (size_t i = 0; i < n; ++i) v[i] = (nm == "z") ? (double)z[i] : (double)z[i] - 0.5;
+    }
+    return OCC_OK;
+}
+// "z" of one chain set from doubles (non-zero: occupied)
+int push_z(occ_sampler *s, uint8_t *z_dev, size_t n, const double *in, int64_t len)
+{
+    if ((size_t)len != n) return set_error(s, OCC_E_STATE, "wrong length");
+    std::vector<uint8_t> z(n);
+    for (size_t i = 0; i < n; ++i) z[i] = in[i] != 0.0;
+    HIP_TRY(copy_on(s, z_dev, z.data(), n, hipMemcpyHostToDevice));
+    return OCC_OK;
+}
+// the end of occ_get_state: the length always, the values when the caller gave a buffer
+int give_state(occ_sampler *s, const std::vector<double> &v, double *out, int64_t cap, int64_t *len)
+{
+    *len = (int64_t)v.size();
+    if (out) {
+        if (cap < (int64_t)v.size()) return set_error(s, OCC_E_STATE, "output buffer too small");
+        std::copy(v.begin(), v.end(), out);
+    }
+    return OCC_OK;
+}
+
 int pb_get_state(occ_sampler *s, int chain, const std::string &nm, std::vector<double> &v)
 {
     const PbArgs &A = s->pb;
@@ -1557,18 +1617,7 @@ int pb_get_state(occ_sampler *s, int chain, const std::string &nm, std::vector<d
         }
         return OCC_OK;
     }
-    if (nm == "z" || nm == "k" || nm == "exists") {
-        std::vector<uint8_t> z(n);
-        HIP_TRY(copy_on(s, z.data(), A.z + chain * n, n, hipMemcpyDeviceToHost));
-        if (nm == "exists") {
-            v.resize((size_t)A.S);
-            for (int t = 0; t < A.S; ++t) v[t] = (s->obs_site[t] || z[s->site_id[t]]) ? 1.0 : 0.0;
-        } else {
-            v.resize(n);
-            for (size_t i = 0; i < n; ++i) v[i] = (nm == "z") ? (double)z[i] : (double)z[i] - 0.5;
-        }
-        return OCC_OK;
-    }
+    if (nm == "z" || nm == "k" || nm == "exists") return pull_z_view(s, nm, A.z + chain * n, n, A.S, v);
     if (nm == "alpha") v.assign(c.alpha, c.alpha + A.q);
     else if (nm == "beta") v.assign(c.beta, c.beta + A.p);
     else if (nm == "tau") v.assign(1, c.tau);
@@ -1596,13 +1645,7 @@ int pb_set_state(occ_sampler *s, int chain, const std::string &nm, const double 
         if (!need(m)) return set_error(s, OCC_E_STATE, "wrong length");
         return pb_set_theta(s, chain, in);
     }
-    if (nm == "z") {
-        if (!need(n)) return set_error(s, OCC_E_STATE, "wrong length");
-        std::vector<uint8_t> z(n);
-        for (size_t i = 0; i < n; ++i) z[i] = in[i] != 0.0;
-        HIP_TRY(copy_on(s, A.z + chain * n, z.data(), n, hipMemcpyHostToDevice));
-        return OCC_OK;
-    }
+    if (nm == "z") return push_z(s, A.z + chain * n, n, in, len);
     std::vector<PbChain> h;
     int rc = pb_read_chains(s, h);
     if (rc) return rc;
@@ -2934,13 +2977,11 @@ static int fallback_to_launch_per_step(occ_sampler *s)
     HIP_TRY(copy_on(s, c.z, s->snap_z, Cn, hipMemcpyDeviceToDevice));
     HIP_TRY(copy_on(s, c.Xv, s->snap_x, sizeof(double2) * Cn, hipMemcpyDeviceToDevice));
     if (s->rsr.m > 0) HIP_TRY(copy_on(s, s->rsr.theta, s->snap_theta, sizeof(double) * (size_t)c.C * s->rsr.m, hipMemcpyDeviceToDevice));
-    if (s->site_snapped) {
-        HIP_TRY(copy_on(s, c.site_acc, s->snap_site, sizeof(double) * SITE_NACC * Cn, hipMemcpyDeviceToDevice));
-        HIP_TRY(copy_on(s, c.site_count, s->snap_site + SITE_NACC * Cn, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
-    }
-    if (s->ll_snapped) {
-        HIP_TRY(copy_on(s, c.ll_acc, s->snap_ll, sizeof(double) * LL_NACC * Cn, hipMemcpyDeviceToDevice));
-        HIP_TRY(copy_on(s, c.ll_count, s->snap_ll + LL_NACC * Cn, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
+    for (int k = 0; k < N_SUMS; ++k) {
+        const size_t nsum = (size_t)SUMS[k].nacc * Cn;
+        if (!s->sums[k].snapped) continue;
+        HIP_TRY(copy_on(s, c.*SUMS[k].acc, s->sums[k].snap, sizeof(double) * nsum, hipMemcpyDeviceToDevice));
+        HIP_TRY(copy_on(s, c.*SUMS[k].count, s->sums[k].snap + nsum, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
     }
     for (auto &sc : s->snap_sc) sc.err = 0;
     if ((rc = write_scalars(s, s->snap_sc))) return rc;
@@ -3060,37 +3101,17 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
     return rc;
 }
 
-// The state names of the per-site sums, of either kind (SUMS_SITE: the posterior summaries, site_*; SUMS_LL: the
-// log-likelihood sums of streaming WAIC, ll_*): -> kind and 0.. the sum's place in the kind's array, SITE_COUNT, SITE_SWITCH;
-// SITE_NONE.
+// The state names of the per-site sums, of any kind (SUMS): -> kind and 0.. the sum's place in the kind's array, SITE_COUNT,
+// SITE_SWITCH; SITE_NONE (then *kind says nothing).
 enum : int { SITE_NONE = -1, SITE_COUNT = -2, SITE_SWITCH = -3 };
-enum : int { SUMS_SITE = 0, SUMS_LL = 1 };
-struct SumsKind {
-    uint32_t bit;  // of ChainScalars::site_on
-    int nacc;
-    double *Ctx::*acc, *Ctx::*count;
-    const char *what, *sw, *cnt;
-};
-static const SumsKind SUMS[2] = {{1u, SITE_NACC, &Ctx::site_acc, &Ctx::site_count, "site summaries", "site_stats", "site_count"},
-                                 {2u, LL_NACC, &Ctx::ll_acc, &Ctx::ll_count, "log-likelihood sums", "ll_stats", "ll_count"}};
 static int site_field(const std::string &nm, int *kind)
 {
-    if (nm.compare(0, 5, "site_") == 0) {
-        *kind = SUMS_SITE;
-        if (nm == "site_stats") return SITE_SWITCH;
-        if (nm == "site_count") return SITE_COUNT;
-        if (nm == "site_psi") return SITE_PSI;
-        if (nm == "site_occ") return SITE_OCC;
-        if (nm == "site_z") return SITE_Z;
-        if (nm == "site_eta") return SITE_ETA;
-        if (nm == "site_eta2") return SITE_ETA2;
-    } else if (nm.compare(0, 3, "ll_") == 0) {
-        *kind = SUMS_LL;
-        if (nm == "ll_stats") return SITE_SWITCH;
-        if (nm == "ll_count") return SITE_COUNT;
-        if (nm == "ll_lik") return LL_LIK;
-        if (nm == "ll_log") return LL_LOG;
-        if (nm == "ll_log2") return LL_LOG2;
+    for (int k = 0; k < N_SUMS; ++k) {
+        *kind = k;
+        if (nm == SUMS[k].sw) return SITE_SWITCH;
+        if (nm == SUMS[k].cnt) return SITE_COUNT;
+        for (int q = 0; q < SUMS[k].nacc; ++q)
+            if (nm == SUMS[k].sum[q]) return q;
     }
     return SITE_NONE;
 }
@@ -3101,8 +3122,8 @@ static int sums_refused(occ_sampler *s, const SumsKind &k)
 
 // occ_set_state of those names.  The switch = 1: allocate at first use, zero the chain's sums and count, switch on;
 // 0: switch off (the sums stay readable).  The sums and the count themselves (checkpoint restore): only while the switch is on.
-// Which z kernel is launched follows "is any chain on", the log-likelihood sums first (k_z_ob_ll serves both kinds); a change
-// of kernel drops the captured graphs (rebuilt by the next occ_run).  The two switches are independent of each other.
+// Which z kernel is launched follows "is any chain on", kind by kind (occ_sampler::z_ob_kind); a change of kernel drops the
+// captured graphs (rebuilt by the next occ_run).  The kinds' switches are independent of each other.
 // Nothing of the chain's state changes: omega_b of the coming iteration is NOT redrawn.
 static int set_site_state(occ_sampler *s, int chain, int kind, int field, const double *in, int64_t len)
 {
@@ -3142,10 +3163,9 @@ static int set_site_state(occ_sampler *s, int chain, int kind, int field, const 
     if ((rc = write_scalars(s, h))) return rc;
     uint32_t any = 0u;
     for (const auto &sc : h) any |= sc.site_on;
-    const bool site_any = (any & SUMS[SUMS_SITE].bit) != 0u, ll_any = (any & SUMS[SUMS_LL].bit) != 0u;
-    if ((ll_any ? 2 : site_any ? 1 : 0) != (s->ll_launch ? 2 : s->site_launch ? 1 : 0)) destroy_graph(s);
-    s->site_launch = site_any;
-    s->ll_launch = ll_any;
+    const int z_ob_before = s->z_ob_kind();
+    for (int j = 0; j < N_SUMS; ++j) s->sums[j].launch = (any & SUMS[j].bit) != 0u;
+    if (s->z_ob_kind() != z_ob_before) destroy_graph(s);
     return OCC_OK;
 }
 
@@ -3170,13 +3190,7 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     }
     if (s->probit) {
         const int prc = pb_get_state(s, chain, nm, v);
-        if (prc) return prc;
-        *len = (int64_t)v.size();
-        if (out) {
-            if (cap < (int64_t)v.size()) return set_error(s, OCC_E_STATE, "output buffer too small");
-            std::copy(v.begin(), v.end(), out);
-        }
-        return OCC_OK;
+        return prc ? prc : give_state(s, v, out, cap, len);
     }
     auto pull = [&](const double *src, size_t count) -> int {
         v.resize(count);
@@ -3192,17 +3206,8 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     else if (nm == "omega_b") rc = pull(c.omega_b[(it + 1) & 1] + chain * n, n);  // of the last completed iteration
     else if (nm == "omega_a") rc = pull(c.omega_a + chain * R, R);
     else if (nm == "rhs") rc = pull(c.rhs + chain * n, n);
-    else if (nm == "z" || nm == "k" || nm == "exists") {
-        std::vector<uint8_t> z(n);
-        HIP_TRY(copy_on(s, z.data(), c.z + chain * n, n, hipMemcpyDeviceToHost));
-        if (nm == "exists") {
-            v.resize((size_t)c.S);
-            for (int t = 0; t < c.S; ++t) v[t] = (s->obs_site[t] || z[s->site_id[t]]) ? 1.0 : 0.0;
-        } else {
-            v.resize(n);
-            for (size_t i = 0; i < n; ++i) v[i] = (nm == "z") ? (double)z[i] : (double)z[i] - 0.5;
-        }
-    } else if (nm == "xz") {
+    else if (nm == "z" || nm == "k" || nm == "exists") rc = pull_z_view(s, nm, c.z + chain * n, n, c.S, v);
+    else if (nm == "xz") {
         std::vector<double2> x(n);
         HIP_TRY(copy_on(s, x.data(), c.Xv + chain * n, sizeof(double2) * n, hipMemcpyDeviceToHost));
         v.resize(2 * n);
@@ -3228,13 +3233,7 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
         HIP_TRY(copy_on(s, v.data(), s->rsr.theta + (size_t)chain * s->rsr.m, sizeof(double) * v.size(), hipMemcpyDeviceToHost));
     }
     else return set_error(s, OCC_E_STATE, "unknown state name");
-    if (rc) return rc;
-    *len = (int64_t)v.size();
-    if (out) {
-        if (cap < (int64_t)v.size()) return set_error(s, OCC_E_STATE, "output buffer too small");
-        std::copy(v.begin(), v.end(), out);
-    }
-    return OCC_OK;
+    return rc ? rc : give_state(s, v, out, cap, len);
 }
 
 int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double *in, int64_t len)
@@ -3259,10 +3258,8 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
         if (!need(R)) return set_error(s, OCC_E_STATE, "wrong length");
         HIP_TRY(copy_on(s, c.omega_a + chain * R, in, sizeof(double) * R, hipMemcpyHostToDevice));
     } else if (nm == "z") {
-        if (!need(n)) return set_error(s, OCC_E_STATE, "wrong length");
-        std::vector<uint8_t> z(n);
-        for (size_t i = 0; i < n; ++i) z[i] = in[i] != 0.0;
-        HIP_TRY(copy_on(s, c.z + chain * n, z.data(), n, hipMemcpyHostToDevice));
+        int rc = push_z(s, c.z + chain * n, n, in, len);
+        if (rc) return rc;
     } else if (nm == "theta" && s->rsr.m > 0) {
         if (!need((size_t)s->rsr.m)) return set_error(s, OCC_E_STATE, "wrong length");
         int rc = set_theta(s, chain, in);
@@ -3419,9 +3416,15 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     // handle is replayed here)
     struct PlainZob {
         occ_sampler *s;
-        bool old, old_ll;
-        explicit PlainZob(occ_sampler *p) : s(p), old(p->site_launch), old_ll(p->ll_launch) { s->site_launch = s->ll_launch = false; }
-        ~PlainZob() { s->site_launch = old, s->ll_launch = old_ll; }
+        bool old[N_SUMS];
+        explicit PlainZob(occ_sampler *p) : s(p)
+        {
+            for (int k = 0; k < N_SUMS; ++k) old[k] = s->sums[k].launch, s->sums[k].launch = false;
+        }
+        ~PlainZob()
+        {
+            for (int k = 0; k < N_SUMS; ++k) s->sums[k].launch = old[k];
+        }
     } plain_z_ob(s);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops
     if (rc) return rc;

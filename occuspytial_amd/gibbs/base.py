@@ -9,6 +9,7 @@ chains to the HIP engine in one batch instead of forking one process per chain
 import numpy as np
 from scipy.sparse import csc_matrix, isspmatrix_csc
 
+from .. import _lib
 from .._problem import FlatProblem, default_start
 from ..chain import Chain
 from ..data import Data
@@ -132,33 +133,27 @@ class GibbsBase:
             raise ValueError('burnin value cannot be larger than sample size')
         if chains < 1:
             raise ValueError('chains must a positive integer.')
-        extra = {}
-        if site_summaries:
-            self._check_site_summaries()
-            extra['site_summaries'] = True
-        if waic:
-            self._check_waic()
-            extra['waic'] = True
+        kinds = self._sums_asked(site_summaries=site_summaries, waic=waic)
+        for kind in kinds:
+            self._refuse_sums(kind)
+        extra = {_lib.SUMS_KINDS[kind].option: True for kind in kinds}   # (with the defaults, no keyword about them goes on)
         samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start,
                                   progressbar=progressbar, **extra)
         out = PosteriorParameter(*samples)
-        if site_summaries:
-            out.sites = self.__dict__.pop('_sites')
-        if waic:
-            out.waic = self.__dict__.pop('_waic')
+        for kind in kinds:
+            result = _lib.SUMS_KINDS[kind].result
+            setattr(out, result, self.__dict__.pop('_' + result))
         return out
 
-    def _check_site_summaries(self):
-        """Per-site summaries are accumulated by the engine's z update: a sampler with a Python ``step`` has none."""
-        if not hasattr(self, '_run_chains'):
-            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: site summaries are accumulated by the '
-                                      'device engine only')
+    @staticmethod
+    def _sums_asked(**options):
+        """The kinds of per-site sums (``_lib.SUMS_KINDS``) whose keyword is set."""
+        return [kind for kind, k in _lib.SUMS_KINDS.items() if options[k.option]]
 
-    def _check_waic(self):
-        """The log-likelihood sums are accumulated by the engine's z update: a sampler with a Python ``step`` has none."""
+    def _refuse_sums(self, kind):
+        """Per-site sums of either kind are accumulated by the engine's z update: a sampler with a Python ``step`` has none."""
         if not hasattr(self, '_run_chains'):
-            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: the log-likelihood sums of WAIC are '
-                                      'accumulated by the device engine only')
+            raise NotImplementedError(f'{self.__class__.__name__} {_lib.SUMS_KINDS[kind].python_step}')
 
     def copy(self):
         """A shallow copy with its own generator spawned from this one's seed sequence

@@ -1,9 +1,14 @@
 """``LogitICARGibbs`` on the MI355X engine (API of reference ``occuspytial/gibbs/logit.py:102-266``)."""
 import numpy as np
 
+from .. import _lib
 from .._engine import Engine, EngineGroup
 from ..chain import Chain
+from ..sites import SiteSummary
+from ..waic import WAIC
 from .base import GibbsBase
+
+SUMS_RESULT = {'site': SiteSummary, 'll': WAIC}   # kind of per-site sums (_lib.SUMS_KINDS) -> what a result holds of them
 
 
 def _philox_key(rng):
@@ -121,17 +126,11 @@ class LogitICARGibbs(GibbsBase):
             np.savez(path, **ckpt)
         return ckpt
 
-    def _site_switch(self, eng, on):
+    def _sums_switch(self, eng, kind, on):
         try:
-            eng.site_stats(on)
+            eng.sums_switch(kind, on)
         except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
-            raise ValueError(f'the loaded engine library has no site summaries ({exc}): rebuild it') from None
-
-    def _ll_switch(self, eng, on):
-        try:
-            eng.loglik_stats(on)
-        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
-            raise ValueError(f'the loaded engine library has no log-likelihood sums ({exc}): rebuild it') from None
+            raise ValueError(f'the loaded engine library has no {_lib.SUMS_KINDS[kind].what} ({exc}): rebuild it') from None
 
     def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False):
         """Continue the chains of ``checkpoint`` (a dict from :meth:`checkpoint` or the path of its ``.npz``)
@@ -152,14 +151,11 @@ class LogitICARGibbs(GibbsBase):
         self.__dict__['_stepping'] = False
         eng = self._get_engine([int(k) for k in np.asarray(checkpoint['keys'])])
         eng.restore(checkpoint)
-        if site_summaries:
-            self._check_site_summaries()
-            if 'site_stats' not in checkpoint:
-                self._site_switch(eng, True)
-        if waic:
-            self._check_waic()
-            if 'll_stats' not in checkpoint:
-                self._ll_switch(eng, True)
+        kinds = self._sums_asked(site_summaries=site_summaries, waic=waic)
+        for kind in kinds:
+            self._refuse_sums(kind)
+            if _lib.SUMS_KINDS[kind].fields[0] not in checkpoint:
+                self._sums_switch(eng, kind, True)
         alpha = np.zeros((C, size, self._problem.q))
         beta = np.zeros((C, size, self._problem.p))
         tau = np.zeros((C, size))
@@ -176,12 +172,8 @@ class LogitICARGibbs(GibbsBase):
         self.chain = chains[0]
         self._pull_state(eng, 0)
         out = PosteriorParameter(*chains)
-        if site_summaries:
-            from ..sites import SiteSummary
-            out.sites = SiteSummary.from_engine(eng)
-        if waic:
-            from ..waic import WAIC
-            out.waic = WAIC.from_engine(eng)
+        for kind in kinds:
+            setattr(out, _lib.SUMS_KINDS[kind].result, SUMS_RESULT[kind].from_engine(eng))
         return out
 
     # ------------------------------------------------------------------ batched chains
@@ -208,11 +200,11 @@ class LogitICARGibbs(GibbsBase):
         for c, s in enumerate(samplers):
             self._push_start(eng, c, s.state)
             eng.set('z', z0, c)
-        if site_summaries or getattr(eng, '_site_on', False):   # (a reused engine that an earlier call left switched on)
-            self._site_switch(eng, False)   # (also the early answer of a library that does not know site summaries)
-        if waic or getattr(eng, '_ll_on', False):
-            self._ll_switch(eng, False)
-        sites_on = ll_on = False
+        kinds = self._sums_asked(site_summaries=site_summaries, waic=waic)
+        for kind in _lib.SUMS_KINDS:
+            if kind in kinds or getattr(eng, '_sums_on', {}).get(kind):   # (a reused engine that an earlier call left switched on)
+                self._sums_switch(eng, kind, False)   # (also the early answer of a library that does not know the kind)
+        sums_on = False
 
         C = len(samplers)
         keep = size - burnin
@@ -228,12 +220,10 @@ class LogitICARGibbs(GibbsBase):
             if b == step:  # the whole chunk is burn-in: run it, keep only its last draw, drop it
                 eng.run(step, step - 1)
             else:
-                if site_summaries and not sites_on:
-                    self._site_switch(eng, True)
-                    sites_on = True
-                if waic and not ll_on:
-                    self._ll_switch(eng, True)
-                    ll_on = True
+                if not sums_on:
+                    for kind in kinds:
+                        self._sums_switch(eng, kind, True)
+                    sums_on = True
                 a_, b_, t_ = eng.run(step, b)
                 m = step - b
                 alpha[:, kept:kept + m], beta[:, kept:kept + m], tau[:, kept:kept + m] = a_, b_, t_
@@ -250,12 +240,8 @@ class LogitICARGibbs(GibbsBase):
             s.chain = ch
             chains.append(ch)
         self._pull_state(eng, 0)
-        if site_summaries:
-            from ..sites import SiteSummary
-            self.__dict__['_sites'] = SiteSummary.from_engine(eng)
-        if waic:
-            from ..waic import WAIC
-            self.__dict__['_waic'] = WAIC.from_engine(eng)
+        for kind in kinds:
+            self.__dict__['_' + _lib.SUMS_KINDS[kind].result] = SUMS_RESULT[kind].from_engine(eng)
         return chains
 
 

@@ -7,6 +7,7 @@ the same model with both fixed (DESIGN.md "ProbitRSRGibbs").
 """
 import numpy as np
 
+from .. import _lib
 from .._engine import Engine
 from .logit import LogitICARGibbs
 from .base import GibbsBase
@@ -97,13 +98,10 @@ class ProbitRSRGibbs(GibbsBase):
         st = self.state
         st.eps = eng.get('eps', chain)
 
-    def _check_site_summaries(self):
-        # (its z update conditions on the auxiliary eps: what "psi" should mean there is a modelling decision not yet made)
-        raise NotImplementedError('site summaries are not available for the probit model')
-
-    def _check_waic(self):
-        # (the same decision: its z update conditions on eps, so the site's marginal likelihood is not what it forms)
-        raise NotImplementedError('WAIC is not available for the probit model')
+    def _refuse_sums(self, kind):
+        # (its z update conditions on the auxiliary eps: what "psi" should mean there is a modelling decision not yet made,
+        # and the site's marginal likelihood is not what it forms)
+        raise NotImplementedError(_lib.SUMS_KINDS[kind].probit)
 
     step = LogitICARGibbs.step
     checkpoint = LogitICARGibbs.checkpoint
