@@ -168,7 +168,23 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  * switch-on: OCC_E_STATE; nothing is redrawn, a re-run call counts nothing twice, occ_profile and occ_cond_* never accumulate;
  * alpha, beta, tau, eta, z are bit-identical with the switch on or off; a probit handle answers every one of the names with
  * OCC_E_STATE.  ll_stats and site_stats are independent of each other: either, both or neither may be on for a chain, and
- * the site_* sums are the same bits with ll_stats on or off. */
+ * the site_* sums are the same bits with ll_stats on or off.
+ *
+ * Occupied sites per region and draw (every model: logit ICAR, logit reduced rank, probit): N_g(t) = sum over the sites i of
+ * region g of z_i(t), counted on the device by the z update and recorded per KEPT draw of occ_run, like alpha, beta and tau:
+ * row t = it - (first iteration of the call) - burnin, 0 <= t < keep.  Sites with a detection count (their z is 1 in every
+ * iteration); sites of no region (-1) do not.  Counts are unsigned 32-bit integers added with integer atomics: the same
+ * values whatever the path, the placement or the order of addition.
+ *   region_id(n)          the HANDLE's map, set and read through any valid chain index: whole numbers in [-1, 256), -1 = no
+ *                         region; G = max + 1 >= 1.  Another value: OCC_E_BADARG.  Settable only while no chain of the handle
+ *                         has region_stats on (else OCC_E_STATE); allocates at first use.
+ *   region_stats(1)       the chain's switch, 0 / 1 (another value: OCC_E_BADARG).
+ *   region_draws(keep G)  read-only: the chain's counts of the last completed occ_run, row-major [t][g], as doubles; length 0
+ *                         if the chain's switch was off during that call (or no call has completed since).
+ * Every one of the three names answers OCC_E_STATE before the handle's first region_id.  Nothing is redrawn; occ_set_start
+ * and occ_set_keys touch neither map nor switch; a call that is re-run after a device-side wait gave up counts nothing
+ * twice; occ_step, occ_profile and the occ_cond_* entry points never count.  alpha, beta, tau, eta, z and the site_* and
+ * ll_* sums are bit-identical with the switch on or off. */
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len);
 int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double *in, int64_t len);
 

@@ -116,6 +116,9 @@ class Engine:
         self.keys = [int(v) & (2 ** 64 - 1) for v in keys]
         # kind of per-site sums (_lib.SUMS_KINDS) -> switched on (sums_switch); off: no call about them reaches the library
         self._sums_on = dict.fromkeys(_lib.SUMS_KINDS, False)
+        # occupied sites per region and draw: the map (None: never set) and the switch; until set, no call about them reaches the library
+        self._regions = None
+        self._region_on = False
         _LIVE.add(self)
         return self
 
@@ -207,6 +210,9 @@ class Engine:
                 out[switch] = np.ones(self.n_chains)
                 for name in rest:
                     out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
+        if self._regions is not None:   # the map (one row per chain, as every entry) and the switch; the draws belong to a call
+            out['region_id'] = np.tile(self._regions, (self.n_chains, 1))
+            out['region_stats'] = np.full(self.n_chains, float(self._region_on))
         return out
 
     def restore(self, ckpt):
@@ -235,6 +241,33 @@ class Engine:
                         self.set(name, ckpt[name][c], c)
             elif self._sums_on[kind]:
                 self.sums_switch(kind, False)
+        if 'region_id' in ckpt:
+            self.regions(np.asarray(ckpt['region_id'])[0])
+            self.region_stats(bool(np.all(np.asarray(ckpt['region_stats']) != 0)))
+        elif self._region_on:
+            self.region_stats(False)
+
+    # ---- occupied sites per region and draw (state names region_*, include/occ_gibbs.h) ----
+    def regions(self, ids):
+        """Set the handle's map: the region of every site, whole numbers in [-1, 256), -1 for none.  The switches of all
+        chains go off first (the library sets a map only then)."""
+        ids = np.asarray(ids, dtype=np.int64).ravel()
+        if self._region_on:
+            self.region_stats(False)
+        self.set('region_id', ids.astype(np.float64), 0)
+        self._regions = ids.copy()
+
+    def region_stats(self, on):
+        """Switch the count of occupied sites per region of every chain.  While on, every kept draw of ``run`` records, per
+        region, the number of its sites with z = 1 (:meth:`region_draws`)."""
+        for c in range(self.n_chains):
+            self.set('region_stats', 1.0 if on else 0.0, c)
+        self._region_on = bool(on)
+
+    def region_draws(self, chain=0):
+        """``(keep, G)`` counts of one chain from the last ``run``; ``(0, G)`` if its switch was off during that call."""
+        G = max(int(self._regions.max()) + 1, 1) if self._regions is not None else 1
+        return self.get('region_draws', chain).reshape(-1, G)
 
     # ---- per-site sums accumulated on the device (state names site_* and ll_*, include/occ_gibbs.h), by kind ----
     def sums_switch(self, kind, on):
@@ -444,6 +477,27 @@ class EngineGroup:
     def sums(self, kind, chain=0):
         g, i = self.where[chain]
         return self.engines[g].sums(kind, i)
+
+    # occupied sites per region and draw: the map on every device, the draws routed by chain
+    @property
+    def _regions(self):
+        return getattr(self.engines[0], '_regions', None)
+
+    @property
+    def _region_on(self):
+        return any(getattr(e, '_region_on', False) for e in self.engines)
+
+    def regions(self, ids):
+        for e in self.engines:
+            e.regions(ids)
+
+    def region_stats(self, on):
+        for e in self.engines:
+            e.region_stats(on)
+
+    def region_draws(self, chain=0):
+        g, i = self.where[chain]
+        return self.engines[g].region_draws(i)
 
     # (the entry points by name are Engine's own: each only names its kind)
     site_stats, site_sums, loglik_stats, loglik_sums = Engine.site_stats, Engine.site_sums, Engine.loglik_stats, Engine.loglik_sums

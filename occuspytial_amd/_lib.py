@@ -19,6 +19,8 @@ N_KERNEL_KINDS = 9
 SITE_FIELDS = ('site_stats', 'site_count', 'site_psi', 'site_occ', 'site_z', 'site_eta', 'site_eta2')
 # likewise the per-site log-likelihood sums of streaming WAIC: switch, count, and the three sums of length n
 LOGLIK_FIELDS = ('ll_stats', 'll_count', 'll_lik', 'll_log', 'll_log2')
+# the occupied sites per region and draw: the handle's map (n), the chain's switch, the chain's counts of the last occ_run (keep G)
+REGION_FIELDS = ('region_id', 'region_stats', 'region_draws')
 KERNEL_KINDS = ('omega_b', 'noise', 'eta_init', 'minres', 'beta_partial', 'omega_a', 'alpha_draw', 'z_ob', 'iter')
 
 

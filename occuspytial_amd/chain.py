@@ -18,14 +18,15 @@ class Chain:
         self._store = {name: np.zeros((size, dim) if dim > 1 else size) for name, dim in params.items()}
 
     @classmethod
-    def _from_arrays(cls, arrays):
-        """Wrap already-filled arrays (one row per kept draw) without copying row by row."""
+    def _from_arrays(cls, arrays, vectors=()):
+        """Wrap already-filled arrays (one row per kept draw) without copying row by row.  ``vectors``: names that stay
+        ``(size, dim)`` even when ``dim`` is 1."""
         first = next(iter(arrays.values()))
         out = cls.__new__(cls)
         out.size = first.shape[0]
         out._names = tuple(arrays)
         out._index = first.shape[0]
-        out._store = {k: (v[:, 0] if (v.ndim > 1 and v.shape[1] == 1) else v) for k, v in arrays.items()}
+        out._store = {k: (v[:, 0] if (v.ndim > 1 and v.shape[1] == 1 and k not in vectors) else v) for k, v in arrays.items()}
         return out
 
     @property

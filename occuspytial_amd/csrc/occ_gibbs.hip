@@ -87,7 +87,7 @@ inline DeviceLease lease_device(int device) { return DeviceLease(device_slot(dev
 // occ_get_state / occ_set_state.  Whatever the host does for a kind -- names, snapshot and restore around a call that may
 // be re-run, the choice of kernel -- is a loop over this table.
 using KernelEI = void (*)(const Ctx *, ChainScalars *, Slot *, int, int, int);
-KernelEI pick_z_ob_stats(int p), pick_z_ob_ll(int p);  // (defined with the other choices of an instantiation, below)
+KernelEI pick_z_ob_stats(int p), pick_z_ob_ll(int p), pick_z_ob_occ(int p);  // (defined with the other choices of an instantiation, below)
 enum : int { SUMS_SITE = 0, SUMS_LL = 1, N_SUMS = 2 };
 struct SumsKind {
     uint32_t bit;  // of ChainScalars::site_on
@@ -102,6 +102,11 @@ const SumsKind SUMS[N_SUMS] = {
      {"site_psi", "site_occ", "site_z", "site_eta", "site_eta2"}, pick_z_ob_stats, 1},
     {2u, LL_NACC, &Ctx::ll_acc, &Ctx::ll_count, "log-likelihood sums", "ll_stats", "ll_count",
      {"ll_lik", "ll_log", "ll_log2"}, pick_z_ob_ll, 2}};
+// What occ_sampler::z_ob_kind() answers while a chain keeps the occupied sites per region and draw (bit REGION_BIT of
+// ChainScalars::site_on; occ_sampler::regions): k_z_ob_occ, which ranks above every kind of sums and serves them all.
+// Not a row of SUMS: it keeps no sums, has no count and nothing to snapshot -- its record is zeroed when a call's window opens.
+enum : int { Z_OB_OCC = N_SUMS };
+constexpr uint32_t REGION_BIT = 4u;
 
 }  // namespace
 
@@ -143,9 +148,32 @@ struct occ_sampler {
         bool launch = false, snapped = false;
         double *snap = nullptr;
     } sums[N_SUMS];
-    // the kind whose z-update kernel runs: of those with a chain switched on, the one of highest rank; -1: k_z_ob itself
+    // Occupied sites per region and kept draw (state names region_id, region_stats, region_draws).  G = 0: no map yet.
+    // launch: a chain has its switch on, so k_z_ob_occ (probit: k_pb_z_occ) stands where the plain kernel stands.  rec: the
+    // counts of the running occ_run on the device, [C][keep][G], sized like rec_buf and grown between calls, zeroed on the
+    // stream when the call's window opens and copied out (pin) behind its last batch; last: those of the last completed
+    // occ_run on the host, for the chains whose switch was on during it (last_on).
+    struct Regions {
+        bool launch = false;
+        int G = 0;
+        std::vector<int16_t> id;
+        int16_t *id_dev = nullptr;
+        uint32_t *rec = nullptr, *pin = nullptr;
+        size_t rec_cap = 0, pin_cap = 0, run_need = 0;
+        std::vector<uint32_t> last;
+        std::vector<uint8_t> last_on;
+        int64_t last_keep = 0;
+        int last_G = 0;
+        // probit handle: the chains' switches (its PbChain has no word for them) and the address of `rec`, in device memory
+        std::vector<uint32_t> pb_on;
+        uint32_t *pb_on_dev = nullptr;
+        uint32_t **pb_rec = nullptr;
+    } regions;
+    // the kind whose z-update kernel runs: Z_OB_OCC while a chain counts regions; else, of the kinds of sums with a chain
+    // switched on, the one of highest rank; -1: k_z_ob itself
     int z_ob_kind() const
     {
+        if (regions.launch) return Z_OB_OCC;
         int top = -1;
         for (int k = 0; k < N_SUMS; ++k)
             if (sums[k].launch && (top < 0 || SUMS[k].rank > SUMS[top].rank)) top = k;
@@ -437,6 +465,7 @@ KernelRsr pick_rsr_solve(int m)
 KernelEI pick_z_ob(int p) { return OCC_PICK_P(k_z_ob, p); }
 KernelEI pick_z_ob_stats(int p) { return OCC_PICK_P(k_z_ob_stats, p); }
 KernelEI pick_z_ob_ll(int p) { return OCC_PICK_P(k_z_ob_ll, p); }
+KernelEI pick_z_ob_occ(int p) { return OCC_PICK_P(k_z_ob_occ, p); }
 KernelEI pick_omega_a(int q)
 {
     switch (q) {
@@ -479,7 +508,7 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
     const int tp = P.generic ? 0 : c.p, tq = P.generic ? 0 : c.q;  // template arguments: 0 = the generic (run-time) instantiation
     const size_t lds_p = P.generic ? generic_lds_bytes(nacc(c.p), P.tpb) : 0, lds_q = P.generic ? generic_lds_bytes(nacc(c.q), P.tpb) : 0;
     const int zk = s->z_ob_kind();  // (a kind of per-site sums is switched on: its kernel where k_z_ob stands)
-    const KernelEI z_ob = zk < 0 ? pick_z_ob(tp) : SUMS[zk].z_ob(tp);
+    const KernelEI z_ob = zk < 0 ? pick_z_ob(tp) : zk == Z_OB_OCC ? pick_z_ob_occ(tp) : SUMS[zk].z_ob(tp);
     switch (kind) {
         case K_OMEGA_B: hipLaunchKernelGGL(pick_omega_b(tp), gs, blk, 0, st, OCC_ARGS); break;
         case K_NOISE:
@@ -1252,6 +1281,63 @@ int residency_probe(occ_sampler *s, bool *ok)
 
 }  // namespace
 
+// ---- occupied sites per region and draw: the record of one occ_run (both models) ---------------------------------------
+namespace {
+
+// Head of an occ_run with `keep` recorded rows: the device record holds C keep G counts (grown between calls: nothing is in
+// flight to the old one) and is zeroed on the stream in front of the call's kernels -- also when a call is re-run after a
+// run-time fallback, so a re-run counts nothing twice.  What the last call left on the host is dropped: region_draws
+// speaks of the last COMPLETED call.  *moved: the record's address changed (the descriptors that hold it are the caller's).
+int regions_open(occ_sampler *s, int C, int64_t keep, bool *moved)
+{
+    occ_sampler::Regions &rg = s->regions;
+    *moved = false;
+    rg.last.clear();
+    rg.last_on.assign((size_t)C, 0);
+    rg.last_keep = 0;
+    rg.run_need = rg.launch ? (size_t)C * (size_t)keep * (size_t)rg.G : 0;
+    if (!rg.run_need) return OCC_OK;
+    if (rg.run_need > rg.rec_cap) {
+        WAIT_TRY(s->stream);
+        if (rg.rec) HIP_TRY(hipFree(rg.rec));
+        rg.rec = nullptr;
+        rg.rec_cap = 0;
+        HIP_TRY(hipMalloc((void **)&rg.rec, sizeof(uint32_t) * rg.run_need));
+        rg.rec_cap = rg.run_need;
+        *moved = true;
+    }
+    if (rg.run_need > rg.pin_cap) {
+        WAIT_TRY(s->stream);
+        if (rg.pin) HIP_TRY(hipHostFree(rg.pin));
+        rg.pin = nullptr;
+        rg.pin_cap = 0;
+        const size_t cap = std::max<size_t>(rg.run_need, 4096);
+        HIP_TRY(hipHostMalloc((void **)&rg.pin, sizeof(uint32_t) * cap, hipHostMallocDefault));
+        rg.pin_cap = cap;
+    }
+    HIP_TRY(hipMemsetAsync(rg.rec, 0, sizeof(uint32_t) * rg.run_need, s->stream));
+    return OCC_OK;
+}
+// Behind the call's last batch, with the recorded rows: the copy to the page-locked staging buffer
+int regions_copy_out(occ_sampler *s)
+{
+    const occ_sampler::Regions &rg = s->regions;
+    if (rg.run_need) HIP_TRY(hipMemcpyAsync(rg.pin, rg.rec, sizeof(uint32_t) * rg.run_need, hipMemcpyDeviceToHost, s->stream));
+    return OCC_OK;
+}
+// Clean end of the call (the stream has been waited for): what region_draws answers from now on.  on[c]: chain c's switch
+void regions_close(occ_sampler *s, int64_t keep, const std::vector<uint8_t> &on)
+{
+    occ_sampler::Regions &rg = s->regions;
+    if (!rg.run_need) return;
+    rg.last.assign(rg.pin, rg.pin + rg.run_need);
+    rg.last_on = on;
+    rg.last_keep = keep;
+    rg.last_G = rg.G;
+}
+
+}  // namespace
+
 // ---- probit model (ProbitRSRGibbs): creation, one iteration, occ_run, state -------------------------------------------
 namespace {
 
@@ -1279,7 +1365,14 @@ int pb_launch_role(occ_sampler *s, hipStream_t st, int role)
                 default: return set_error(s, OCC_E_BADARG, "the probit model takes 1 to 8 detection covariates");
             }
             break;
-        case PB_Z: hipLaunchKernelGGL(k_pb_z, blocks((long long)A.C * A.n, PB_WG), dim3(PB_WG), 0, st, A); break;
+        case PB_Z:
+            if (s->regions.launch) {  // (a chain counts the occupied sites per region: the twin, one chain per workgroup)
+                const PbRegions rg = {s->regions.id_dev, s->regions.pb_on_dev, s->regions.pb_rec, s->regions.G};
+                hipLaunchKernelGGL(k_pb_z_occ, dim3((unsigned)((A.n + PB_WG - 1) / PB_WG), (unsigned)A.C), dim3(PB_WG), 0, st, A, rg);
+            } else {
+                hipLaunchKernelGGL(k_pb_z, blocks((long long)A.C * A.n, PB_WG), dim3(PB_WG), 0, st, A);
+            }
+            break;
         default: hipLaunchKernelGGL(k_pb_tail, blocks(A.C, 64), dim3(64), 0, st, A); break;
     }
     return OCC_OK;
@@ -1490,6 +1583,9 @@ int pb_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, do
     for (PbChain &c : h) { c.rec_first = c.it + (uint32_t)burnin; c.rec_keep = (uint32_t)keep; }
     if ((rc = pb_write_chains(s, h))) return rc;
     HIP_TRY(copy_on(s, A.rec, &s->rec_buf, sizeof(double *), hipMemcpyHostToDevice));
+    bool moved = false;
+    if ((rc = regions_open(s, A.C, keep, &moved))) return rc;
+    if (s->regions.run_need) HIP_TRY(copy_on(s, s->regions.pb_rec, &s->regions.rec, sizeof(uint32_t *), hipMemcpyHostToDevice));
     if (!s->pb_exec) {  // one linear graph of PB_GRAPH_SEQ iterations, captured once (the kernels take nothing that changes)
         HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
         for (int k = 0; k < PB_GRAPH_SEQ && rc == OCC_OK; ++k) rc = pb_launch_iteration(s, s->stream);
@@ -1512,12 +1608,17 @@ int pb_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, do
         ++s->eager_iterations;
     }
     HIP_TRY(hipEventRecord(s->ev1, s->stream));
+    if ((rc = regions_copy_out(s))) return rc;
     WAIT_TRY(s->stream);
     float ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     s->last_run_ms = ms;
     double *none = nullptr;
     HIP_TRY(copy_on(s, A.rec, &none, sizeof(double *), hipMemcpyHostToDevice));
+    if (s->regions.run_need) {  // (occ_step and occ_profile never count: outside occ_run the kernel finds no record)
+        uint32_t *no_rec = nullptr;
+        HIP_TRY(copy_on(s, s->regions.pb_rec, &no_rec, sizeof(uint32_t *), hipMemcpyHostToDevice));
+    }
     std::vector<double> rec(need);
     if (need) HIP_TRY(copy_on(s, rec.data(), s->rec_buf, sizeof(double) * need, hipMemcpyDeviceToHost));
     for (int c = 0; c < A.C; ++c)
@@ -1529,7 +1630,9 @@ int pb_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, do
         }
     if ((rc = pb_read_chains(s, h))) return rc;
     s->iterations = h[0].it;
-    return pb_check(s, h);
+    if ((rc = pb_check(s, h))) return rc;
+    regions_close(s, keep, std::vector<uint8_t>(s->regions.pb_on.begin(), s->regions.pb_on.end()));
+    return OCC_OK;
 }
 
 int pb_set_start(occ_sampler *s, int chain, const double *alpha, const double *beta, double tau, const double *theta)
@@ -1664,6 +1767,12 @@ int pb_set_state(occ_sampler *s, int chain, const std::string &nm, const double 
 int pb_profile(occ_sampler *s, int reps, int64_t counts[OCC_N_KERNEL_KINDS], double total_us[OCC_N_KERNEL_KINDS])
 {
     for (int k = 0; k < OCC_N_KERNEL_KINDS; ++k) { counts[k] = 0; total_us[k] = 0.0; }
+    struct PlainZ {  // (the timing loops launch k_pb_z itself, never the twin that counts the occupied sites per region)
+        occ_sampler *s;
+        bool old;
+        explicit PlainZ(occ_sampler *p) : s(p), old(p->regions.launch) { s->regions.launch = false; }
+        ~PlainZ() { s->regions.launch = old; }
+    } plain_z(s);
     std::vector<PbChain> saved;
     int rc = pb_read_chains(s, saved);
     if (rc) return rc;
@@ -1734,6 +1843,8 @@ int occ_destroy(occ_sampler *s)
             if (s->pb_graph) (void)hipGraphDestroy(s->pb_graph);
             for (void *p : s->allocs) (void)hipFree(p);
             if (s->rec_buf) (void)hipFree(s->rec_buf);
+            if (s->regions.rec) (void)hipFree(s->regions.rec);
+            if (s->regions.pin) (void)hipHostFree(s->regions.pin);
             if (s->pin_sc) (void)hipHostFree(s->pin_sc);
             if (s->pin_rec) (void)hipHostFree(s->pin_rec);
             for (hipEvent_t ev : {s->ev0, s->ev1, s->ev_z[0], s->ev_z[1], s->ev_side[0], s->ev_side[1]})
@@ -2767,6 +2878,8 @@ static int finish_marks(occ_sampler *s, bool last, size_t n_rec)
         s->pin_rec_cap = cap;
     }
     if (n_rec) HIP_TRY(hipMemcpyAsync(s->pin_rec, s->rec_buf, sizeof(double) * n_rec, hipMemcpyDeviceToHost, s->stream));
+    const int rrc = regions_copy_out(s);
+    if (rrc) return rrc;
     s->marks_done = true;
     return OCC_OK;
 }
@@ -2786,12 +2899,15 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
         HIP_TRY(hipMalloc((void **)&s->rec_buf, sizeof(double) * need));
         s->rec_cap = need;
     }
-    if (c.rec != s->rec_buf) {
+    bool occ_moved = false;
+    int rc = regions_open(s, C, keep, &occ_moved);  // (zeroed here, in front of the window: also when the call is re-run)
+    if (rc) return rc;
+    if (c.rec != s->rec_buf || c.occ_rec != s->regions.rec) {
         c.rec = s->rec_buf;
+        c.occ_rec = s->regions.rec;
         HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
     }
-    int rc = open_window(s, n_iter, burnin, keep, snapshot, true);
-    if (rc) return rc;
+    if ((rc = open_window(s, n_iter, burnin, keep, snapshot, true))) return rc;
     std::vector<ChainScalars> h;
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
     s->marks_done = false;
@@ -2929,6 +3045,9 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
             std::copy(row + q, row + q + p, out_beta + ((size_t)ch * keep + t) * p);
             out_tau[(size_t)ch * keep + t] = row[q + p];
         }
+    std::vector<uint8_t> occ_on((size_t)C, 0);
+    for (int ch = 0; ch < C; ++ch) occ_on[(size_t)ch] = (h[ch].site_on & REGION_BIT) ? 1 : 0;
+    regions_close(s, keep, occ_on);
     return OCC_OK;
 }
 
@@ -3169,6 +3288,125 @@ static int set_site_state(occ_sampler *s, int chain, int kind, int field, const 
     return OCC_OK;
 }
 
+// ---- occ_get_state / occ_set_state of the region names (both models) --------------------------------------------------
+// region_id (n): the handle's map, through any chain index -- whole numbers in [-1, REGION_MAX), -1: no region, G = max + 1
+// (at least 1); set only while no chain counts; allocates at first use.  region_stats (1): the chain's switch, 0 or 1.
+// region_draws (keep G, read-only): the chain's counts of the last completed occ_run, row-major [t][g]; length 0 if its
+// switch was off during that call.  Before the first region_id every name answers OCC_E_STATE.  Nothing of a chain's state
+// changes: nothing is redrawn.  Which z kernel is launched follows "is any chain on" (occ_sampler::z_ob_kind): a change
+// drops the captured graphs.
+enum : int { REGION_NONE = -1, REGION_ID = 0, REGION_SWITCH = 1, REGION_DRAWS = 2 };
+static int region_field(const std::string &nm)
+{
+    return nm == "region_id" ? REGION_ID : nm == "region_stats" ? REGION_SWITCH : nm == "region_draws" ? REGION_DRAWS : REGION_NONE;
+}
+static int regions_unset(occ_sampler *s)
+{
+    return set_error(s, OCC_E_STATE, "no regions have been set for this handle (set region_id first)");
+}
+// the chains' switches as the handle holds them now
+static int region_switches(occ_sampler *s, std::vector<uint8_t> &on, std::vector<ChainScalars> *scalars = nullptr)
+{
+    on.assign((size_t)s->ctx.C, 0);
+    if (s->probit) {
+        for (size_t c = 0; c < on.size() && c < s->regions.pb_on.size(); ++c) on[c] = s->regions.pb_on[c] != 0u;
+        return OCC_OK;
+    }
+    std::vector<ChainScalars> h;
+    const int rc = read_scalars(s, h);
+    if (rc) return rc;
+    for (size_t c = 0; c < on.size(); ++c) on[c] = (h[c].site_on & REGION_BIT) != 0u;
+    if (scalars) scalars->swap(h);
+    return OCC_OK;
+}
+static int get_region_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
+{
+    const occ_sampler::Regions &rg = s->regions;
+    if (rg.G == 0) return regions_unset(s);
+    if (field == REGION_ID) {
+        v.assign(rg.id.begin(), rg.id.end());
+    } else if (field == REGION_SWITCH) {
+        std::vector<uint8_t> on;
+        const int rc = region_switches(s, on);
+        if (rc) return rc;
+        v.assign(1, on[(size_t)chain] ? 1.0 : 0.0);
+    } else {
+        v.clear();
+        if ((size_t)chain < rg.last_on.size() && rg.last_on[(size_t)chain]) {
+            const size_t per = (size_t)rg.last_keep * (size_t)rg.last_G;
+            v.assign(rg.last.begin() + (size_t)chain * per, rg.last.begin() + (size_t)(chain + 1) * per);
+        }
+    }
+    return OCC_OK;
+}
+static int set_region_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+{
+    occ_sampler::Regions &rg = s->regions;
+    Ctx &c = s->ctx;
+    const size_t n = (size_t)c.n;
+    int rc;
+    if (field == REGION_DRAWS) return set_error(s, OCC_E_STATE, rg.G == 0 ? "no regions have been set for this handle (set region_id first)" : "region_draws is read-only");
+    if (field == REGION_SWITCH && rg.G == 0) return regions_unset(s);
+    std::vector<uint8_t> on;
+    std::vector<ChainScalars> h;
+    if ((rc = region_switches(s, on, &h))) return rc;
+    if (field == REGION_ID) {
+        for (uint8_t o : on)
+            if (o) return set_error(s, OCC_E_STATE, "region_id cannot be set while a chain has region_stats on");
+        if ((size_t)len != n) return set_error(s, OCC_E_STATE, "wrong length");
+        std::vector<int16_t> id(n);
+        int top = 0;
+        for (size_t i = 0; i < n; ++i) {
+            if (!(in[i] >= -1.0 && in[i] < (double)REGION_MAX) || in[i] != std::floor(in[i]))
+                return set_error(s, OCC_E_BADARG, "region_id holds whole numbers from -1 (no region) to 255");
+            id[i] = (int16_t)in[i];
+            top = std::max(top, (int)id[i]);
+        }
+        WAIT_TRY(s->side);
+        if (!rg.id_dev) {
+            if ((rc = dev_alloc(s, &rg.id_dev, n))) return rc;
+            if (s->probit) {
+                if ((rc = dev_alloc(s, &rg.pb_on_dev, (size_t)c.C))) return rc;
+                if ((rc = dev_alloc(s, &rg.pb_rec, 1))) return rc;
+                rg.pb_on.assign((size_t)c.C, 0u);
+            }
+        }
+        HIP_TRY(copy_on(s, rg.id_dev, id.data(), sizeof(int16_t) * n, hipMemcpyHostToDevice));
+        rg.id.swap(id);
+        rg.G = top + 1;
+        if (!s->probit) {
+            c.region_id = rg.id_dev;
+            c.region_G = rg.G;
+            HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
+        }
+        return OCC_OK;
+    }
+    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
+    if (in[0] != 0.0 && in[0] != 1.0) return set_error(s, OCC_E_BADARG, "region_stats is 0 or 1");
+    on[(size_t)chain] = in[0] != 0.0;
+    bool any = false;
+    for (uint8_t o : on) any = any || o;
+    WAIT_TRY(s->side);
+    if (s->probit) {
+        rg.pb_on[(size_t)chain] = on[(size_t)chain];
+        HIP_TRY(copy_on(s, rg.pb_on_dev, rg.pb_on.data(), sizeof(uint32_t) * rg.pb_on.size(), hipMemcpyHostToDevice));
+        if (any != rg.launch) {  // (the choice of kernel is baked into the captured graph)
+            if (s->pb_exec) (void)hipGraphExecDestroy(s->pb_exec);
+            if (s->pb_graph) (void)hipGraphDestroy(s->pb_graph);
+            s->pb_exec = nullptr;
+            s->pb_graph = nullptr;
+        }
+        rg.launch = any;
+        return OCC_OK;
+    }
+    h[chain].site_on = (h[chain].site_on & ~REGION_BIT) | (on[(size_t)chain] ? REGION_BIT : 0u);
+    if ((rc = write_scalars(s, h))) return rc;
+    const int z_ob_before = s->z_ob_kind();
+    rg.launch = any;
+    if (s->z_ob_kind() != z_ob_before) destroy_graph(s);
+    return OCC_OK;
+}
+
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len)
 {
     if (!s || !name || !len) return OCC_E_BADARG;
@@ -3180,6 +3418,10 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     const std::string nm(name);
     const size_t n = (size_t)c.n, R = (size_t)c.R;
     std::vector<double> v;
+    if (region_field(nm) != REGION_NONE) {
+        const int rrc = get_region_state(s, chain, region_field(nm), v);
+        return rrc ? rrc : give_state(s, v, out, cap, len);
+    }
     int sums_kind = SUMS_SITE;
     const int site_q = site_field(nm, &sums_kind);
     const SumsKind &sk = SUMS[sums_kind];
@@ -3245,6 +3487,7 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     HIP_TRY(hipSetDevice(s->device));
     WAIT_TRY(s->stream);
     const std::string nm(name);
+    if (region_field(nm) != REGION_NONE) return set_region_state(s, chain, region_field(nm), in, len);
     int sums_kind = SUMS_SITE;
     const int sums_q = site_field(nm, &sums_kind);
     if (sums_q != SITE_NONE) return set_site_state(s, chain, sums_kind, sums_q, in, len);
@@ -3416,14 +3659,16 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     // handle is replayed here)
     struct PlainZob {
         occ_sampler *s;
-        bool old[N_SUMS];
-        explicit PlainZob(occ_sampler *p) : s(p)
+        bool old[N_SUMS], old_regions;
+        explicit PlainZob(occ_sampler *p) : s(p), old_regions(p->regions.launch)
         {
             for (int k = 0; k < N_SUMS; ++k) old[k] = s->sums[k].launch, s->sums[k].launch = false;
+            s->regions.launch = false;
         }
         ~PlainZob()
         {
             for (int k = 0; k < N_SUMS; ++k) s->sums[k].launch = old[k];
+            s->regions.launch = old_regions;
         }
     } plain_z_ob(s);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops

@@ -112,7 +112,8 @@ struct ChainScalars {
     int32_t err;               // OCC_E_* raised on device
     int32_t minres_itn_last;
     uint32_t site_on;          // bit 0: per-site posterior sums (Ctx::site_acc) are kept for this chain; bit 1: the log-likelihood
-                               // sums (Ctx::ll_acc); sits where the layout had padding
+                               // sums (Ctx::ll_acc); bit 2: the occupied sites per region and draw (Ctx::occ_rec); sits where
+                               // the layout had padding
     unsigned long long krylov_total, krylov_sq_total, solves, carries;
 };
 
@@ -200,6 +201,12 @@ struct Ctx {
     // the surveyed sites, and the iterations added per chain.
     double *ll_acc;
     double *ll_count;  // [C]
+    // Occupied sites per region and kept draw (state names region_*; null until the handle's map is first set): the region of
+    // every site, -1 for none, the number of regions G = max + 1, and the counts of the running occ_run, [C][keep][G] --
+    // added to by the z update of k_z_ob_occ with integer atomics, zeroed by the host when the call's window opens.
+    const int16_t *region_id;  // [n]
+    uint32_t *occ_rec;
+    int region_G;
 };
 
 // ---- reductions ----------------------------------------------------------------------------------
@@ -2093,7 +2100,7 @@ __device__ __forceinline__ double expit_e(double a, double e) { return a < 0.0 ?
 // psi, the product, D, the probability and z are formed by the operations of z_update_site: the same bits.
 // xb_of(): x_i beta; wa_of(r): -w_r alpha (the fixed and the run-time forms of the two dot products).
 template <int INJ, class XB, class WA>
-__device__ __forceinline__ void z_update_site_ll(const Ctx &c, uint64_t key, int chain, int i, uint32_t it, double eta_i, bool stats_on,
+__device__ __forceinline__ int z_update_site_ll(const Ctx &c, uint64_t key, int chain, int i, uint32_t it, double eta_i, bool stats_on,
                                                  XB xb_of, WA wa_of)
 {
     const int sidx = c.site_sidx[i], n = c.n;
@@ -2117,7 +2124,7 @@ __device__ __forceinline__ void z_update_site_ll(const Ctx &c, uint64_t key, int
         if (seen) {
             if (stats_on) site_add(c, chain, i, num1, 1.0, 1.0, eta_i);
             ll_add(c, chain, i, exp(ll), ll);
-            return;
+            return 1;
         }
         const double num = num1 * prod;
         const double den = (1.0 - num1) + num;  // the site's likelihood: what the update divides by
@@ -2127,6 +2134,7 @@ __device__ __forceinline__ void z_update_site_ll(const Ctx &c, uint64_t key, int
     const double u = INJ ? c.inj->z_u[i] : block_uniform(key, (uint32_t)i, 0, it, STREAM_Z);
     c.z[(size_t)chain * n + i] = (u < pr) ? 1 : 0;
     if (stats_on) site_add(c, chain, i, num1, pr, (u < pr) ? 1.0 : 0.0, eta_i);
+    return (u < pr) ? 1 : 0;
 }
 
 // STATS (k_z_ob_stats, k_z_ob_ll; `stats_on`: this chain, this iteration): the site's psi, P(z = 1 | rest), new z, eta and
@@ -2136,12 +2144,12 @@ __device__ __forceinline__ void z_update_site_ll(const Ctx &c, uint64_t key, int
 // update itself is the likelihood, l = log D.  A detection: l = lsig(x_i beta + eta_i) + sum_r lsig(+- w_r alpha), + where
 // y_r = 1, the rows added in row order, L = exp(l).  Such a chain's sites go through z_update_site_ll (above).
 template <int P, int INJ = 0, int STATS = 0>
-__device__ __forceinline__ void z_update_site(const Ctx &c, uint64_t key, int chain, int i, uint32_t it, const double (&beta)[P],
+__device__ __forceinline__ int z_update_site(const Ctx &c, uint64_t key, int chain, int i, uint32_t it, const double (&beta)[P],
                                               const double (&alpha)[MAXC], double eta_i, bool stats_on = false, bool ll_on = false)
 {
-    if constexpr (STATS == 2) {
+    if constexpr (STATS >= 2) {
         if (ll_on) {  // (uniform over the workgroup: a chain's switch)
-            z_update_site_ll<INJ>(
+            return z_update_site_ll<INJ>(
                 c, key, chain, i, it, eta_i, stats_on,
                 [&]() {
                     double xb = 0.0;
@@ -2156,7 +2164,6 @@ __device__ __forceinline__ void z_update_site(const Ctx &c, uint64_t key, int ch
                         if (a < c.q) wa = fma(c.Wt[(size_t)a * c.R + r], -alpha[a], wa);
                     return wa;
                 });
-            return;
         }
     }
     const int sidx = c.site_sidx[i];
@@ -2170,7 +2177,7 @@ __device__ __forceinline__ void z_update_site(const Ctx &c, uint64_t key, int ch
                 site_add(c, chain, i, expit(xb + eta_i), 1.0, 1.0, eta_i);
             }
         }
-        return;
+        return 1;
     }
     const int n = c.n, Q = c.q;
     double xb = 0.0;
@@ -2197,6 +2204,7 @@ __device__ __forceinline__ void z_update_site(const Ctx &c, uint64_t key, int ch
     if constexpr (STATS) {
         if (stats_on) site_add(c, chain, i, num1, pr, (u < pr) ? 1.0 : 0.0, eta_i);
     }
+    return (u < pr) ? 1 : 0;
 }
 template <int P>
 __device__ __forceinline__ void record_draws(const Ctx &c, const ChainScalars &sc, int chain, uint32_t it, const double (&alpha)[MAXC],
@@ -2212,6 +2220,39 @@ __device__ __forceinline__ void record_draws(const Ctx &c, const ChainScalars &s
 #pragma unroll
     for (int a = 0; a < P; ++a) row[Q + a] = beta[a];
     row[Q + P] = tau;
+}
+
+// Occupied sites per region (Ctx::occ_rec): one workgroup's sites into the G counts of one chain and kept draw, `row`.
+// EVERY thread of the workgroup comes here (the barriers): `g` the region of the thread's site -- -1: none, or no site --
+// and `zi` its new z.  The workgroup reduces in LDS first -- one region: a wave's ballot and popcount, one LDS add per wave;
+// several: one LDS add per occupied site -- and then issues one global add per region present among its sites.  Integer
+// adds: their order cannot change a bit.
+constexpr int REGION_MAX = 256;  // regions of a handle (the header's range of region_id)
+__device__ __forceinline__ void region_count(uint32_t *__restrict__ row, int G, int g, int zi)
+{
+    __shared__ unsigned s_occ[REGION_MAX];
+    const bool one = zi != 0 && g >= 0;
+    for (int k = threadIdx.x; k < G; k += blockDim.x) s_occ[k] = 0u;
+    __syncthreads();
+    if (G == 1) {
+        const unsigned long long m = __ballot(one);
+        if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(&s_occ[0], (unsigned)__popcll(m));
+    } else if (one) {
+        atomicAdd(&s_occ[g], 1u);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < G; k += blockDim.x) {
+        const unsigned v = s_occ[k];
+        if (v != 0u) atomicAdd(row + k, v);
+    }
+}
+// STATS = 3 (k_z_ob_occ): the row of Ctx::occ_rec this pass adds to, or null -- the chain's bit 2 is on and iteration `it`
+// is one the call records (the rows of record_draws).  Uniform over the workgroup.
+__device__ __forceinline__ uint32_t *region_row(const Ctx &c, const ChainScalars &sc, int chain, uint32_t it)
+{
+    const uint32_t rel = it - sc.it_base;
+    if (!(sc.site_on & 4u) || c.occ_rec == nullptr || rel < sc.burnin || rel - sc.burnin >= sc.keep) return nullptr;
+    return c.occ_rec + ((size_t)chain * sc.keep + (rel - sc.burnin)) * (size_t)c.region_G;
 }
 
 template <int P, int STATS = 0>
@@ -2354,7 +2395,20 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
     }
     if (writer) record_draws<P>(c, sc, chain, it, alpha, beta, sc.tau);
     const int n = c.n, i = (blk >> 1) * blockDim.x + threadIdx.x;
-    if constexpr (STATS == 2) {
+    if constexpr (STATS == 3) {
+        // the two kinds of sums and the region counts, each where the chain's bit is on.  No thread leaves before the
+        // counts' barriers: one past n, or of a site with a detection, comes back from the update with its z
+        const uint32_t on = sc.site_on;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        if (debug_skip & 1) return;
+        if (writer && stats_on) c.site_count[chain] += 1.0;
+        if (writer && ll_on) c.ll_count[chain] += 1.0;
+        uint32_t *row = region_row(c, sc, chain, it);
+        const int g = (row != nullptr && i < n) ? (int)c.region_id[i] : -1;  // (asked for ahead of the update's own loads)
+        int zi = 0;
+        if (i < n) zi = z_update_site<P, 0, 3>(c, key, chain, i, it, beta, alpha, c.eta[(size_t)chain * n + i], stats_on, ll_on);
+        if (row != nullptr) region_count(row, c.region_G, g, zi);
+    } else if constexpr (STATS == 2) {
         // both kinds of sums, each where the chain's bit is on: the same iterations count for either
         const uint32_t on = sc.site_on;
         const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
@@ -2377,12 +2431,12 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
 // The z update of one site with run-time numbers of covariates (generic path); alpha and beta come from the chain's
 // scalars.  Same operations as z_update_site.
 template <int INJ, int STATS = 0>
-__device__ __forceinline__ void z_update_site_g(const Ctx &c, const ChainScalars &sc, int chain, int i, uint32_t it, double eta_i,
+__device__ __forceinline__ int z_update_site_g(const Ctx &c, const ChainScalars &sc, int chain, int i, uint32_t it, double eta_i,
                                                 bool stats_on = false, bool ll_on = false)
 {
-    if constexpr (STATS == 2) {
+    if constexpr (STATS >= 2) {
         if (ll_on) {
-            z_update_site_ll<INJ>(
+            return z_update_site_ll<INJ>(
                 c, sc.key, chain, i, it, eta_i, stats_on,
                 [&]() {
                     double xb = 0.0;
@@ -2394,7 +2448,6 @@ __device__ __forceinline__ void z_update_site_g(const Ctx &c, const ChainScalars
                     for (int a = 0; a < c.q; ++a) wa = fma(c.Wt[(size_t)a * c.R + r], -sc.alpha[a], wa);
                     return wa;
                 });
-            return;
         }
     }
     const int sidx = c.site_sidx[i];
@@ -2407,7 +2460,7 @@ __device__ __forceinline__ void z_update_site_g(const Ctx &c, const ChainScalars
                 site_add(c, chain, i, expit(xb + eta_i), 1.0, 1.0, eta_i);
             }
         }
-        return;
+        return 1;
     }
     const int n = c.n, P = c.p, Q = c.q;
     double xb = 0.0;
@@ -2431,6 +2484,7 @@ __device__ __forceinline__ void z_update_site_g(const Ctx &c, const ChainScalars
     if constexpr (STATS) {
         if (stats_on) site_add(c, chain, i, num1, pr, (u < pr) ? 1.0 : 0.0, eta_i);
     }
+    return (u < pr) ? 1 : 0;
 }
 
 // k_z_ob of the generic path: beta has been drawn by k_beta_draw<0> (the previous kernel of the stream); this path never
@@ -2466,7 +2520,18 @@ __device__ __forceinline__ void z_ob_body_g(const Ctx &c, ChainScalars *__restri
         }
     }
     const int n = c.n, i = (blk >> 1) * blockDim.x + threadIdx.x;
-    if constexpr (STATS == 2) {
+    if constexpr (STATS == 3) {
+        const uint32_t on = sc.site_on;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        if (debug_skip & 1) return;
+        if (writer && stats_on) c.site_count[chain] += 1.0;
+        if (writer && ll_on) c.ll_count[chain] += 1.0;
+        uint32_t *row = region_row(c, sc, chain, it);
+        const int g = (row != nullptr && i < n) ? (int)c.region_id[i] : -1;
+        int zi = 0;
+        if (i < n) zi = z_update_site_g<0, 3>(c, sc, chain, i, it, c.eta[(size_t)chain * n + i], stats_on, ll_on);
+        if (row != nullptr) region_count(row, c.region_G, g, zi);
+    } else if constexpr (STATS == 2) {
         const uint32_t on = sc.site_on;
         const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
         if (writer && stats_on && !(debug_skip & 1)) c.site_count[chain] += 1.0;
@@ -2569,6 +2634,23 @@ __global__ void __launch_bounds__(256, 3) k_z_ob_ll(OCC_KARGS, int flags)  // fl
         const bool synced = (flags & 1) && c.sync != nullptr;
         const unsigned seq = synced ? (unsigned)__builtin_amdgcn_readfirstlane((int)c.sync[SYNC_MAIN]) : 0u;  // (uniform: a scalar register)
         z_ob_body<P, 2>(c, scs, chain_base, e, synced, seq, (flags & 2) != 0, (flags >> 3) & 3, (flags & 4) != 0);
+    }
+}
+
+// k_z_ob with the occupied sites per region and draw (Ctx::occ_rec), the log-likelihood sums and the per-site posterior sums,
+// each for the chains whose bit of ChainScalars::site_on is set: launched in k_z_ob's place while a chain of the handle has
+// bit 2 on.  A fourth kernel family, so that the three above stay the code they were.
+template <int P>
+__global__ void __launch_bounds__(256, 3) k_z_ob_occ(OCC_KARGS, int flags)  // flags: k_z_ob's
+{
+    __builtin_amdgcn_s_setprio(3);
+    const Ctx &c = *cp;
+    if constexpr (P == 0) {
+        z_ob_body_g<3>(c, scs, chain_base, e, (flags & 2) != 0, (flags >> 3) & 3);
+    } else {
+        const bool synced = (flags & 1) && c.sync != nullptr;
+        const unsigned seq = synced ? (unsigned)__builtin_amdgcn_readfirstlane((int)c.sync[SYNC_MAIN]) : 0u;  // (uniform: a scalar register)
+        z_ob_body<P, 3>(c, scs, chain_base, e, synced, seq, (flags & 2) != 0, (flags >> 3) & 3, (flags & 4) != 0);
     }
 }
 

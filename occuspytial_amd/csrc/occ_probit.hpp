@@ -388,13 +388,11 @@ __global__ void __launch_bounds__(PB_WG) k_pb_alpha(const PbArgs A)
     }
 }
 
-__global__ void __launch_bounds__(PB_WG) k_pb_z(const PbArgs A)
+// the z update of one site of one chain -> its z
+__device__ __forceinline__ int pb_z_site(const PbArgs &A, int chain, int i)
 {
-    const long long g = (long long)blockIdx.x * PB_WG + threadIdx.x;
-    if (g >= (long long)A.C * A.n) return;
-    const int chain = (int)(g / A.n), i = (int)(g - (long long)chain * A.n);
     const int t = A.sidx[i];
-    if (t >= 0 && A.obs_site[t]) return;  // a detection: z stays 1
+    if (t >= 0 && A.obs_site[t]) return 1;  // a detection: z stays 1
     const PbChain &ch = A.ch[chain];
     const size_t ci = (size_t)chain * A.n + i;
     const double loc = (xdot(A.Xt, A.n, i, ch.beta, A.p) + A.eta[ci]) + A.eps[ci];
@@ -412,6 +410,40 @@ __global__ void __launch_bounds__(PB_WG) k_pb_z(const PbArgs A)
     }
     const double u = block_uniform(ch.key, (uint32_t)i, 0, ch.it, STREAM_Z);
     A.z[ci] = u < pr ? 1 : 0;
+    return u < pr ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(PB_WG) k_pb_z(const PbArgs A)
+{
+    const long long g = (long long)blockIdx.x * PB_WG + threadIdx.x;
+    if (g >= (long long)A.C * A.n) return;
+    const int chain = (int)(g / A.n), i = (int)(g - (long long)chain * A.n);
+    (void)pb_z_site(A, chain, i);
+}
+
+// k_pb_z with the occupied sites per region and draw: launched in its place while a chain of the handle has its switch on.
+// One chain per workgroup (blockIdx.y), so that a workgroup's sites share the row they add to (region_count); the update of
+// a site is k_pb_z's own function: the same z.  `on` [C]: the chains' switches; *rec: [C][rec_keep][G] counts of the running
+// occ_run, or null; the rows are those k_pb_tail records.
+struct PbRegions {
+    const int16_t *region_id;  // [n], -1: no region
+    const uint32_t *on;
+    uint32_t **rec;
+    int G;
+};
+__global__ void __launch_bounds__(PB_WG) k_pb_z_occ(const PbArgs A, const PbRegions Rg)
+{
+    const int chain = blockIdx.y, i = blockIdx.x * PB_WG + threadIdx.x;
+    const PbChain &ch = A.ch[chain];
+    const uint32_t it = ch.it;
+    uint32_t *rec = *Rg.rec;
+    uint32_t *row = nullptr;  // (uniform over the workgroup)
+    if (rec && Rg.on[chain] && it >= ch.rec_first && it - ch.rec_first < ch.rec_keep)
+        row = rec + ((size_t)chain * ch.rec_keep + (it - ch.rec_first)) * (size_t)Rg.G;
+    const int g = (row != nullptr && i < A.n) ? (int)Rg.region_id[i] : -1;
+    int zi = 0;
+    if (i < A.n) zi = pb_z_site(A, chain, i);
+    if (row != nullptr) region_count(row, Rg.G, g, zi);
 }
 
 __global__ void __launch_bounds__(64) k_pb_tail(const PbArgs A)

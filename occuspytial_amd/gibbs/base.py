@@ -14,6 +14,7 @@ from .._problem import FlatProblem, default_start
 from ..chain import Chain
 from ..data import Data
 from ..posterior import PosteriorParameter
+from ..regions import region_ids
 from ..utils import get_generator
 from .parallel import sample_parallel
 from .state import FixedState, State
@@ -114,7 +115,7 @@ class GibbsBase:
                 self.chain.append(self.state.posteriors)
         return self.chain
 
-    def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False, waic=False):
+    def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False, waic=False, regions=None):
         """Draw ``size`` iterations per chain and return the kept ``alpha``, ``beta``, ``tau`` draws.
 
         Same contract as the reference (``base.py:243-291``): ``burnin < size`` else ``ValueError``;
@@ -128,6 +129,12 @@ class GibbsBase:
         ``waic=True`` (the same samplers) accumulates, over the same iterations, every surveyed site's marginal likelihood
         and log-likelihood (z integrated out) on the device and returns ``out.waic``, a :class:`~occuspytial_amd.waic.WAIC`
         (``None`` otherwise): compare two fits with :func:`occuspytial_amd.waic.compare`.
+
+        ``regions`` (every sampler that runs on the engine, the probit one included): ``True`` -- the whole lattice as one
+        region -- or an integer array with the region of every site, ``-1`` for none.  The device then counts, per kept
+        draw, the occupied sites of every region: ``out['occupied']`` is ``(chains, size - burnin, G)``, it appears in
+        ``out.summary`` (mean, sd, HDI, ESS, R-hat of the finite-sample occupancy), and ``out.regions`` is a
+        :class:`~occuspytial_amd.regions.RegionOccupancy` (sizes, detected sites, proportion of area occupied).
         """
         if burnin >= size:
             raise ValueError('burnin value cannot be larger than sample size')
@@ -137,13 +144,29 @@ class GibbsBase:
         for kind in kinds:
             self._refuse_sums(kind)
         extra = {_lib.SUMS_KINDS[kind].option: True for kind in kinds}   # (with the defaults, no keyword about them goes on)
+        ids = region_ids(regions, self._problem.n)
+        if ids is not None:
+            self._refuse_regions()
+            extra['regions'] = ids
         samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start,
                                   progressbar=progressbar, **extra)
         out = PosteriorParameter(*samples)
         for kind in kinds:
             result = _lib.SUMS_KINDS[kind].result
             setattr(out, result, self.__dict__.pop('_' + result))
+        if ids is not None:
+            out.regions = self._region_result(ids, out)
         return out
+
+    def _refuse_regions(self):
+        """The occupied sites per region are counted by the engine's z update: a sampler with a Python ``step`` has none."""
+        if not hasattr(self, '_run_chains'):
+            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: the occupied sites per region are counted by '
+                                      'the device engine only')
+
+    def _region_result(self, ids, post):
+        from ..regions import RegionOccupancy
+        return RegionOccupancy(ids, self._problem.obs, post['occupied'])
 
     @staticmethod
     def _sums_asked(**options):

@@ -4,6 +4,7 @@ import numpy as np
 from .. import _lib
 from .._engine import Engine, EngineGroup
 from ..chain import Chain
+from ..regions import region_ids
 from ..sites import SiteSummary
 from ..waic import WAIC
 from .base import GibbsBase
@@ -132,14 +133,21 @@ class LogitICARGibbs(GibbsBase):
         except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
             raise ValueError(f'the loaded engine library has no {_lib.SUMS_KINDS[kind].what} ({exc}): rebuild it') from None
 
-    def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False):
+    def _regions_call(self, call):
+        try:
+            return call()
+        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
+            raise ValueError(f'the loaded engine library does not count the occupied sites per region ({exc}): rebuild it') from None
+
+    def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False, regions=None):
         """Continue the chains of ``checkpoint`` (a dict from :meth:`checkpoint` or the path of its ``.npz``)
         for ``size`` more iterations on this sampler's problem.  Returns a ``PosteriorParameter`` of the new
         draws; every chain's ``Chain`` is the continuation (use ``Chain.expand`` / ``append`` to join them to
         earlier draws).  The result equals the tail of an uninterrupted run bit for bit.  ``site_summaries=True``: the
         per-site sums go on from those the checkpoint holds (from zero if it holds none); the result's ``sites`` covers
         every iteration accumulated so far, those before the checkpoint included.  ``waic=True``: the same for the
-        log-likelihood sums and the result's ``waic``."""
+        log-likelihood sums and the result's ``waic``.  ``regions`` (as in :meth:`sample`): the occupied sites per region of
+        the new draws, ``out['occupied']`` and ``out.regions``; the draws belong to a call, so nothing of them is carried."""
         from ..posterior import PosteriorParameter
         from tqdm.auto import tqdm
         if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, '__fspath__'):
@@ -147,6 +155,9 @@ class LogitICARGibbs(GibbsBase):
                 checkpoint = {k: f[k] for k in f.files}
         if size < 1:
             raise ValueError('size must be a positive integer')
+        ids = region_ids(regions, self._problem.n)
+        if ids is not None:
+            self._refuse_regions()
         C = int(checkpoint['n_chains'])
         self.__dict__['_stepping'] = False
         eng = self._get_engine([int(k) for k in np.asarray(checkpoint['keys'])])
@@ -156,6 +167,9 @@ class LogitICARGibbs(GibbsBase):
             self._refuse_sums(kind)
             if _lib.SUMS_KINDS[kind].fields[0] not in checkpoint:
                 self._sums_switch(eng, kind, True)
+        if ids is not None:
+            self._regions_call(lambda: (eng.regions(ids), eng.region_stats(True)))
+            occupied = np.zeros((C, size, max(int(ids.max()) + 1, 1)))
         alpha = np.zeros((C, size, self._problem.q))
         beta = np.zeros((C, size, self._problem.p))
         tau = np.zeros((C, size))
@@ -165,19 +179,25 @@ class LogitICARGibbs(GibbsBase):
         while done < size:
             step = min(chunk, size - done)
             alpha[:, done:done + step], beta[:, done:done + step], tau[:, done:done + step] = eng.run(step, 0)
+            if ids is not None:
+                occupied[:, done:done + step] = [eng.region_draws(c) for c in range(C)]
             done += step
             bar.update(step)
         bar.close()
-        chains = [Chain._from_arrays({'alpha': alpha[c], 'beta': beta[c], 'tau': tau[c]}) for c in range(C)]
+        extra = {'occupied': occupied} if ids is not None else {}
+        chains = [Chain._from_arrays({'alpha': alpha[c], 'beta': beta[c], 'tau': tau[c], **{k: v[c] for k, v in extra.items()}},
+                                     vectors=tuple(extra)) for c in range(C)]
         self.chain = chains[0]
         self._pull_state(eng, 0)
         out = PosteriorParameter(*chains)
         for kind in kinds:
             setattr(out, _lib.SUMS_KINDS[kind].result, SUMS_RESULT[kind].from_engine(eng))
+        if ids is not None:
+            out.regions = self._region_result(ids, out)
         return out
 
     # ------------------------------------------------------------------ batched chains
-    def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False, waic=False):
+    def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False, waic=False, regions=None):
         """All chains of one ``sample`` call as one device batch.
 
         Mirrors ``GibbsBase._run`` (base.py:214-241) per chain: start values from the chain's own
@@ -186,6 +206,8 @@ class LogitICARGibbs(GibbsBase):
         zeroes them) right before the first chunk that keeps a draw, and inside that chunk the engine itself counts
         only the iterations past the chunk's burn-in.  With the default no call about them reaches the engine.
         ``waic``: the log-likelihood sums, switched in exactly the same way.
+        ``regions`` (an array of region ids, or None): the count of occupied sites per region, switched in the same way; every
+        chunk's rows are appended to the chains' ``occupied``.  With the default no call about it reaches the engine.
         """
         from tqdm.auto import tqdm
 
@@ -204,10 +226,15 @@ class LogitICARGibbs(GibbsBase):
         for kind in _lib.SUMS_KINDS:
             if kind in kinds or getattr(eng, '_sums_on', {}).get(kind):   # (a reused engine that an earlier call left switched on)
                 self._sums_switch(eng, kind, False)   # (also the early answer of a library that does not know the kind)
+        if regions is not None:   # (sets the map with every chain's switch off)
+            self._regions_call(lambda: eng.regions(regions))
+        elif getattr(eng, '_region_on', False):   # (a reused engine that an earlier call left counting)
+            eng.region_stats(False)
         sums_on = False
 
         C = len(samplers)
         keep = size - burnin
+        extra = {'occupied': np.zeros((C, keep, max(int(regions.max()) + 1, 1)))} if regions is not None else {}
         alpha = np.zeros((C, keep, self._problem.q))
         beta = np.zeros((C, keep, self._problem.p))
         tau = np.zeros((C, keep))
@@ -223,10 +250,14 @@ class LogitICARGibbs(GibbsBase):
                 if not sums_on:
                     for kind in kinds:
                         self._sums_switch(eng, kind, True)
+                    if regions is not None:
+                        eng.region_stats(True)
                     sums_on = True
                 a_, b_, t_ = eng.run(step, b)
                 m = step - b
                 alpha[:, kept:kept + m], beta[:, kept:kept + m], tau[:, kept:kept + m] = a_, b_, t_
+                if regions is not None:
+                    extra['occupied'][:, kept:kept + m] = [eng.region_draws(c) for c in range(C)]
                 kept += m
             done += step
             for bar in bars:
@@ -236,7 +267,8 @@ class LogitICARGibbs(GibbsBase):
 
         chains = []
         for c, s in enumerate(samplers):
-            ch = Chain._from_arrays({'alpha': alpha[c], 'beta': beta[c], 'tau': tau[c]})
+            ch = Chain._from_arrays({'alpha': alpha[c], 'beta': beta[c], 'tau': tau[c], **{k: v[c] for k, v in extra.items()}},
+                                    vectors=tuple(extra))
             s.chain = ch
             chains.append(ch)
         self._pull_state(eng, 0)

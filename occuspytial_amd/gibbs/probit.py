@@ -107,4 +107,5 @@ class ProbitRSRGibbs(GibbsBase):
     checkpoint = LogitICARGibbs.checkpoint
     resume = LogitICARGibbs.resume
     _run_chains = LogitICARGibbs._run_chains
+    _regions_call = LogitICARGibbs._regions_call   # (the occupied sites per region ARE counted here: its z is drawn as the reference draws it)
 

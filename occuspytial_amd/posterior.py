@@ -35,11 +35,13 @@ class PosteriorParameter:
     """Posterior samples of ``alpha``, ``beta``, ``tau`` from one or more chains.
 
     ``PosteriorParameter(*chains)`` takes :class:`~occuspytial_amd.chain.Chain` objects;
-    ``post['alpha']`` is an ndarray ``(chains, draws, q)``, ``post['tau']`` is ``(chains, draws)``.
+    ``post['alpha']`` is an ndarray ``(chains, draws, q)``, ``post['tau']`` is ``(chains, draws)``; chains sampled with
+    ``regions=`` also hold ``post['occupied']``, ``(chains, draws, G)``: the occupied sites per region.
     """
 
     sites = None   # a SiteSummary when sample(..., site_summaries=True) asked for the per-site posterior map
     waic = None    # a WAIC when sample(..., waic=True) asked for the streaming log-likelihood sums
+    regions = None  # a RegionOccupancy when sample(..., regions=...) asked for the occupied sites per region and draw
 
     def __init__(self, *chains):
         self.data = self._create_inference_data(chains)
