@@ -2,7 +2,11 @@
 // plain C++17: a function of the problem's shape, the device's CU count, the plan knobs and whether the CU-masked stream pair
 // was granted.  plan_wanted: before the streams are asked for; plan_granted: the rest, with the LADDER of forms the residency
 // probes walk (k_tiles -> one XCD per chain -> any placement -> one launch per MINRES step); plan_settle: the form chosen.
+// Below the plan: the ORDER of a launch sequence and the scheduling MODE (seq_launches, seq_mode, seq_parts), which the
+// engine walks.  tests/test_plan_cpu.py and tests/test_order_cpu.py pin both on the CPU.
 #pragma once
+#include "../../include/occ_gibbs.h"  // (OCC_N_KERNEL_KINDS)
+
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -273,5 +277,94 @@ inline void plan_settle(Plan &P, int form)
     if (form == FORM_STEPS && P.persistent) P.main_cus = P.share_on = 0;
     P.flag_sync = P.main_cus > 0 && !P.opt.event_sync;
 }
+
+// ---- the ORDER of a launch sequence and the engine's scheduling MODE ---------------------------------------------------
+// A launch sequence is one Gibbs iteration of every chain (or a carried solve).  It has three PARTS, and every scheduling
+// mode is a way of laying them on the two streams (tests/test_order_cpu.py pins all of it):
+//   SIDE   k_omega_a (with alpha's draw), k_noise of the NEXT iteration: inputs are last iteration's alpha and z
+//   SOLVE  the eta conditional: k_iter, or k_eta_init / k_minres ... / k_beta_partial, or the reduced-rank three
+//   TAIL   k_z_ob (beta, z, omega_b): after both
+// The kernel kinds: occ_profile's indices first (include/occ_gibbs.h), then the ones it does not report.
+enum Kind { K_OMEGA_B = 0, K_NOISE, K_ETA_INIT, K_MINRES, K_BETA_PARTIAL, K_OMEGA_A, K_ALPHA_DRAW, K_Z_OB, K_ITER, K_GATE /* internal: not a profiled kind */,
+            K_RSR_GRAM, K_RSR_SOLVE, K_RSR_ETA_BETA /* reduced-rank model */ };
+static_assert(K_ITER + 1 == OCC_N_KERNEL_KINDS, "kernel kinds out of sync with the header");
+
+// launch sequences (iterations) per captured graph on the paths that need no host decision between iterations:
+// even, so that the sequence parity is the same at every replay; a graph boundary costs several microseconds
+constexpr int GRAPH_SEQ = 2;  // (16 per graph measured the same: the boundary between two replays is not what costs)
+
+enum SeqMode : int {
+    SEQ_COUNTERS = 0,        // hand-overs by device counters: two graphs of GRAPH_SEQ sequences, main and side
+    SEQ_RSR_ONE_STREAM = 1,  // reduced-rank model without them: one graph of GRAPH_SEQ sequences
+    SEQ_EVENT_NODES = 2,     // per-parity graphs that carry their own event waits and records
+    SEQ_STREAM_EVENTS = 3,   // per-parity graphs, fork / join by stream calls, k_z_ob behind them (diagnostic)
+    SEQ_ONE_STREAM = 4       // the same graphs one behind the other on the main stream (diagnostic)
+};
+constexpr SeqMode seq_mode(bool flag_sync, bool rsr, bool event_nodes, bool side_enabled)
+{
+    return flag_sync ? SEQ_COUNTERS : rsr ? SEQ_RSR_ONE_STREAM : event_nodes ? SEQ_EVENT_NODES : side_enabled ? SEQ_STREAM_EVENTS : SEQ_ONE_STREAM;
+}
+constexpr int sequences_per_enqueue(SeqMode m) { return m <= SEQ_RSR_ONE_STREAM ? GRAPH_SEQ : 1; }
+constexpr int seq_parity(int p, int t) { return p ^ (t & 1); }  // of sequence t of a graph captured at parity p
+
+// The shape of the solve.  CAPTURED / EAGER: one launch per MINRES step, a fixed number of them in a graph / the host
+// watching the chains' `done` flags between launches.
+enum SeqSolve : int { SOLVE_RSR = 0, SOLVE_FUSED, SOLVE_CAPTURED, SOLVE_EAGER };
+// The counters' graphs hold GRAPH_SEQ whole sequences: a solve the host has to size or watch cannot stand in them.
+constexpr bool seq_mode_runs(SeqMode m, SeqSolve sv) { return m == SEQ_COUNTERS ? sv <= SOLVE_FUSED : m != SEQ_RSR_ONE_STREAM || sv == SOLVE_RSR; }
+// The side stream's gate (it waits for the previous k_z_ob's counter): none without counters; else the head of k_omega_a,
+// or a kernel of its own (OCC_GATE_KERNEL, diagnostic: as until round 3)
+enum SeqGate : int { GATE_NONE = 0, GATE_IN_OMEGA_A, GATE_KERNEL };
+constexpr SeqGate seq_gate(SeqMode m, bool as_kernel) { return m != SEQ_COUNTERS ? GATE_NONE : as_kernel ? GATE_KERNEL : GATE_IN_OMEGA_A; }
+
+enum SeqPart : int { PART_SIDE = 0, PART_SOLVE, PART_TAIL, PART_WAIT /* event wait node */, PART_RECORD /* event record node */ };
+struct SeqLaunch { int kind, e, extra; };
+// SOLVE_EAGER: the host-watched stretch of k_minres launches stands where this `extra` of a K_MINRES is; the last launch's
+// number is K_BETA_PARTIAL's extra
+constexpr int EXTRA_HOST_WATCHED = -1, EXTRA_K_LAST = -2;
+
+// The launches of one part with sequence parity e, in order, handed to emit(SeqLaunch).  cap: the captured Krylov cap
+// (iteration j of a solve is tested by launch j + 3: cap + 3 launches).
+template <class Emit>
+void seq_launches(SeqPart part, SeqSolve sv, int e, int cap, SeqGate gate, Emit &&emit)
+{
+    switch (part) {
+        case PART_SIDE:
+            if (gate == GATE_KERNEL) emit(SeqLaunch{K_GATE, 0, 0});
+            emit(SeqLaunch{K_OMEGA_A, e, gate == GATE_IN_OMEGA_A ? 1 : 0});
+            emit(SeqLaunch{K_NOISE, e, 1});  // ahead = 1: the coming iteration's
+            break;
+        case PART_SOLVE:
+            if (sv == SOLVE_RSR)  // the theta conditional stands where the ICAR solve is
+                for (int k : {K_RSR_GRAM, K_RSR_SOLVE, K_RSR_ETA_BETA}) emit(SeqLaunch{k, e, 0});
+            if (sv == SOLVE_FUSED) emit(SeqLaunch{K_ITER, e, 0});
+            if (sv <= SOLVE_FUSED) break;
+            emit(SeqLaunch{K_ETA_INIT, e, 0});  // one launch per MINRES step
+            if (sv == SOLVE_EAGER) emit(SeqLaunch{K_MINRES, e, EXTRA_HOST_WATCHED});
+            else for (int k = 1; k <= cap + 3; ++k) emit(SeqLaunch{K_MINRES, e, k});
+            emit(SeqLaunch{K_BETA_PARTIAL, e, sv == SOLVE_EAGER ? EXTRA_K_LAST : cap + 3});
+            break;
+        case PART_TAIL: emit(SeqLaunch{K_Z_OB, e, 0}); break;
+        default: break;  // (the event nodes are the engine's: no launch)
+    }
+}
+
+// What a mode lays where, per sequence: the main-stream graph, the side graph, and what is enqueued eagerly behind the
+// graphs.  The graphs of the first two modes hold GRAPH_SEQ sequences of alternating parity, the others one per parity.
+enum SeqWhere : int { ON_MAIN = 0, ON_SIDE, BEHIND };
+struct SeqParts { int n; SeqPart part[4]; };
+constexpr SeqParts seq_parts(SeqMode m, SeqWhere w)
+{
+    switch (m) {
+        case SEQ_COUNTERS: return w == ON_MAIN ? SeqParts{2, {PART_SOLVE, PART_TAIL}} : w == ON_SIDE ? SeqParts{1, {PART_SIDE}} : SeqParts{0, {}};
+        case SEQ_RSR_ONE_STREAM: return w == ON_MAIN ? SeqParts{3, {PART_SIDE, PART_SOLVE, PART_TAIL}} : SeqParts{0, {}};
+        case SEQ_EVENT_NODES:  // main: ... -> wait(side chain of this iteration) -> k_z_ob -> record; side: wait(previous k_z_ob) -> ... -> record
+            return w == ON_MAIN ? SeqParts{4, {PART_SOLVE, PART_WAIT, PART_TAIL, PART_RECORD}} : w == ON_SIDE ? SeqParts{3, {PART_WAIT, PART_SIDE, PART_RECORD}} : SeqParts{0, {}};
+        default: return w == ON_MAIN ? SeqParts{1, {PART_SOLVE}} : w == ON_SIDE ? SeqParts{1, {PART_SIDE}} : SeqParts{1, {PART_TAIL}};
+    }
+}
+// An eager sequence in every mode: everything on the main stream, the reference's order of conditionals (logit.py:254-266)
+// with omega_a / alpha moved up front -- stream order is the synchronisation
+constexpr SeqParts seq_eager() { return SeqParts{3, {PART_SIDE, PART_SOLVE, PART_TAIL}}; }
 
 }  // namespace occ

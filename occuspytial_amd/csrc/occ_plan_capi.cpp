@@ -1,5 +1,5 @@
-// occ_plan_capi.cpp -- the planner (occ_plan.hpp) behind a C entry point for tests/test_plan_cpu.py (ctypes).  Test
-// infrastructure: `make plan` builds it with g++ into build/; it is never linked into libocc_gibbs.so.
+// occ_plan_capi.cpp -- the planner and the launch order (occ_plan.hpp) behind C entry points for tests/test_plan_cpu.py
+// and tests/test_order_cpu.py (ctypes).  Test infrastructure: `make plan` builds it with g++ into build/; it is never linked into libocc_gibbs.so.
 #include <cstdio>
 
 #include "occ_plan.hpp"
@@ -45,6 +45,33 @@ int occ_plan_eval(const int32_t shape[8], int32_t ncu, const PlanOptions *opt, i
     out->n_ladder = (int32_t)P.ladder.size();
     for (size_t i = 0; i < P.ladder.size() && i < 4; ++i) { out->ladder_form[i] = P.ladder[i].form; out->ladder_nbg[i] = P.ladder[i].nbg; }
     return 0;
+}
+
+// The scheduling mode of the four flags; -1 where that mode cannot run a solve of shape `solve`.
+int32_t occ_order_mode(int32_t flag_sync, int32_t rsr, int32_t event_nodes, int32_t side_enabled, int32_t solve)
+{
+    const SeqMode m = seq_mode(flag_sync != 0, rsr != 0, event_nodes != 0, side_enabled != 0);
+    return seq_mode_runs(m, (SeqSolve)solve) ? (int32_t)m : -1;
+}
+int32_t occ_order_sequences_per_enqueue(int32_t mode) { return sequences_per_enqueue((SeqMode)mode); }
+
+// What one enqueue of a mode puts `where` (a SeqWhere; 3: an eager sequence instead) from sequence parity p, as
+// {kind, e, extra} triples; an event wait / record node is {-1 / -2, e, 0}.  The number of triples, -1 beyond `max`.
+int32_t occ_order_launches(int32_t mode, int32_t where, int32_t solve, int32_t p, int32_t cap, int32_t gate_kernel, int32_t *out, int32_t max)
+{
+    const SeqMode m = (SeqMode)mode;
+    const SeqParts parts = where == 3 ? seq_eager() : seq_parts(m, (SeqWhere)where);
+    int32_t n = 0;
+    for (int t = 0; t < (where == 3 ? 1 : sequences_per_enqueue(m)); ++t)
+        for (int i = 0; i < parts.n; ++i) {
+            auto emit = [&](const SeqLaunch &l) {
+                if (n < max) { out[3 * n] = l.kind; out[3 * n + 1] = l.e; out[3 * n + 2] = l.extra; }
+                ++n;
+            };
+            if (parts.part[i] == PART_WAIT || parts.part[i] == PART_RECORD) emit(SeqLaunch{parts.part[i] == PART_WAIT ? -1 : -2, seq_parity(p, t), 0});
+            else seq_launches(parts.part[i], (SeqSolve)solve, seq_parity(p, t), cap, where == 3 ? GATE_NONE : seq_gate(m, gate_kernel != 0), emit);
+        }
+    return n <= max ? n : -1;
 }
 
 }  // extern "C"
