@@ -23,6 +23,7 @@
 #include "occ_tiles.hpp"
 #include "occ_rsr.hpp"
 #include "occ_probit.hpp"
+#include "occ_layout.hpp"
 
 using namespace occ;
 
@@ -1434,26 +1435,14 @@ int pb_create(occ_sampler *s, const occ_problem *pb, int32_t C, const uint64_t *
     for (double v : lam)
         if (!(v >= 0.0) || !std::isfinite(v)) return set_error(s, OCC_E_BADARG, "pb_lam must be finite and non-negative");
     // index sets (base.py:112-152): surveyed index of every site and row, sites with a detection
-    std::vector<int> sidx((size_t)n, -1), row_t((size_t)R, 0);
-    std::vector<uint8_t> yrow((size_t)R, 0);
-    s->obs_site.assign((size_t)S, 0);
-    if (s->site_ptr[0] != 0 || s->site_ptr[S] != R) return set_error(s, OCC_E_BADARG, "site_ptr must run from 0 to n_rows");
-    for (int t = 0; t < S; ++t) {
-        const int site = s->site_id[t];
-        if (site < 0 || site >= n || sidx[site] != -1) return set_error(s, OCC_E_BADARG, "site_id entries must be unique and in [0, n)");
-        if (s->site_ptr[t + 1] < s->site_ptr[t]) return set_error(s, OCC_E_BADARG, "site_ptr must not decrease");
-        sidx[site] = t;
-        for (int r = s->site_ptr[t]; r < s->site_ptr[t + 1]; ++r) {
-            row_t[r] = t;
-            yrow[r] = y[r] != 0.0;
-            s->obs_site[t] |= yrow[r];
-        }
-    }
-    std::vector<double> Xt((size_t)p * n), Wt((size_t)q * R);
-    for (int i = 0; i < n; ++i)
-        for (int a = 0; a < p; ++a) Xt[(size_t)a * n + i] = X[(size_t)i * p + a];
-    for (int r = 0; r < R; ++r)
-        for (int a = 0; a < q; ++a) Wt[(size_t)a * R + r] = W[(size_t)r * q + a];
+    std::vector<int> sidx, row_t;
+    std::vector<uint8_t> yrow;
+    std::string why;
+    if (!layout_site_span(S, R, s->site_ptr, &why) || !layout_sites(n, S, R, s->site_id, s->site_ptr, y, sidx, row_t, yrow, s->obs_site, &why))
+        return set_error(s, OCC_E_BADARG, why.c_str());
+    std::vector<double> Xt, Wt;
+    layout_transpose(n, p, X, Xt);
+    layout_transpose(R, q, W, Wt);
     // beta's precision X'X + b_prec, factored once (upper, M = U'U); the reference overwrote it with its factor
     std::vector<double> U((size_t)p * p, 0.0), b_pbm((size_t)p, 0.0), a_pbm((size_t)q, 0.0);
     for (int a = 0; a < p; ++a)
@@ -1474,10 +1463,8 @@ int pb_create(occ_sampler *s, const occ_problem *pb, int32_t C, const uint64_t *
             U[(size_t)j * p + i] = v / ujj;
         }
     }
-    for (int a = 0; a < p; ++a)
-        for (int b = 0; b < p; ++b) b_pbm[a] += b_prec[(size_t)a * p + b] * b_mu[b];
-    for (int a = 0; a < q; ++a)
-        for (int b = 0; b < q; ++b) a_pbm[a] += a_prec[(size_t)a * q + b] * a_mu[b];
+    layout_prec_mu(p, b_prec, b_mu, b_pbm.data());
+    layout_prec_mu(q, a_prec, a_mu, a_pbm.data());
     PbArgs &A = s->pb;
     A.n = n; A.m = m; A.p = p; A.q = q; A.R = R; A.S = S; A.C = C;
     A.ldm = 16 * ((m + 15) / 16);  // rows on whole 128-byte lines
@@ -1823,21 +1810,7 @@ static int init_occupancy(occ_sampler *s)
     return OCC_OK;
 }
 
-// Everything the host derives from the caller's problem, once: checked inputs in the layouts the kernels read (SELL-64 /
-// diagonal form of Q, structure-of-arrays designs, index sets of base.py:112-152, prior products).  A group of
-// samplers -- one per device, or one per process -- is built from ONE layout: the root uploads it, the others receive
-// the device arrays by RCCL broadcast (occ_create_group, occ_create_distributed).
-struct HostLayout {
-    int n = 0, S = 0, R = 0, p = 0, q = 0, ell_w = 0, rsr_dim = 0;
-    double tau_rate = 0.0, tau_shape = 0.0;
-    std::vector<int> sell_ptr, sell_col, dia_off, row_site, site_sidx;
-    std::vector<double> sell_val, qdiag, dia_val, Xt, Wt, hyp, Kh, Qh, Eh;
-    std::vector<double> prior_F;  // reference-form prior draw: n x prior_m, row-major (empty: edge form)
-    int prior_m = 0;
-    std::vector<uint8_t> dia_mask, yrow, obs_site;
-    std::vector<int32_t> site_id, site_ptr;
-};
-
+// The caller's problem, fetched and laid out (occ_layout.hpp), once
 static int build_layout(occ_sampler *s, const occ_problem *pb, HostLayout &L)
 {
     if (!pb) return set_error(s, OCC_E_BADARG, "null problem");
@@ -1852,16 +1825,14 @@ static int build_layout(occ_sampler *s, const occ_problem *pb, HostLayout &L)
     const int n = (int)pb->n, S = (int)pb->n_surveyed, R = (int)pb->n_rows, p = pb->p, q = pb->q;
     L.n = n; L.S = S; L.R = R; L.p = p; L.q = q; L.rsr_dim = pb->rsr_dim;
     L.tau_rate = pb->tau_rate; L.tau_shape = pb->tau_shape;
-    auto &sell_ptr = L.sell_ptr; auto &sell_col = L.sell_col; auto &sell_val = L.sell_val; auto &qdiag = L.qdiag;
-    auto &dia_off = L.dia_off; auto &dia_val = L.dia_val; auto &dia_mask = L.dia_mask;
-    auto &Xt = L.Xt; auto &Wt = L.Wt; auto &yrow = L.yrow; auto &row_site = L.row_site; auto &site_sidx = L.site_sidx; auto &hyp = L.hyp;
 
     // ---- fetch and check the inputs on the host -------------------------------------------------
     std::vector<int32_t> indptr, indices;
     std::vector<double> qdata, X, W, y, a_mu, a_prec, b_mu, b_prec;
     int rc;
     if ((rc = fetch(s, indptr, pb->q_indptr, (size_t)n + 1))) return rc;
-    if (indptr[0] != 0 || indptr[n] < n) return set_error(s, OCC_E_BADARG, "malformed Q indptr");
+    std::string why;
+    if (!layout_q_indptr(n, indptr, &why)) return set_error(s, OCC_E_BADARG, why.c_str());
     const size_t nnz = (size_t)indptr[n];
     if ((rc = fetch(s, indices, pb->q_indices, nnz))) return rc;
     if ((rc = fetch(s, qdata, pb->q_data, nnz))) return rc;
@@ -1874,141 +1845,14 @@ static int build_layout(occ_sampler *s, const occ_problem *pb, HostLayout &L)
     if ((rc = fetch(s, a_prec, pb->a_prec, (size_t)q * q))) return rc;
     if ((rc = fetch(s, b_mu, pb->b_mu, (size_t)p))) return rc;
     if ((rc = fetch(s, b_prec, pb->b_prec, (size_t)p * p))) return rc;
-    if (S > 0 && (L.site_ptr[0] != 0 || L.site_ptr[S] != R)) return set_error(s, OCC_E_BADARG, "site_ptr does not span the rows");
-
-    // ---- Q: CSR -> diagonal + SELL-64 off-diagonals (coalesced per-wave slices) -------------------
-    // Also checks what the edge form of the prior term needs: zero row sums, non-positive
-    // off-diagonals (Q = D - W), the singular ICAR precision of gibbs/base.py:166-170.
-    const int nslice = (n + 63) / 64;
-    sell_ptr.assign((size_t)nslice + 1, 0);
-    qdiag.assign((size_t)n, 0.0);
-    double scale = 0.0;
-    for (int i = 0; i < n; ++i) {
-        double rowsum = 0.0, rowabs = 0.0;
-        int last = -1;
-        for (int k = indptr[i]; k < indptr[i + 1]; ++k) {
-            const int j = indices[k];
-            if (j < 0 || j >= n || j <= last) return set_error(s, OCC_E_BADARG, "Q columns must be sorted, unique and in range");
-            last = j;
-            rowsum += qdata[k];
-            rowabs += std::fabs(qdata[k]);
-            if (j == i) qdiag[i] = qdata[k];
-            else if (qdata[k] > 0.0 && !pb->prior_factor)
-                return set_error(s, OCC_E_BADARG, "Q must have non-positive off-diagonal entries (or come with a prior factor: occ_problem::prior_factor)");
-        }
-        scale = std::max(scale, rowabs);
-        // (with a prior factor the caller has established the singularity: F F' = Q of rank < n)
-        if (!pb->prior_factor && std::fabs(rowsum) > 1e-10 * std::max(rowabs, 1e-300))
-            return set_error(s, OCC_E_BADARG, "Spatial precision matrix Q must be singular.");
-    }
-    if (!(scale > 0.0)) return set_error(s, OCC_E_BADARG, "Spatial precision matrix Q must be singular.");
-    for (int sl = 0; sl < nslice; ++sl) {
-        int width = 0;
-        for (int i = sl * 64; i < std::min(n, sl * 64 + 64); ++i) {
-            int cnt = 0;
-            for (int k = indptr[i]; k < indptr[i + 1]; ++k) cnt += (indices[k] != i);
-            width = std::max(width, cnt);
-        }
-        sell_ptr[sl + 1] = sell_ptr[sl] + width * 64;
-    }
-    // uniform width (ELL) when the padding it adds is small: the slice base becomes arithmetic
-    {
-        int wmax = 0;
-        for (int sl = 0; sl < nslice; ++sl) wmax = std::max(wmax, (sell_ptr[sl + 1] - sell_ptr[sl]) / 64);
-        const long long ell_slots = (long long)wmax * 64 * nslice;
-        L.ell_w = (wmax > 0 && ell_slots <= (long long)(1.25 * sell_ptr[nslice]) + 64) ? wmax : 0;
-        if (L.ell_w)
-            for (int sl = 0; sl <= nslice; ++sl) sell_ptr[sl] = sl * wmax * 64;
-    }
-    // 64 spare slots: k_iter reads slot `base + lane` of a slice even when the slice has no off-diagonals
-    sell_col.assign((size_t)sell_ptr[nslice] + 64, 0);
-    sell_val.assign((size_t)sell_ptr[nslice] + 64, 0.0);
-    for (int sl = 0; sl < nslice; ++sl) {
-        const int base = sell_ptr[sl], width = (sell_ptr[sl + 1] - base) / 64;
-        for (int lane = 0; lane < 64; ++lane) {
-            const int i = sl * 64 + lane;
-            int kk = 0;
-            if (i < n)
-                for (int k = indptr[i]; k < indptr[i + 1]; ++k)
-                    if (indices[k] != i) {
-                        sell_col[(size_t)base + kk * 64 + lane] = indices[k];
-                        sell_val[(size_t)base + kk * 64 + lane] = qdata[k];
-                        ++kk;
-                    }
-            for (; kk < width; ++kk) sell_col[(size_t)base + kk * 64 + lane] = std::min(i, n - 1);  // padding: value 0
-        }
-    }
-
-    // ---- diagonal form, when the off-diagonals lie on at most NPRE diagonals with one value each (lattices) -----
-    {
-        std::vector<long long> offs;
-        bool ok = true;
-        for (int i = 0; i < n && ok; ++i)
-            for (int k = indptr[i]; k < indptr[i + 1] && ok; ++k) {
-                if (indices[k] == i) continue;
-                const long long d = (long long)indices[k] - i;
-                size_t t = 0;
-                while (t < offs.size() && offs[t] != d) ++t;
-                if (t == offs.size()) {
-                    if (offs.size() == (size_t)NPRE) { ok = false; break; }
-                    offs.push_back(d);
-                    dia_val.push_back(qdata[k]);
-                } else if (dia_val[t] != qdata[k]) ok = false;
-            }
-        if (ok && !offs.empty()) {
-            std::vector<size_t> order(offs.size());
-            for (size_t t = 0; t < order.size(); ++t) order[t] = t;
-            std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return offs[a] < offs[b]; });  // CSR column order
-            std::vector<double> v2;
-            for (size_t t : order) { dia_off.push_back((int)offs[t]); v2.push_back(dia_val[t]); }
-            dia_val = v2;
-            dia_mask.assign((size_t)n, 0);
-            for (int i = 0; i < n; ++i)
-                for (int k = indptr[i]; k < indptr[i + 1]; ++k) {
-                    if (indices[k] == i) continue;
-                    const int d = indices[k] - i;
-                    for (size_t t = 0; t < dia_off.size(); ++t)
-                        if (dia_off[t] == d) dia_mask[i] |= (uint8_t)(1u << t);
-                }
-        } else {
-            dia_val.clear();
-        }
-    }
-
-    // ---- design matrices as structure-of-arrays; ragged visits; index sets (base.py:112-152) -----
-    Xt.assign((size_t)n * p, 0.0);
-    Wt.assign((size_t)R * q, 0.0);
-    for (int i = 0; i < n; ++i)
-        for (int a = 0; a < p; ++a) Xt[(size_t)a * n + i] = X[(size_t)i * p + a];
-    for (int r = 0; r < R; ++r)
-        for (int a = 0; a < q; ++a) Wt[(size_t)a * R + r] = W[(size_t)r * q + a];
-    yrow.assign((size_t)R, 0);
-    row_site.assign((size_t)R, 0);
-    site_sidx.assign((size_t)n, -1);
-    L.obs_site.assign((size_t)S, 0);
-    for (int t = 0; t < S; ++t) {
-        const int site = L.site_id[t];
-        if (site < 0 || site >= n || site_sidx[site] != -1) return set_error(s, OCC_E_BADARG, "site_id entries must be unique and in [0, n)");
-        if (L.site_ptr[t + 1] < L.site_ptr[t]) return set_error(s, OCC_E_BADARG, "site_ptr must be non-decreasing");
-        site_sidx[site] = t;
-        uint8_t any = 0;
-        for (int r = L.site_ptr[t]; r < L.site_ptr[t + 1]; ++r) {
-            yrow[r] = (y[r] != 0.0) ? 1 : 0;
-            any |= yrow[r];
-        }
-        L.obs_site[t] = any;
-        for (int r = L.site_ptr[t]; r < L.site_ptr[t + 1]; ++r) row_site[r] = site | (any ? (int)0x80000000 : 0);
-    }
-    hyp.assign((size_t)q * q + q + (size_t)p * p + p, 0.0);
-    {
-        double *ap = hyp.data(), *apm = ap + q * q, *bp = apm + q, *bpm = bp + p * p;
-        std::copy(a_prec.begin(), a_prec.end(), ap);
-        std::copy(b_prec.begin(), b_prec.end(), bp);
-        for (int a = 0; a < q; ++a)
-            for (int b = 0; b < q; ++b) apm[a] += a_prec[(size_t)a * q + b] * a_mu[b];  // base.py:161
-        for (int a = 0; a < p; ++a)
-            for (int b = 0; b < p; ++b) bpm[a] += b_prec[(size_t)a * p + b] * b_mu[b];  // base.py:162
-    }
+    std::vector<int> row_t;  // (the probit model's)
+    if (!layout_site_span(S, R, L.site_ptr, &why) || !layout_q(n, indptr, indices, qdata, pb->prior_factor != nullptr, L, &why))
+        return set_error(s, OCC_E_BADARG, why.c_str());
+    layout_transpose(n, p, X, L.Xt);
+    layout_transpose(R, q, W, L.Wt);
+    if (!layout_sites(n, S, R, L.site_id, L.site_ptr, y, L.site_sidx, row_t, L.yrow, L.obs_site, &why)) return set_error(s, OCC_E_BADARG, why.c_str());
+    layout_row_site(L);
+    layout_hyp(p, q, a_mu, a_prec, b_mu, b_prec, L.hyp);
 
     if (pb->prior_factor) {  // the reference's form of the prior draw: u = F eps
         if (pb->prior_factor_cols < 1 || pb->prior_factor_cols > n) return set_error(s, OCC_E_BADARG, "prior_factor_cols must lie in [1, n]");
@@ -2047,11 +1891,6 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
     c.maxiter = 10LL * n;  // scipy default 5 * (2n)  (minres.py, called at logit.py:87)
     c.ell_w = L.ell_w;
     s->site_id = L.site_id; s->site_ptr = L.site_ptr; s->obs_site = L.obs_site;
-    const auto &sell_ptr = L.sell_ptr; const auto &sell_col = L.sell_col; const auto &sell_val = L.sell_val; const auto &qdiag = L.qdiag;
-    const auto &dia_off = L.dia_off; const auto &dia_val = L.dia_val; const auto &dia_mask = L.dia_mask;
-    const auto &Xt = L.Xt; const auto &Wt = L.Wt; const auto &yrow = L.yrow; const auto &row_site = L.row_site;
-    const auto &site_sidx = L.site_sidx; const auto &hyp = L.hyp;
-    const int nslice = (n + 63) / 64;
     const uint8_t *dia_mask_dev = nullptr;
     int rc;
 
@@ -2059,8 +1898,8 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, s->device));
     PlanShape shape;
-    shape.n = n; shape.rows = R; shape.chains = C; shape.p = p; shape.q = q; shape.rsr_dim = L.rsr_dim; shape.dia = !dia_off.empty();
-    for (int sl = 0; sl < nslice; ++sl) shape.wmax = std::max(shape.wmax, (sell_ptr[sl + 1] - sell_ptr[sl]) / 64);
+    shape.n = n; shape.rows = R; shape.chains = C; shape.p = p; shape.q = q; shape.rsr_dim = L.rsr_dim; shape.dia = !L.dia_off.empty();
+    shape.wmax = L.wmax();
     Plan &P = s->plan;
     std::string why;
     if (!plan_wanted(shape, prop.multiProcessorCount, plan_options_from_env(), &P, &why)) return set_error(s, OCC_E_BADARG, why.c_str());
@@ -2090,22 +1929,22 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
     std::memcpy(c.tile_most, P.tile_most, sizeof(c.tile_most));
 
     // ---- device memory ------------------------------------------------------------------------------
-    if ((rc = upload(s, &c.sell_ptr, sell_ptr, "sell_ptr"))) return rc;
-    if ((rc = upload(s, &c.sell_col, sell_col, "sell_col"))) return rc;
-    if ((rc = upload(s, &c.sell_val, sell_val, "sell_val"))) return rc;
-    if ((rc = upload(s, &c.qdiag, qdiag, "qdiag"))) return rc;
-    if (!dia_off.empty() && (rc = upload(s, &dia_mask_dev, dia_mask, "dia_mask_dev"))) return rc;
-    if ((rc = upload(s, &c.Xt, Xt, "Xt"))) return rc;
-    if ((rc = upload(s, &c.Wt, Wt, "Wt"))) return rc;
-    if ((rc = upload(s, &c.yrow, yrow, "yrow"))) return rc;
-    if ((rc = upload(s, &c.row_site, row_site, "row_site"))) return rc;
-    if ((rc = upload(s, &c.site_sidx, site_sidx, "site_sidx"))) return rc;
+    if ((rc = upload(s, &c.sell_ptr, L.sell_ptr, "sell_ptr"))) return rc;
+    if ((rc = upload(s, &c.sell_col, L.sell_col, "sell_col"))) return rc;
+    if ((rc = upload(s, &c.sell_val, L.sell_val, "sell_val"))) return rc;
+    if ((rc = upload(s, &c.qdiag, L.qdiag, "qdiag"))) return rc;
+    if (!L.dia_off.empty() && (rc = upload(s, &dia_mask_dev, L.dia_mask, "dia_mask_dev"))) return rc;
+    if ((rc = upload(s, &c.Xt, L.Xt, "Xt"))) return rc;
+    if ((rc = upload(s, &c.Wt, L.Wt, "Wt"))) return rc;
+    if ((rc = upload(s, &c.yrow, L.yrow, "yrow"))) return rc;
+    if ((rc = upload(s, &c.row_site, L.row_site, "row_site"))) return rc;
+    if ((rc = upload(s, &c.site_sidx, L.site_sidx, "site_sidx"))) return rc;
     {
         std::vector<int> sp(s->site_ptr.begin(), s->site_ptr.end());
         if ((rc = upload(s, &c.site_ptr, sp, "site_ptr"))) return rc;
     }
     if ((rc = upload(s, &c.obs_site, s->obs_site, "obs_site"))) return rc;
-    if ((rc = upload(s, &c.hyp, hyp, "hyp"))) return rc;
+    if ((rc = upload(s, &c.hyp, L.hyp, "hyp"))) return rc;
     c.dense_F = nullptr;
     c.dense_m = 0;
     if (L.prior_m > 0) {  // reference-form prior draw
@@ -2190,8 +2029,8 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
         k.dia_n = 0;
         k.dia_mask = nullptr;
         if (P.dia) {
-            k.dia_n = (int)dia_off.size();
-            for (size_t d = 0; d < dia_off.size(); ++d) { k.dia_off[d] = dia_off[d]; k.dia_val[d] = dia_val[d]; }
+            k.dia_n = (int)L.dia_off.size();
+            for (size_t d = 0; d < L.dia_off.size(); ++d) { k.dia_off[d] = L.dia_off[d]; k.dia_val[d] = L.dia_val[d]; }
             k.dia_mask = dia_mask_dev;
         }
         k.sell_ptr = c.sell_ptr; k.sell_col = c.sell_col; k.sell_val = c.sell_val; k.qdiag = c.qdiag;
@@ -2362,37 +2201,6 @@ int comm_allreduce(occ_comm *cm, double *inout, int n, ncclRedOp_t op)
     return OCC_OK;
 }
 
-// What a peer needs to size its arrays before the broadcast
-struct LayoutHeader {
-    int32_t ok, n, S, R, p, q, ell_w, ndia, nsell_ptr, pad_;
-    double tau_rate, tau_shape;
-    int32_t dia_off[8];
-    double dia_val[8];
-};
-
-void size_peer_layout(HostLayout &L, const LayoutHeader &h)
-{
-    L.n = h.n; L.S = h.S; L.R = h.R; L.p = h.p; L.q = h.q; L.ell_w = h.ell_w; L.rsr_dim = 0;
-    L.tau_rate = h.tau_rate; L.tau_shape = h.tau_shape;
-    L.dia_off.assign(h.dia_off, h.dia_off + h.ndia);
-    L.dia_val.assign(h.dia_val, h.dia_val + h.ndia);
-    const size_t slots = (size_t)L.sell_ptr.back() + 64;
-    L.sell_col.assign(slots, 0);
-    L.sell_val.assign(slots, 0.0);
-    L.qdiag.assign((size_t)h.n, 0.0);
-    if (h.ndia > 0) L.dia_mask.assign((size_t)h.n, 0);
-    L.Xt.assign((size_t)h.n * h.p, 0.0);
-    L.Wt.assign((size_t)h.R * h.q, 0.0);
-    L.yrow.assign((size_t)h.R, 0);
-    L.row_site.assign((size_t)h.R, 0);
-    L.site_sidx.assign((size_t)h.n, -1);
-    L.hyp.assign((size_t)h.q * h.q + h.q + (size_t)h.p * h.p + h.p, 0.0);
-    L.site_id.assign((size_t)h.S, 0);
-    for (int t = 0; t < h.S; ++t) L.site_id[t] = t;  // placeholders (unique, in range) until the real arrays arrive
-    L.site_ptr.assign((size_t)h.S + 1, 0);
-    L.obs_site.assign((size_t)h.S, 0);
-}
-
 // Checksums of the sampler's fixed arrays as they sit on ITS device (k_checksum), in fixed_list order: what a group
 // compares after the broadcast -- a first multi-GPU run must be able to tell a wrong broadcast from a right one.
 int fixed_checksums(occ_sampler *s, std::vector<unsigned long long> &sums)
@@ -2546,13 +2354,7 @@ int occ_create_distributed(const occ_problem *problem, occ_comm *cm, int32_t roo
         rc = build_layout(s, problem, L);
         if (rc == OCC_OK && (L.rsr_dim > 0 || L.prior_m > 0))
             rc = set_error(s, OCC_E_BADARG, "occ_create_distributed covers the ICAR model with the edge-form prior draw");
-        h.ok = rc == OCC_OK;
-        if (h.ok) {
-            h.n = L.n; h.S = L.S; h.R = L.R; h.p = L.p; h.q = L.q; h.ell_w = L.ell_w;
-            h.ndia = (int32_t)L.dia_off.size(); h.nsell_ptr = (int32_t)L.sell_ptr.size();
-            h.tau_rate = L.tau_rate; h.tau_shape = L.tau_shape;
-            for (int d = 0; d < h.ndia; ++d) { h.dia_off[d] = L.dia_off[d]; h.dia_val[d] = L.dia_val[d]; }
-        }
+        if (rc == OCC_OK) h = layout_header(L);
     }
     int crc = comm_bcast_host(cm, &h, sizeof(h), root);  // (a root that failed says so: nobody waits for arrays that never come)
     if (crc) return fail(crc);

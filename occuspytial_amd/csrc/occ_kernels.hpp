@@ -1499,8 +1499,6 @@ __device__ __forceinline__ double2 kry_apply(double d, const double (&av)[NW], d
     return make_double2(hx, hy);
 }
 
-constexpr int NPRE = 8;  // neighbour slots fetched before the scalars are known (queen lattice: all)
-
 // One MINRES iteration per launch, pipelined so that every inner product is a DIRECT sum (no
 // algebraic shortcut): with p_m = r2_m (scipy's Lanczos residual after iteration m, p_0 = b - A x0) and
 // g_m = A p_{m-1} (unscaled), scipy's iteration m reads

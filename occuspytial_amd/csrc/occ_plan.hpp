@@ -17,6 +17,7 @@
 namespace occ {
 
 constexpr int MAXC = 8;                 // covariates of the register-resident fast path (templates on P, Q)
+constexpr int NPRE = 8;                 // neighbour slots k_iter fetches before the scalars are known (queen lattice: all)
 constexpr int nacc(int d) { return d * (d + 1) / 2 + d; }
 constexpr int ITER_WG = 256;            // threads per workgroup of k_iter, any placement
 constexpr int ITER_WG_XL = 512;         // ... one XCD per chain: two waves per SIMD IN one workgroup (see k_iter)

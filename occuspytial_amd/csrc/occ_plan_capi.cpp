@@ -1,8 +1,10 @@
-// occ_plan_capi.cpp -- the planner and the launch order (occ_plan.hpp) behind C entry points for tests/test_plan_cpu.py
-// and tests/test_order_cpu.py (ctypes).  Test infrastructure: `make plan` builds it with g++ into build/; it is never linked into libocc_gibbs.so.
+// occ_plan_capi.cpp -- the planner and the launch order (occ_plan.hpp) and the problem layout (occ_layout.hpp) behind C entry
+// points for tests/test_plan_cpu.py, tests/test_order_cpu.py and tests/test_layout_cpu.py (ctypes).  Test infrastructure:
+// `make plan` builds it with g++ into build/; it is never linked into libocc_gibbs.so.
 #include <cstdio>
+#include <cstring>
 
-#include "occ_plan.hpp"
+#include "occ_layout.hpp"
 
 using namespace occ;
 
@@ -72,6 +74,73 @@ int32_t occ_order_launches(int32_t mode, int32_t where, int32_t solve, int32_t p
             else seq_launches(parts.part[i], (SeqSolve)solve, seq_parity(p, t), cap, where == 3 ? GATE_NONE : seq_gate(m, gate_kernel != 0), emit);
         }
     return n <= max ? n : -1;
+}
+
+// The layout of a logit problem, by build_layout's steps in its order (occ_gibbs.hip), plus the probit model's row_t.
+// A handle for occ_layout_array / occ_layout_peer, or null with the refusal in err.
+struct OccLayout {
+    HostLayout L;
+    std::vector<int> row_t;
+};
+OccLayout *occ_layout_build(int32_t n, int32_t S, int32_t R, int32_t p, int32_t q, const int32_t *indptr, const int32_t *indices, const double *data,
+                            int32_t has_prior_factor, const double *X, const int32_t *site_id, const int32_t *site_ptr, const double *W,
+                            const double *y, const double *a_mu, const double *a_prec, const double *b_mu, const double *b_prec, char *err, int32_t errlen)
+{
+    OccLayout *h = new OccLayout();
+    HostLayout &L = h->L;
+    L.n = n; L.S = S; L.R = R; L.p = p; L.q = q;
+    std::string why;
+    auto build = [&]() {
+        const std::vector<int32_t> ip(indptr, indptr + n + 1);
+        if (!layout_q_indptr(n, ip, &why)) return false;
+        const size_t nnz = (size_t)ip[n];
+        L.site_id.assign(site_id, site_id + S);
+        L.site_ptr.assign(site_ptr, site_ptr + S + 1);
+        if (!layout_site_span(S, R, L.site_ptr, &why)) return false;
+        if (!layout_q(n, ip, std::vector<int32_t>(indices, indices + nnz), std::vector<double>(data, data + nnz), has_prior_factor != 0, L, &why)) return false;
+        layout_transpose(n, p, std::vector<double>(X, X + (size_t)n * p), L.Xt);
+        layout_transpose(R, q, std::vector<double>(W, W + (size_t)R * q), L.Wt);
+        if (!layout_sites(n, S, R, L.site_id, L.site_ptr, std::vector<double>(y, y + R), L.site_sidx, h->row_t, L.yrow, L.obs_site, &why)) return false;
+        layout_row_site(L);
+        layout_hyp(p, q, std::vector<double>(a_mu, a_mu + q), std::vector<double>(a_prec, a_prec + q * q), std::vector<double>(b_mu, b_mu + p),
+                   std::vector<double>(b_prec, b_prec + p * p), L.hyp);
+        return true;
+    };
+    if (build()) return h;
+    std::snprintf(err, (size_t)errlen, "%s", why.c_str());
+    delete h;
+    return nullptr;
+}
+
+// What a peer sizes from the root's header and sell_ptr (occ_create_distributed), before any array arrives
+OccLayout *occ_layout_peer(const OccLayout *root)
+{
+    OccLayout *h = new OccLayout();
+    h->L.sell_ptr = root->L.sell_ptr;
+    size_peer_layout(h->L, layout_header(root->L));
+    return h;
+}
+
+void occ_layout_free(OccLayout *h) { delete h; }
+
+// One array of the layout, by its name in HostLayout, as doubles (ell_w, wmax: one element).  Its length (the first `cap`
+// elements are written), -1 for an unknown name.
+int64_t occ_layout_array(const OccLayout *h, const char *name, double *out, int64_t cap)
+{
+    const HostLayout &L = h->L;
+    auto give = [&](const auto &v) {
+        for (size_t i = 0; i < v.size() && (int64_t)i < cap; ++i) out[i] = (double)v[i];
+        return (int64_t)v.size();
+    };
+#define OCC_LAYOUT_ARRAY(NAME) if (!std::strcmp(name, #NAME)) return give(L.NAME);
+    OCC_LAYOUT_ARRAY(sell_ptr) OCC_LAYOUT_ARRAY(sell_col) OCC_LAYOUT_ARRAY(sell_val) OCC_LAYOUT_ARRAY(qdiag) OCC_LAYOUT_ARRAY(dia_off)
+    OCC_LAYOUT_ARRAY(dia_val) OCC_LAYOUT_ARRAY(dia_mask) OCC_LAYOUT_ARRAY(Xt) OCC_LAYOUT_ARRAY(Wt) OCC_LAYOUT_ARRAY(yrow) OCC_LAYOUT_ARRAY(row_site)
+    OCC_LAYOUT_ARRAY(site_sidx) OCC_LAYOUT_ARRAY(site_id) OCC_LAYOUT_ARRAY(site_ptr) OCC_LAYOUT_ARRAY(obs_site) OCC_LAYOUT_ARRAY(hyp)
+#undef OCC_LAYOUT_ARRAY
+    if (!std::strcmp(name, "row_t")) return give(h->row_t);
+    if (!std::strcmp(name, "ell_w")) return give(std::vector<int>{L.ell_w});
+    if (!std::strcmp(name, "wmax")) return give(std::vector<int>{L.wmax()});
+    return -1;
 }
 
 }  // extern "C"
