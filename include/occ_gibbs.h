@@ -184,7 +184,31 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  * Every one of the three names answers OCC_E_STATE before the handle's first region_id.  Nothing is redrawn; occ_set_start
  * and occ_set_keys touch neither map nor switch; a call that is re-run after a device-side wait gave up counts nothing
  * twice; occ_step, occ_profile and the occ_cond_* entry points never count.  alpha, beta, tau, eta, z and the site_* and
- * ll_* sums are bit-identical with the switch on or off. */
+ * ll_* sums are bit-identical with the switch on or off.
+ *
+ * Posterior predictive check of the detection histories (logit models; ICAR and reduced rank), conditional on z: per KEPT draw
+ * of occ_run -- row t as above -- of a chain whose switch is on, the z update replicates the detections of every surveyed
+ * site i, visit rows r0 <= r < r1, from alpha of the iteration and the NEW z_i:
+ *   d_r = expit(w_r alpha), from the dot product and the exponential the update forms anyway;
+ *   u_r = the uniform of Philox stream 13 (STREAM_PPC) at sub-stream index r, the FLAT visit row, block 0, first 64-bit word:
+ *         what occ_draw(kind 3, key, iteration, 13, R) returns, so a caller can re-draw it;
+ *   y_i = sum_r y_r,   E_i = z_i sum_r d_r (rows in row order),   y*_i = z_i sum_r [u_r < d_r];
+ *   Freeman-Tukey terms a_i = (sqrt y_i - sqrt E_i)^2 and b_i = (sqrt y*_i - sqrt E_i)^2 (both 0 where z_i = 0: such a site
+ *   has had no detection).
+ * A row holds four unsigned 64-bit integers: sum_i fx(a_i) (T_obs), sum_i fx(b_i) (T_rep), sum_i y*_i (replicated detections;
+ * observed counterpart: sum y) and #{i: y*_i > 0} (replicated sites with a detection; observed: the sites with one), with
+ * fx(x) = x 2^32 rounded to nearest.  Fixed point makes every column an integer sum, added with integer atomics: the same
+ * values whatever the path, the placement or the order of addition (a term is at most the site's visits and R < 2^31, so a
+ * column stays below 2^63; a quantum is 2^-32 = 2.3e-10 per site against terms of order 0.1 to 1).
+ *   ppc_stats(1)        the chain's switch, 0 / 1 (another value: OCC_E_BADARG); allocates at first use.
+ *   ppc_draws(keep 4)   read-only: the chain's rows of the last completed occ_run, row-major [t][column], as doubles, columns 0
+ *                       and 1 multiplied by 2^-32 (exact below 2^53 quanta, otherwise rounded to nearest); length 0 if the
+ *                       chain's switch was off during that call (or no call has completed since).
+ * Both names answer OCC_E_STATE before the handle's first switch-on, and a probit handle answers them with OCC_E_STATE,
+ * "posterior predictive checks are not available for the probit model".  Nothing is redrawn; occ_set_start and occ_set_keys
+ * do not touch the switch; a call that is re-run after a device-side wait gave up counts nothing twice; occ_step, occ_profile
+ * and the occ_cond_* entry points never count.  alpha, beta, tau, eta, z, the site_* and ll_* sums and region_draws are
+ * bit-identical with the switch on or off, and the four switches are independent of each other. */
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len);
 int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double *in, int64_t len);
 
@@ -318,6 +342,11 @@ int occ_cond_z(occ_sampler *s, int32_t chain, const double *u, double *z_out);
  * kind 4 is a device self-test, not a variate: n (a multiple of 64) values in param, out[i] = the wave sum of one of four
  * quantities derived from them, NaN where the three forms of the engine's wave sum (plain, four at once, transposed)
  * disagree in a bit (tests/test_gpu_rng.py).
+ * The streams (sub-stream index in brackets): 1 omega_b [site], 2 tau's gamma, 3 and 4 the site and edge normals of eta's
+ * prior term, 5 beta's normals [coefficient], 6 omega_a [visit row], 7 alpha's normals [coefficient], 8 the uniform of the z
+ * update [site], 10 the normals of the reference-form prior draw [column of the factor], 11 and 12 the probit model's eps
+ * [site] and coefficient normals [basis column], 13 (STREAM_PPC) the uniform of a replicated detection of the posterior
+ * predictive check [flat visit row].
  * Errors are reported through occ_last_error(NULL). */
 int occ_draw(int32_t device, int32_t kind, uint64_t key, uint32_t iteration, uint32_t stream, int64_t n, const double *param,
              double *out);

@@ -119,6 +119,8 @@ class Engine:
         # occupied sites per region and draw: the map (None: never set) and the switch; until set, no call about them reaches the library
         self._regions = None
         self._region_on = False
+        # posterior predictive check: the switch; until it is first set, no call about it reaches the library
+        self._ppc_on = False
         _LIVE.add(self)
         return self
 
@@ -213,6 +215,8 @@ class Engine:
         if self._regions is not None:   # the map (one row per chain, as every entry) and the switch; the draws belong to a call
             out['region_id'] = np.tile(self._regions, (self.n_chains, 1))
             out['region_stats'] = np.full(self.n_chains, float(self._region_on))
+        if self._ppc_on:   # the switch; the draws belong to a call
+            out['ppc_stats'] = np.ones(self.n_chains)
         return out
 
     def restore(self, ckpt):
@@ -246,6 +250,24 @@ class Engine:
             self.region_stats(bool(np.all(np.asarray(ckpt['region_stats']) != 0)))
         elif self._region_on:
             self.region_stats(False)
+        if 'ppc_stats' in ckpt and np.all(np.asarray(ckpt['ppc_stats']) != 0):
+            self.ppc_stats(True)
+        elif self._ppc_on:
+            self.ppc_stats(False)
+
+    # ---- posterior predictive check (state names ppc_*, include/occ_gibbs.h) ----
+    def ppc_stats(self, on):
+        """Switch the posterior predictive check of every chain.  While on, every kept draw of ``run`` replicates the
+        detections of every surveyed site from the draw's z and alpha and records four sums (:meth:`ppc_draws`)."""
+        for c in range(self.n_chains):
+            self.set('ppc_stats', 1.0 if on else 0.0, c)
+        self._ppc_on = bool(on)
+
+    def ppc_draws(self, chain=0):
+        """``(keep, 4)`` rows of one chain from the last ``run`` -- the Freeman-Tukey discrepancy of the observed and of the
+        replicated detections, the replicated detections, the replicated sites with a detection -- ``(0, 4)`` if its
+        switch was off during that call."""
+        return self.get('ppc_draws', chain).reshape(-1, 4)
 
     # ---- occupied sites per region and draw (state names region_*, include/occ_gibbs.h) ----
     def regions(self, ids):
@@ -498,6 +520,19 @@ class EngineGroup:
     def region_draws(self, chain=0):
         g, i = self.where[chain]
         return self.engines[g].region_draws(i)
+
+    # posterior predictive check: the switch on every device, the draws routed by chain
+    @property
+    def _ppc_on(self):
+        return any(getattr(e, '_ppc_on', False) for e in self.engines)
+
+    def ppc_stats(self, on):
+        for e in self.engines:
+            e.ppc_stats(on)
+
+    def ppc_draws(self, chain=0):
+        g, i = self.where[chain]
+        return self.engines[g].ppc_draws(i)
 
     # (the entry points by name are Engine's own: each only names its kind)
     site_stats, site_sums, loglik_stats, loglik_sums = Engine.site_stats, Engine.site_sums, Engine.loglik_stats, Engine.loglik_sums

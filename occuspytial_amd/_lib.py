@@ -21,6 +21,9 @@ SITE_FIELDS = ('site_stats', 'site_count', 'site_psi', 'site_occ', 'site_z', 'si
 LOGLIK_FIELDS = ('ll_stats', 'll_count', 'll_lik', 'll_log', 'll_log2')
 # the occupied sites per region and draw: the handle's map (n), the chain's switch, the chain's counts of the last occ_run (keep G)
 REGION_FIELDS = ('region_id', 'region_stats', 'region_draws')
+# the posterior predictive check: the chain's switch, the chain's rows of the last occ_run (keep 4: T_obs, T_rep, replicated
+# detections, replicated sites with a detection)
+PPC_FIELDS = ('ppc_stats', 'ppc_draws')
 KERNEL_KINDS = ('omega_b', 'noise', 'eta_init', 'minres', 'beta_partial', 'omega_a', 'alpha_draw', 'z_ob', 'iter')
 
 

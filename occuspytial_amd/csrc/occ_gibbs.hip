@@ -84,7 +84,7 @@ inline DeviceLease lease_device(int device) { return DeviceLease(device_slot(dev
 // occ_get_state / occ_set_state.  Whatever the host does for a kind -- names, snapshot and restore around a call that may
 // be re-run, the choice of kernel -- is a loop over this table.
 using KernelEI = void (*)(const Ctx *, ChainScalars *, Slot *, int, int, int);
-KernelEI pick_z_ob_stats(int p), pick_z_ob_ll(int p), pick_z_ob_occ(int p);  // (defined with the other choices of an instantiation, below)
+KernelEI pick_z_ob_stats(int p), pick_z_ob_ll(int p), pick_z_ob_occ(int p), pick_z_ob_ppc(int p);  // (defined with the other choices of an instantiation, below)
 enum : int { SUMS_SITE = 0, SUMS_LL = 1, N_SUMS = 2 };
 struct SumsKind {
     uint32_t bit;  // of ChainScalars::site_on
@@ -104,6 +104,10 @@ const SumsKind SUMS[N_SUMS] = {
 // Not a row of SUMS: it keeps no sums, has no count and nothing to snapshot -- its record is zeroed when a call's window opens.
 enum : int { Z_OB_OCC = N_SUMS };
 constexpr uint32_t REGION_BIT = 4u;
+// ... and while a chain keeps the posterior predictive check (bit PPC_BIT; occ_sampler::ppc): k_z_ob_ppc, which ranks above
+// k_z_ob_occ and serves the regions and every kind of sums as well.  Like the regions, a record per call and no sums.
+enum : int { Z_OB_PPC = N_SUMS + 1 };
+constexpr uint32_t PPC_BIT = 8u;
 
 }  // namespace
 
@@ -166,10 +170,24 @@ struct occ_sampler {
         uint32_t *pb_on_dev = nullptr;
         uint32_t **pb_rec = nullptr;
     } regions;
-    // the kind whose z-update kernel runs: Z_OB_OCC while a chain counts regions; else, of the kinds of sums with a chain
-    // switched on, the one of highest rank; -1: k_z_ob itself
+    // Posterior predictive check (state names ppc_stats, ppc_draws; logit models).  ready: a chain has been switched on once.
+    // launch: a chain has its switch on, so k_z_ob_ppc stands where k_z_ob stands.  rec: the four integer sums per chain and
+    // kept draw of the running occ_run on the device, [C][keep][PPC_NCOL], sized like rec_buf and grown between calls, zeroed
+    // on the stream when the call's window opens and copied out (pin) behind its last batch; last: those of the last
+    // completed occ_run on the host, for the chains whose switch was on during it (last_on).
+    struct Ppc {
+        bool ready = false, launch = false;
+        unsigned long long *rec = nullptr, *pin = nullptr;
+        size_t rec_cap = 0, pin_cap = 0, run_need = 0;
+        std::vector<unsigned long long> last;
+        std::vector<uint8_t> last_on;
+        int64_t last_keep = 0;
+    } ppc;
+    // the kind whose z-update kernel runs: Z_OB_PPC while a chain keeps the predictive check; else Z_OB_OCC while a chain
+    // counts regions; else, of the kinds of sums with a chain switched on, the one of highest rank; -1: k_z_ob itself
     int z_ob_kind() const
     {
+        if (ppc.launch) return Z_OB_PPC;
         if (regions.launch) return Z_OB_OCC;
         int top = -1;
         for (int k = 0; k < N_SUMS; ++k)
@@ -502,6 +520,7 @@ KernelEI pick_z_ob(int p) { return OCC_PICK_P(k_z_ob, p); }
 KernelEI pick_z_ob_stats(int p) { return OCC_PICK_P(k_z_ob_stats, p); }
 KernelEI pick_z_ob_ll(int p) { return OCC_PICK_P(k_z_ob_ll, p); }
 KernelEI pick_z_ob_occ(int p) { return OCC_PICK_P(k_z_ob_occ, p); }
+KernelEI pick_z_ob_ppc(int p) { return OCC_PICK_P(k_z_ob_ppc, p); }
 KernelEI pick_omega_a(int q)
 {
     switch (q) {
@@ -544,7 +563,7 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
     const int tp = P.generic ? 0 : c.p, tq = P.generic ? 0 : c.q;  // template arguments: 0 = the generic (run-time) instantiation
     const size_t lds_p = P.generic ? generic_lds_bytes(nacc(c.p), P.tpb) : 0, lds_q = P.generic ? generic_lds_bytes(nacc(c.q), P.tpb) : 0;
     const int zk = s->z_ob_kind();  // (a kind of per-site sums is switched on: its kernel where k_z_ob stands)
-    const KernelEI z_ob = zk < 0 ? pick_z_ob(tp) : zk == Z_OB_OCC ? pick_z_ob_occ(tp) : SUMS[zk].z_ob(tp);
+    const KernelEI z_ob = zk < 0 ? pick_z_ob(tp) : zk == Z_OB_PPC ? pick_z_ob_ppc(tp) : zk == Z_OB_OCC ? pick_z_ob_occ(tp) : SUMS[zk].z_ob(tp);
     switch (kind) {
         case K_OMEGA_B: hipLaunchKernelGGL(pick_omega_b(tp), gs, blk, 0, st, OCC_ARGS); break;
         case K_NOISE:
@@ -1311,6 +1330,57 @@ void regions_close(occ_sampler *s, int64_t keep, const std::vector<uint8_t> &on)
 
 }  // namespace
 
+// ---- posterior predictive check: the record of one occ_run (logit models) ---------------------------------------------
+namespace {
+
+// regions_open / regions_copy_out / regions_close for the four sums per chain and kept draw
+int ppc_open(occ_sampler *s, int C, int64_t keep, bool *moved)
+{
+    occ_sampler::Ppc &pc = s->ppc;
+    *moved = false;
+    pc.last.clear();
+    pc.last_on.assign((size_t)C, 0);
+    pc.last_keep = 0;
+    pc.run_need = pc.launch ? (size_t)C * (size_t)keep * (size_t)PPC_NCOL : 0;
+    if (!pc.run_need) return OCC_OK;
+    if (pc.run_need > pc.rec_cap) {
+        WAIT_TRY(s->stream);
+        if (pc.rec) HIP_TRY(hipFree(pc.rec));
+        pc.rec = nullptr;
+        pc.rec_cap = 0;
+        HIP_TRY(hipMalloc((void **)&pc.rec, sizeof(unsigned long long) * pc.run_need));
+        pc.rec_cap = pc.run_need;
+        *moved = true;
+    }
+    if (pc.run_need > pc.pin_cap) {
+        WAIT_TRY(s->stream);
+        if (pc.pin) HIP_TRY(hipHostFree(pc.pin));
+        pc.pin = nullptr;
+        pc.pin_cap = 0;
+        const size_t cap = std::max<size_t>(pc.run_need, 4096);
+        HIP_TRY(hipHostMalloc((void **)&pc.pin, sizeof(unsigned long long) * cap, hipHostMallocDefault));
+        pc.pin_cap = cap;
+    }
+    HIP_TRY(hipMemsetAsync(pc.rec, 0, sizeof(unsigned long long) * pc.run_need, s->stream));
+    return OCC_OK;
+}
+int ppc_copy_out(occ_sampler *s)
+{
+    const occ_sampler::Ppc &pc = s->ppc;
+    if (pc.run_need) HIP_TRY(hipMemcpyAsync(pc.pin, pc.rec, sizeof(unsigned long long) * pc.run_need, hipMemcpyDeviceToHost, s->stream));
+    return OCC_OK;
+}
+void ppc_close(occ_sampler *s, int64_t keep, const std::vector<uint8_t> &on)
+{
+    occ_sampler::Ppc &pc = s->ppc;
+    if (!pc.run_need) return;
+    pc.last.assign(pc.pin, pc.pin + pc.run_need);
+    pc.last_on = on;
+    pc.last_keep = keep;
+}
+
+}  // namespace
+
 // ---- probit model (ProbitRSRGibbs): creation, one iteration, occ_run, state -------------------------------------------
 namespace {
 
@@ -1788,6 +1858,8 @@ int occ_destroy(occ_sampler *s)
             if (s->rec_buf) (void)hipFree(s->rec_buf);
             if (s->regions.rec) (void)hipFree(s->regions.rec);
             if (s->regions.pin) (void)hipHostFree(s->regions.pin);
+            if (s->ppc.rec) (void)hipFree(s->ppc.rec);
+            if (s->ppc.pin) (void)hipHostFree(s->ppc.pin);
             if (s->pin_sc) (void)hipHostFree(s->pin_sc);
             if (s->pin_rec) (void)hipHostFree(s->pin_rec);
             for (hipEvent_t ev : {s->ev0, s->ev1, s->ev_z[0], s->ev_z[1], s->ev_side[0], s->ev_side[1]})
@@ -2632,6 +2704,8 @@ static int finish_marks(occ_sampler *s, bool last, size_t n_rec)
     if (n_rec) HIP_TRY(hipMemcpyAsync(s->pin_rec, s->rec_buf, sizeof(double) * n_rec, hipMemcpyDeviceToHost, s->stream));
     const int rrc = regions_copy_out(s);
     if (rrc) return rrc;
+    const int prc = ppc_copy_out(s);
+    if (prc) return prc;
     s->marks_done = true;
     return OCC_OK;
 }
@@ -2647,9 +2721,12 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     if (rc) return rc;
     bool occ_moved = false;
     if ((rc = regions_open(s, C, keep, &occ_moved))) return rc;  // (zeroed here, in front of the window: also when the call is re-run)
-    if (c.rec != s->rec_buf || c.occ_rec != s->regions.rec) {
+    bool ppc_moved = false;
+    if ((rc = ppc_open(s, C, keep, &ppc_moved))) return rc;
+    if (c.rec != s->rec_buf || c.occ_rec != s->regions.rec || c.ppc_rec != s->ppc.rec) {
         c.rec = s->rec_buf;
         c.occ_rec = s->regions.rec;
+        c.ppc_rec = s->ppc.rec;
         HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
     }
     if ((rc = open_window(s, n_iter, burnin, keep, snapshot, true))) return rc;
@@ -2788,6 +2865,9 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     std::vector<uint8_t> occ_on((size_t)C, 0);
     for (int ch = 0; ch < C; ++ch) occ_on[(size_t)ch] = (h[ch].site_on & REGION_BIT) ? 1 : 0;
     regions_close(s, keep, occ_on);
+    std::vector<uint8_t> ppc_on((size_t)C, 0);
+    for (int ch = 0; ch < C; ++ch) ppc_on[(size_t)ch] = (h[ch].site_on & PPC_BIT) ? 1 : 0;
+    ppc_close(s, keep, ppc_on);
     return OCC_OK;
 }
 
@@ -3147,6 +3227,61 @@ static int set_region_state(occ_sampler *s, int chain, int field, const double *
     return OCC_OK;
 }
 
+// ---- occ_get_state / occ_set_state of the predictive check's names (logit models) -------------------------------------
+// ppc_stats (1): the chain's switch, 0 or 1; the record of a call is allocated at first use.  ppc_draws (keep 4, read-only):
+// the chain's rows of the last completed occ_run as doubles, columns 0 and 1 times 2^-32 (exact below 2^53 quanta,
+// otherwise rounded to nearest); length 0 if its switch was off during that call.  Before the first switch-on both names
+// answer OCC_E_STATE.  Nothing of a chain's state changes: nothing is redrawn.  Which z kernel is launched follows "is any
+// chain on" (occ_sampler::z_ob_kind): a change drops the captured graphs.
+enum : int { PPC_NONE = -1, PPC_SWITCH = 0, PPC_DRAWS = 1 };
+static int ppc_field(const std::string &nm) { return nm == "ppc_stats" ? PPC_SWITCH : nm == "ppc_draws" ? PPC_DRAWS : PPC_NONE; }
+static int ppc_refused(occ_sampler *s)
+{
+    if (s->probit) return set_error(s, OCC_E_STATE, "posterior predictive checks are not available for the probit model");
+    return set_error(s, OCC_E_STATE, "the posterior predictive check has not been switched on for this handle (set ppc_stats first)");
+}
+static int get_ppc_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
+{
+    const occ_sampler::Ppc &pc = s->ppc;
+    if (s->probit || !pc.ready) return ppc_refused(s);
+    if (field == PPC_SWITCH) {
+        std::vector<ChainScalars> h;
+        const int rc = read_scalars(s, h);
+        if (rc) return rc;
+        v.assign(1, (h[chain].site_on & PPC_BIT) ? 1.0 : 0.0);
+        return OCC_OK;
+    }
+    v.clear();
+    if ((size_t)chain < pc.last_on.size() && pc.last_on[(size_t)chain]) {
+        const size_t per = (size_t)pc.last_keep * (size_t)PPC_NCOL;
+        v.resize(per);
+        const unsigned long long *row = pc.last.data() + (size_t)chain * per;
+        for (size_t k = 0; k < per; ++k) v[k] = (k % PPC_NCOL) < 2 ? (double)row[k] * 0x1.0p-32 : (double)row[k];
+    }
+    return OCC_OK;
+}
+static int set_ppc_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+{
+    occ_sampler::Ppc &pc = s->ppc;
+    if (s->probit) return ppc_refused(s);
+    if (field == PPC_DRAWS) return pc.ready ? set_error(s, OCC_E_STATE, "ppc_draws is read-only") : ppc_refused(s);
+    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
+    if (in[0] != 0.0 && in[0] != 1.0) return set_error(s, OCC_E_BADARG, "ppc_stats is 0 or 1");
+    std::vector<ChainScalars> h;
+    int rc;
+    if ((rc = read_scalars(s, h))) return rc;
+    WAIT_TRY(s->side);
+    h[chain].site_on = (h[chain].site_on & ~PPC_BIT) | (in[0] != 0.0 ? PPC_BIT : 0u);
+    if ((rc = write_scalars(s, h))) return rc;
+    bool any = false;
+    for (const ChainScalars &sc : h) any = any || (sc.site_on & PPC_BIT);
+    const int z_ob_before = s->z_ob_kind();
+    pc.launch = any;
+    pc.ready = true;
+    if (s->z_ob_kind() != z_ob_before) destroy_graph(s);
+    return OCC_OK;
+}
+
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len)
 {
     if (!s || !name || !len) return OCC_E_BADARG;
@@ -3161,6 +3296,10 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     if (region_field(nm) != REGION_NONE) {
         const int rrc = get_region_state(s, chain, region_field(nm), v);
         return rrc ? rrc : give_state(s, v, out, cap, len);
+    }
+    if (ppc_field(nm) != PPC_NONE) {
+        const int prc = get_ppc_state(s, chain, ppc_field(nm), v);
+        return prc ? prc : give_state(s, v, out, cap, len);
     }
     int sums_kind = SUMS_SITE;
     const int site_q = site_field(nm, &sums_kind);
@@ -3228,6 +3367,7 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     WAIT_TRY(s->stream);
     const std::string nm(name);
     if (region_field(nm) != REGION_NONE) return set_region_state(s, chain, region_field(nm), in, len);
+    if (ppc_field(nm) != PPC_NONE) return set_ppc_state(s, chain, ppc_field(nm), in, len);
     int sums_kind = SUMS_SITE;
     const int sums_q = site_field(nm, &sums_kind);
     if (sums_q != SITE_NONE) return set_site_state(s, chain, sums_kind, sums_q, in, len);
@@ -3398,6 +3538,7 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     // (the timing loops always launch k_z_ob itself, never the twin that keeps the per-site sums; no captured graph of the
     // handle is replayed here)
     ScopedFlags plain_z_ob(&s->regions.launch, false);
+    plain_z_ob.set(&s->ppc.launch, false);
     for (int k = 0; k < N_SUMS; ++k) plain_z_ob.set(&s->sums[k].launch, false);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops
     if (rc) return rc;

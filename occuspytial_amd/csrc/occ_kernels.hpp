@@ -112,8 +112,8 @@ struct ChainScalars {
     int32_t err;               // OCC_E_* raised on device
     int32_t minres_itn_last;
     uint32_t site_on;          // bit 0: per-site posterior sums (Ctx::site_acc) are kept for this chain; bit 1: the log-likelihood
-                               // sums (Ctx::ll_acc); bit 2: the occupied sites per region and draw (Ctx::occ_rec); sits where
-                               // the layout had padding
+                               // sums (Ctx::ll_acc); bit 2: the occupied sites per region and draw (Ctx::occ_rec); bit 3: the
+                               // posterior predictive check (Ctx::ppc_rec); sits where the layout had padding
     unsigned long long krylov_total, krylov_sq_total, solves, carries;
 };
 
@@ -207,6 +207,11 @@ struct Ctx {
     const int16_t *region_id;  // [n]
     uint32_t *occ_rec;
     int region_G;
+    // Posterior predictive check of the detection histories (state names ppc_*; null until a chain is first switched on):
+    // four integer sums per chain and kept draw of the running occ_run, [C][keep][PPC_NCOL] -- the Freeman-Tukey discrepancy of
+    // the observed and of the replicated detections in fixed point, the replicated detections and the replicated sites with
+    // one -- added to by the z update of k_z_ob_ppc with integer atomics, zeroed by the host when the call's window opens.
+    unsigned long long *ppc_rec;
 };
 
 // ---- reductions ----------------------------------------------------------------------------------
@@ -2253,6 +2258,128 @@ __device__ __forceinline__ uint32_t *region_row(const Ctx &c, const ChainScalars
     return c.occ_rec + ((size_t)chain * sc.keep + (rel - sc.burnin)) * (size_t)c.region_G;
 }
 
+// ---- posterior predictive check (Ctx::ppc_rec, k_z_ob_ppc) -----------------------------------------------------------
+// Per kept draw every surveyed site's detections are replicated from the NEW z_i and alpha of the iteration: with
+// d_r = expit(w_r alpha) and u_r = block_uniform(key, r, 0, it, STREAM_PPC), r the flat visit row,
+//   y_i = sum_r y_r,   E_i = z_i sum_r d_r (rows in row order),   y*_i = z_i sum_r [u_r < d_r],
+// and the site's Freeman-Tukey terms are a_i = (sqrt y_i - sqrt E_i)^2, b_i = (sqrt y*_i - sqrt E_i)^2; a site with
+// z_i = 0 has had no detection, so both are 0.  The row of a draw: sum fx(a_i), sum fx(b_i), sum y*_i, #{i: y*_i > 0},
+// fx(x) = x 2^32 rounded to nearest: fixed point makes all four integer sums, whose order of addition cannot change a bit.
+enum : int { PPC_T_OBS = 0, PPC_T_REP = 1, PPC_DET_REP = 2, PPC_SITES_REP = 3, PPC_NCOL = 4 };
+__device__ __forceinline__ unsigned long long ppc_fx(double x) { return __double2ull_rn(x * 0x1.0p32); }
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long dpp_shifted_u64(unsigned long long b)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, ROW_MASK, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, ROW_MASK, 0xf, false);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// wave_sum's levels on 64-bit integers; the total is uniform (lane 63's)
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+    v += dpp_shifted_u64<0xB1, 0xf>(v);
+    v += dpp_shifted_u64<0x4E, 0xf>(v);
+    v += dpp_shifted_u64<0x141, 0xf>(v);
+    v += dpp_shifted_u64<0x140, 0xf>(v);
+    v += dpp_shifted_u64<0x142, 0xa>(v);
+    v += dpp_shifted_u64<0x143, 0xc>(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// One workgroup's sites into the four sums of one chain and kept draw, `row`.  EVERY thread of the workgroup comes here (the
+// barriers), one without a surveyed site with zeros: the wave's sums by DPP, the workgroup's in LDS, then one 64-bit
+// integer add to device memory per column that is not zero.
+__device__ __forceinline__ void ppc_count(unsigned long long *__restrict__ row, const unsigned long long (&term)[PPC_NCOL])
+{
+    __shared__ unsigned long long s_ppc[PPC_NCOL];
+    if (threadIdx.x < PPC_NCOL) s_ppc[threadIdx.x] = 0ull;
+    __syncthreads();
+    unsigned long long w[PPC_NCOL];
+#pragma unroll
+    for (int k = 0; k < PPC_NCOL; ++k) w[k] = wave_sum_u64(term[k]);
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+        for (int k = 0; k < PPC_NCOL; ++k)
+            if (w[k] != 0ull) atomicAdd(&s_ppc[k], w[k]);
+    }
+    __syncthreads();
+    if (threadIdx.x < PPC_NCOL) {
+        const unsigned long long v = s_ppc[threadIdx.x];
+        if (v != 0ull) atomicAdd(row + threadIdx.x, v);
+    }
+}
+// STATS = 4 (k_z_ob_ppc): the row of Ctx::ppc_rec this pass adds to, or null -- the chain's bit 3 is on and iteration `it`
+// is one the call records (the rows of record_draws).  Uniform over the workgroup.
+__device__ __forceinline__ unsigned long long *ppc_row(const Ctx &c, const ChainScalars &sc, int chain, uint32_t it)
+{
+    const uint32_t rel = it - sc.it_base;
+    if (!(sc.site_on & 8u) || c.ppc_rec == nullptr || rel < sc.burnin || rel - sc.burnin >= sc.keep) return nullptr;
+    return c.ppc_rec + ((size_t)chain * sc.keep + (rel - sc.burnin)) * (size_t)PPC_NCOL;
+}
+// The z update of one site of a chain and iteration whose detections are replicated (ppc_row is not null): z_update_site
+// with ONE loop over the visit rows of EVERY surveyed site, as z_update_site_ll has it -- d_r = expit_e(-wa, e) comes from the
+// dot product wa = -w_r alpha and the exponential e = exp(-|wa|) the update forms anyway; the replicate count accumulates
+// in the loop and is multiplied by z afterwards.  The per-site and the log-likelihood sums go along where `stats_on` /
+// `ll_on` say so.  psi, the product, D, the probability, z and the terms of the sums are formed by the operations of
+// z_update_site / z_update_site_ll: the same bits.  term: what the site adds to the four columns.
+template <class XB, class WA>
+__device__ __forceinline__ int z_update_site_ppc(const Ctx &c, uint64_t key, int chain, int i, uint32_t it, double eta_i, bool stats_on,
+                                                 bool ll_on, XB xb_of, WA wa_of, unsigned long long (&term)[PPC_NCOL])
+{
+    const int sidx = c.site_sidx[i], n = c.n;
+    const bool not_surveyed = sidx < 0;
+    const bool seen = !not_surveyed && c.obs_site[sidx];  // detection seen: z stays 1 (base.py:116-118)
+    const double a0 = xb_of() + eta_i, e0 = exp(-fabs(a0));
+    const double num1 = expit_e(a0, e0);
+    double pr = num1, E = 0.0;
+    int y_obs = 0, y_rep = 0, zi = 1;
+    if (!not_surveyed) {
+        double prod = 1.0, ll = seen ? lsig_e(a0, e0) : 0.0;
+        const int r0 = c.site_ptr[sidx], r1 = c.site_ptr[sidx + 1];
+        for (int r = r0; r < r1; ++r) {
+            const double wa = wa_of(r), e = exp(-fabs(wa));
+            const double d = expit_e(-wa, e);
+            const double ur = block_uniform(key, (uint32_t)r, 0, it, STREAM_PPC);
+            E += d;  // rows in row order
+            y_rep += (ur < d) ? 1 : 0;
+            if (seen) {
+                const int y = c.yrow[r] ? 1 : 0;
+                y_obs += y;
+                if (ll_on) ll += lsig_e(y ? -wa : wa, e);  // rows in row order
+            } else {
+                const double ex = expit_e(wa, e);
+                prod = (r == r0) ? ex : prod * ex;
+            }
+        }
+        if (seen) {
+            if (stats_on) site_add(c, chain, i, num1, 1.0, 1.0, eta_i);
+            if (ll_on) ll_add(c, chain, i, exp(ll), ll);
+        } else {
+            const double num = num1 * prod;
+            const double den = (1.0 - num1) + num;  // the site's likelihood: what the update divides by
+            pr = num / den;
+            if (ll_on) ll_add(c, chain, i, den, log(den));
+        }
+    }
+    if (!seen) {
+        const double u = block_uniform(key, (uint32_t)i, 0, it, STREAM_Z);
+        zi = (u < pr) ? 1 : 0;
+        c.z[(size_t)chain * n + i] = (uint8_t)zi;
+        if (stats_on) site_add(c, chain, i, num1, pr, zi ? 1.0 : 0.0, eta_i);
+    }
+    if (!not_surveyed && zi) {
+        const double se = sqrt(E), da = sqrt((double)y_obs) - se, db = sqrt((double)y_rep) - se;
+        term[PPC_T_OBS] = ppc_fx(da * da);
+        term[PPC_T_REP] = ppc_fx(db * db);
+        term[PPC_DET_REP] = (unsigned long long)y_rep;
+        term[PPC_SITES_REP] = y_rep > 0 ? 1ull : 0ull;
+    }
+    return zi;
+}
+
+
 template <int P, int STATS = 0>
 __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict__ scs, int chain_base, int e, bool synced, unsigned seq,
                                           bool per_wave, int debug_skip = 0,  // debug_skip (timing experiments): 1 = no z update, 2 = no omega_b draw
@@ -2393,7 +2520,45 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
     }
     if (writer) record_draws<P>(c, sc, chain, it, alpha, beta, sc.tau);
     const int n = c.n, i = (blk >> 1) * blockDim.x + threadIdx.x;
-    if constexpr (STATS == 3) {
+    if constexpr (STATS == 4) {
+        // the two kinds of sums, the region counts and the predictive check, each where the chain's bit is on.  As below, no
+        // thread leaves before the barriers of the two reductions, and `row` / `prow` are uniform over the workgroup
+        const uint32_t on = sc.site_on;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        if (debug_skip & 1) return;
+        if (writer && stats_on) c.site_count[chain] += 1.0;
+        if (writer && ll_on) c.ll_count[chain] += 1.0;
+        uint32_t *row = region_row(c, sc, chain, it);
+        unsigned long long *prow = ppc_row(c, sc, chain, it);
+        const int g = (row != nullptr && i < n) ? (int)c.region_id[i] : -1;
+        int zi = 0;
+        unsigned long long term[PPC_NCOL] = {0ull, 0ull, 0ull, 0ull};
+        if (i < n) {
+            const double eta_i = c.eta[(size_t)chain * n + i];
+            if (prow != nullptr) {
+                zi = z_update_site_ppc(
+                    c, key, chain, i, it, eta_i, stats_on, ll_on,
+                    [&]() {
+                        double xb = 0.0;
+#pragma unroll
+                        for (int a = 0; a < P; ++a) xb = fma(c.Xt[(size_t)a * c.n + i], beta[a], xb);
+                        return xb;
+                    },
+                    [&](int r) {
+                        double wa = 0.0;
+#pragma unroll
+                        for (int a = 0; a < MAXC; ++a)
+                            if (a < c.q) wa = fma(c.Wt[(size_t)a * c.R + r], -alpha[a], wa);
+                        return wa;
+                    },
+                    term);
+            } else {
+                zi = z_update_site<P, 0, 3>(c, key, chain, i, it, beta, alpha, eta_i, stats_on, ll_on);
+            }
+        }
+        if (row != nullptr) region_count(row, c.region_G, g, zi);
+        if (prow != nullptr) ppc_count(prow, term);
+    } else if constexpr (STATS == 3) {
         // the two kinds of sums and the region counts, each where the chain's bit is on.  No thread leaves before the
         // counts' barriers: one past n, or of a site with a detection, comes back from the update with its z
         const uint32_t on = sc.site_on;
@@ -2518,7 +2683,40 @@ __device__ __forceinline__ void z_ob_body_g(const Ctx &c, ChainScalars *__restri
         }
     }
     const int n = c.n, i = (blk >> 1) * blockDim.x + threadIdx.x;
-    if constexpr (STATS == 3) {
+    if constexpr (STATS == 4) {
+        const uint32_t on = sc.site_on;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        if (debug_skip & 1) return;
+        if (writer && stats_on) c.site_count[chain] += 1.0;
+        if (writer && ll_on) c.ll_count[chain] += 1.0;
+        uint32_t *row = region_row(c, sc, chain, it);
+        unsigned long long *prow = ppc_row(c, sc, chain, it);
+        const int g = (row != nullptr && i < n) ? (int)c.region_id[i] : -1;
+        int zi = 0;
+        unsigned long long term[PPC_NCOL] = {0ull, 0ull, 0ull, 0ull};
+        if (i < n) {
+            const double eta_i = c.eta[(size_t)chain * n + i];
+            if (prow != nullptr) {
+                zi = z_update_site_ppc(
+                    c, uniform_u64(sc.key), chain, i, it, eta_i, stats_on, ll_on,
+                    [&]() {
+                        double xb = 0.0;
+                        for (int a = 0; a < c.p; ++a) xb = fma(c.Xt[(size_t)a * c.n + i], sc.beta[a], xb);
+                        return xb;
+                    },
+                    [&](int r) {
+                        double wa = 0.0;
+                        for (int a = 0; a < c.q; ++a) wa = fma(c.Wt[(size_t)a * c.R + r], -sc.alpha[a], wa);
+                        return wa;
+                    },
+                    term);
+            } else {
+                zi = z_update_site_g<0, 3>(c, sc, chain, i, it, eta_i, stats_on, ll_on);
+            }
+        }
+        if (row != nullptr) region_count(row, c.region_G, g, zi);
+        if (prow != nullptr) ppc_count(prow, term);
+    } else if constexpr (STATS == 3) {
         const uint32_t on = sc.site_on;
         const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
         if (debug_skip & 1) return;
@@ -2649,6 +2847,24 @@ __global__ void __launch_bounds__(256, 3) k_z_ob_occ(OCC_KARGS, int flags)  // f
         const bool synced = (flags & 1) && c.sync != nullptr;
         const unsigned seq = synced ? (unsigned)__builtin_amdgcn_readfirstlane((int)c.sync[SYNC_MAIN]) : 0u;  // (uniform: a scalar register)
         z_ob_body<P, 3>(c, scs, chain_base, e, synced, seq, (flags & 2) != 0, (flags >> 3) & 3, (flags & 4) != 0);
+    }
+}
+
+// k_z_ob with the posterior predictive check of the detection histories (Ctx::ppc_rec), the occupied sites per region, the
+// log-likelihood sums and the per-site posterior sums, each for the chains whose bit of ChainScalars::site_on is set:
+// launched in k_z_ob's place while a chain of the handle has bit 3 on.  A fifth kernel family, so that the four above stay
+// the code they were.
+template <int P>
+__global__ void __launch_bounds__(256, 3) k_z_ob_ppc(OCC_KARGS, int flags)  // flags: k_z_ob's
+{
+    __builtin_amdgcn_s_setprio(3);
+    const Ctx &c = *cp;
+    if constexpr (P == 0) {
+        z_ob_body_g<4>(c, scs, chain_base, e, (flags & 2) != 0, (flags >> 3) & 3);
+    } else {
+        const bool synced = (flags & 1) && c.sync != nullptr;
+        const unsigned seq = synced ? (unsigned)__builtin_amdgcn_readfirstlane((int)c.sync[SYNC_MAIN]) : 0u;  // (uniform: a scalar register)
+        z_ob_body<P, 4>(c, scs, chain_base, e, synced, seq, (flags & 2) != 0, (flags >> 3) & 3, (flags & 4) != 0);
     }
 }
 

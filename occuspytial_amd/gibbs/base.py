@@ -14,6 +14,7 @@ from .._problem import FlatProblem, default_start
 from ..chain import Chain
 from ..data import Data
 from ..posterior import PosteriorParameter
+from ..ppc import ppc_flag
 from ..regions import region_ids
 from ..utils import get_generator
 from .parallel import sample_parallel
@@ -115,7 +116,8 @@ class GibbsBase:
                 self.chain.append(self.state.posteriors)
         return self.chain
 
-    def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False, waic=False, regions=None):
+    def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False, waic=False, regions=None,
+               ppc=False):
         """Draw ``size`` iterations per chain and return the kept ``alpha``, ``beta``, ``tau`` draws.
 
         Same contract as the reference (``base.py:243-291``): ``burnin < size`` else ``ValueError``;
@@ -135,6 +137,11 @@ class GibbsBase:
         draw, the occupied sites of every region: ``out['occupied']`` is ``(chains, size - burnin, G)``, it appears in
         ``out.summary`` (mean, sd, HDI, ESS, R-hat of the finite-sample occupancy), and ``out.regions`` is a
         :class:`~occuspytial_amd.regions.RegionOccupancy` (sizes, detected sites, proportion of area occupied).
+
+        ``ppc=True`` (samplers that run on the engine; logit link): per kept draw the device replicates every surveyed
+        site's detections from the draw's z and alpha and records the Freeman-Tukey discrepancy of the observed and of the
+        replicated data; ``out.ppc`` is a :class:`~occuspytial_amd.ppc.PredictiveCheck` (Bayesian p-value, lack-of-fit
+        ratio; ``None`` otherwise).  ``out.summary`` and the chains are unchanged.
         """
         if burnin >= size:
             raise ValueError('burnin value cannot be larger than sample size')
@@ -148,6 +155,9 @@ class GibbsBase:
         if ids is not None:
             self._refuse_regions()
             extra['regions'] = ids
+        if ppc_flag(ppc):
+            self._refuse_ppc()
+            extra['ppc'] = True
         samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start,
                                   progressbar=progressbar, **extra)
         out = PosteriorParameter(*samples)
@@ -156,7 +166,15 @@ class GibbsBase:
             setattr(out, result, self.__dict__.pop('_' + result))
         if ids is not None:
             out.regions = self._region_result(ids, out)
+        if 'ppc' in extra:
+            out.ppc = self.__dict__.pop('_ppc')
         return out
+
+    def _refuse_ppc(self):
+        """The detections are replicated by the engine's z update: a sampler with a Python ``step`` has none."""
+        if not hasattr(self, '_run_chains'):
+            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: posterior predictive checks are formed by '
+                                      'the device engine only')
 
     def _refuse_regions(self):
         """The occupied sites per region are counted by the engine's z update: a sampler with a Python ``step`` has none."""

@@ -4,6 +4,7 @@ import numpy as np
 from .. import _lib
 from .._engine import Engine, EngineGroup
 from ..chain import Chain
+from ..ppc import PredictiveCheck, ppc_flag
 from ..regions import region_ids
 from ..sites import SiteSummary
 from ..waic import WAIC
@@ -139,7 +140,13 @@ class LogitICARGibbs(GibbsBase):
         except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
             raise ValueError(f'the loaded engine library does not count the occupied sites per region ({exc}): rebuild it') from None
 
-    def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False, regions=None):
+    def _ppc_switch(self, eng, on):
+        try:
+            eng.ppc_stats(on)
+        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
+            raise ValueError(f'the loaded engine library has no posterior predictive check ({exc}): rebuild it') from None
+
+    def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False, regions=None, ppc=False):
         """Continue the chains of ``checkpoint`` (a dict from :meth:`checkpoint` or the path of its ``.npz``)
         for ``size`` more iterations on this sampler's problem.  Returns a ``PosteriorParameter`` of the new
         draws; every chain's ``Chain`` is the continuation (use ``Chain.expand`` / ``append`` to join them to
@@ -147,7 +154,8 @@ class LogitICARGibbs(GibbsBase):
         per-site sums go on from those the checkpoint holds (from zero if it holds none); the result's ``sites`` covers
         every iteration accumulated so far, those before the checkpoint included.  ``waic=True``: the same for the
         log-likelihood sums and the result's ``waic``.  ``regions`` (as in :meth:`sample`): the occupied sites per region of
-        the new draws, ``out['occupied']`` and ``out.regions``; the draws belong to a call, so nothing of them is carried."""
+        the new draws, ``out['occupied']`` and ``out.regions``; the draws belong to a call, so nothing of them is carried.
+        ``ppc=True``: the posterior predictive check of the new draws, ``out.ppc``; likewise nothing of it is carried."""
         from ..posterior import PosteriorParameter
         from tqdm.auto import tqdm
         if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, '__fspath__'):
@@ -158,6 +166,9 @@ class LogitICARGibbs(GibbsBase):
         ids = region_ids(regions, self._problem.n)
         if ids is not None:
             self._refuse_regions()
+        ppc = ppc_flag(ppc)
+        if ppc:
+            self._refuse_ppc()
         C = int(checkpoint['n_chains'])
         self.__dict__['_stepping'] = False
         eng = self._get_engine([int(k) for k in np.asarray(checkpoint['keys'])])
@@ -170,6 +181,11 @@ class LogitICARGibbs(GibbsBase):
         if ids is not None:
             self._regions_call(lambda: (eng.regions(ids), eng.region_stats(True)))
             occupied = np.zeros((C, size, max(int(ids.max()) + 1, 1)))
+        if ppc:
+            self._ppc_switch(eng, True)
+            ppc_rows = np.zeros((C, size, 4))
+        elif getattr(eng, '_ppc_on', False):   # (the checkpoint's switch was on: this call did not ask)
+            eng.ppc_stats(False)
         alpha = np.zeros((C, size, self._problem.q))
         beta = np.zeros((C, size, self._problem.p))
         tau = np.zeros((C, size))
@@ -181,6 +197,8 @@ class LogitICARGibbs(GibbsBase):
             alpha[:, done:done + step], beta[:, done:done + step], tau[:, done:done + step] = eng.run(step, 0)
             if ids is not None:
                 occupied[:, done:done + step] = [eng.region_draws(c) for c in range(C)]
+            if ppc:
+                ppc_rows[:, done:done + step] = [eng.ppc_draws(c) for c in range(C)]
             done += step
             bar.update(step)
         bar.close()
@@ -194,10 +212,13 @@ class LogitICARGibbs(GibbsBase):
             setattr(out, _lib.SUMS_KINDS[kind].result, SUMS_RESULT[kind].from_engine(eng))
         if ids is not None:
             out.regions = self._region_result(ids, out)
+        if ppc:
+            out.ppc = PredictiveCheck.from_problem(self._problem, ppc_rows)
         return out
 
     # ------------------------------------------------------------------ batched chains
-    def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False, waic=False, regions=None):
+    def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False, waic=False, regions=None,
+                    ppc=False):
         """All chains of one ``sample`` call as one device batch.
 
         Mirrors ``GibbsBase._run`` (base.py:214-241) per chain: start values from the chain's own
@@ -208,6 +229,9 @@ class LogitICARGibbs(GibbsBase):
         ``waic``: the log-likelihood sums, switched in exactly the same way.
         ``regions`` (an array of region ids, or None): the count of occupied sites per region, switched in the same way; every
         chunk's rows are appended to the chains' ``occupied``.  With the default no call about it reaches the engine.
+        ``ppc``: the posterior predictive check, switched in the same way; every chunk's rows are appended and the
+        :class:`~occuspytial_amd.ppc.PredictiveCheck` made of them is left for ``sample``.  With the default no call about
+        it reaches the engine.
         """
         from tqdm.auto import tqdm
 
@@ -230,11 +254,14 @@ class LogitICARGibbs(GibbsBase):
             self._regions_call(lambda: eng.regions(regions))
         elif getattr(eng, '_region_on', False):   # (a reused engine that an earlier call left counting)
             eng.region_stats(False)
+        if ppc or getattr(eng, '_ppc_on', False):   # (off during burn-in; a reused engine that an earlier call left on)
+            self._ppc_switch(eng, False)
         sums_on = False
 
         C = len(samplers)
         keep = size - burnin
         extra = {'occupied': np.zeros((C, keep, max(int(regions.max()) + 1, 1)))} if regions is not None else {}
+        ppc_rows = np.zeros((C, keep, 4)) if ppc else None
         alpha = np.zeros((C, keep, self._problem.q))
         beta = np.zeros((C, keep, self._problem.p))
         tau = np.zeros((C, keep))
@@ -252,12 +279,16 @@ class LogitICARGibbs(GibbsBase):
                         self._sums_switch(eng, kind, True)
                     if regions is not None:
                         eng.region_stats(True)
+                    if ppc:
+                        eng.ppc_stats(True)
                     sums_on = True
                 a_, b_, t_ = eng.run(step, b)
                 m = step - b
                 alpha[:, kept:kept + m], beta[:, kept:kept + m], tau[:, kept:kept + m] = a_, b_, t_
                 if regions is not None:
                     extra['occupied'][:, kept:kept + m] = [eng.region_draws(c) for c in range(C)]
+                if ppc:
+                    ppc_rows[:, kept:kept + m] = [eng.ppc_draws(c) for c in range(C)]
                 kept += m
             done += step
             for bar in bars:
@@ -274,6 +305,8 @@ class LogitICARGibbs(GibbsBase):
         self._pull_state(eng, 0)
         for kind in kinds:
             self.__dict__['_' + _lib.SUMS_KINDS[kind].result] = SUMS_RESULT[kind].from_engine(eng)
+        if ppc:
+            self.__dict__['_ppc'] = PredictiveCheck.from_problem(self._problem, ppc_rows)
         return chains
 
 

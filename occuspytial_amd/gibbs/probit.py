@@ -103,6 +103,10 @@ class ProbitRSRGibbs(GibbsBase):
         # and the site's marginal likelihood is not what it forms)
         raise NotImplementedError(_lib.SUMS_KINDS[kind].probit)
 
+    def _refuse_ppc(self):
+        # (its detection part is a probit regression on the auxiliary scale: a check of it is out of scope so far)
+        raise NotImplementedError('posterior predictive checks are not available for the probit model')
+
     step = LogitICARGibbs.step
     checkpoint = LogitICARGibbs.checkpoint
     resume = LogitICARGibbs.resume

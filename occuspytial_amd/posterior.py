@@ -42,6 +42,7 @@ class PosteriorParameter:
     sites = None   # a SiteSummary when sample(..., site_summaries=True) asked for the per-site posterior map
     waic = None    # a WAIC when sample(..., waic=True) asked for the streaming log-likelihood sums
     regions = None  # a RegionOccupancy when sample(..., regions=...) asked for the occupied sites per region and draw
+    ppc = None     # a PredictiveCheck when sample(..., ppc=True) asked for the posterior predictive check
 
     def __init__(self, *chains):
         self.data = self._create_inference_data(chains)
