@@ -82,32 +82,18 @@ inline DeviceLease lease_device(int device) { return DeviceLease(device_slot(dev
 // is switched per chain (its bit of ChainScalars::site_on), is kept in arrays of its own ([nacc C n] sums, [C] counts of
 // accumulated iterations) by a z-update kernel of its own that stands where k_z_ob stands, and is read and written through
 // occ_get_state / occ_set_state.  Whatever the host does for a kind -- names, snapshot and restore around a call that may
-// be re-run, the choice of kernel -- is a loop over this table.
-using KernelEI = void (*)(const Ctx *, ChainScalars *, Slot *, int, int, int);
-KernelEI pick_z_ob_stats(int p), pick_z_ob_ll(int p), pick_z_ob_occ(int p), pick_z_ob_ppc(int p);  // (defined with the other choices of an instantiation, below)
+// be re-run -- is a loop over this table.  Which z-update kernel runs is not a kind's business: occ_plan.hpp's OUTPUTS.
 enum : int { SUMS_SITE = 0, SUMS_LL = 1, N_SUMS = 2 };
 struct SumsKind {
     uint32_t bit;  // of ChainScalars::site_on
     int nacc;
     double *Ctx::*acc, *Ctx::*count;
     const char *what, *sw, *cnt, *sum[SITE_NACC];  // in messages; state names: switch, count, the sums in their *_NACC order
-    KernelEI (*z_ob)(int p);  // the z-update kernel that keeps it ...
-    int rank;                 // ... launched when no kind of higher rank is on (a kernel also serves the kinds below its own)
 };
 const SumsKind SUMS[N_SUMS] = {
-    {1u, SITE_NACC, &Ctx::site_acc, &Ctx::site_count, "site summaries", "site_stats", "site_count",
-     {"site_psi", "site_occ", "site_z", "site_eta", "site_eta2"}, pick_z_ob_stats, 1},
-    {2u, LL_NACC, &Ctx::ll_acc, &Ctx::ll_count, "log-likelihood sums", "ll_stats", "ll_count",
-     {"ll_lik", "ll_log", "ll_log2"}, pick_z_ob_ll, 2}};
-// What occ_sampler::z_ob_kind() answers while a chain keeps the occupied sites per region and draw (bit REGION_BIT of
-// ChainScalars::site_on; occ_sampler::regions): k_z_ob_occ, which ranks above every kind of sums and serves them all.
-// Not a row of SUMS: it keeps no sums, has no count and nothing to snapshot -- its record is zeroed when a call's window opens.
-enum : int { Z_OB_OCC = N_SUMS };
-constexpr uint32_t REGION_BIT = 4u;
-// ... and while a chain keeps the posterior predictive check (bit PPC_BIT; occ_sampler::ppc): k_z_ob_ppc, which ranks above
-// k_z_ob_occ and serves the regions and every kind of sums as well.  Like the regions, a record per call and no sums.
-enum : int { Z_OB_PPC = N_SUMS + 1 };
-constexpr uint32_t PPC_BIT = 8u;
+    {OUT_SITE, SITE_NACC, &Ctx::site_acc, &Ctx::site_count, "site summaries", output_of(OUT_SITE).sw, "site_count",
+     {"site_psi", "site_occ", "site_z", "site_eta", "site_eta2"}},
+    {OUT_LL, LL_NACC, &Ctx::ll_acc, &Ctx::ll_count, "log-likelihood sums", output_of(OUT_LL).sw, "ll_count", {"ll_lik", "ll_log", "ll_log2"}}};
 
 }  // namespace
 
@@ -142,58 +128,44 @@ struct occ_sampler {
     uint8_t *snap_z = nullptr;
     double2 *snap_x = nullptr;
     double *snap_theta = nullptr;  // reduced-rank model: the basis coefficients
-    // per-site running sums, kind by kind (SUMS).  launch: a chain has the kind's switch on, so launch_kind() launches a
-    // kernel that keeps it where k_z_ob stands (z_ob_kind; baked into captured graphs: a change of kernel drops them).  The
-    // sums are part of what a call is re-run from: snap ([nacc C n] sums, then [C] counts), snapped: taken for the running call.
+    // The OR of every chain's ChainScalars::site_on (probit handle: OUT_REGION while a chain has region_stats on), kept by
+    // flip_output.  It decides the family launched where k_z_ob stands (z_ob_kind; baked into captured graphs: a change of
+    // family drops them) and which records a call opens.
+    uint32_t outputs_on = 0u;
+    int z_ob_kind() const { return output_level(outputs_on); }
+    // per-site running sums, kind by kind (SUMS): part of what a call is re-run from.  snap: [nacc C n] sums, then [C]
+    // counts; snapped: taken for the running call.
     struct SumsRun {
-        bool launch = false, snapped = false;
+        bool snapped = false;
         double *snap = nullptr;
     } sums[N_SUMS];
-    // Occupied sites per region and kept draw (state names region_id, region_stats, region_draws).  G = 0: no map yet.
-    // launch: a chain has its switch on, so k_z_ob_occ (probit: k_pb_z_occ) stands where the plain kernel stands.  rec: the
-    // counts of the running occ_run on the device, [C][keep][G], sized like rec_buf and grown between calls, zeroed on the
-    // stream when the call's window opens and copied out (pin) behind its last batch; last: those of the last completed
-    // occ_run on the host, for the chains whose switch was on during it (last_on).
-    struct Regions {
-        bool launch = false;
-        int G = 0;
-        std::vector<int16_t> id;
-        int16_t *id_dev = nullptr;
-        uint32_t *rec = nullptr, *pin = nullptr;
+    // The record of one occ_run, [C][keep][width] elements: `rec` on the device, sized like rec_buf and grown between calls,
+    // zeroed on the stream when the call's window opens and copied out (pin) behind its last batch; last: that of the last
+    // completed occ_run on the host, for the chains whose switch was on during it (last_on).  open / copy_out / close: below.
+    template <class T>
+    struct CallRecord {
+        T *rec = nullptr, *pin = nullptr;
         size_t rec_cap = 0, pin_cap = 0, run_need = 0;
-        std::vector<uint32_t> last;
+        std::vector<T> last;
         std::vector<uint8_t> last_on;
         int64_t last_keep = 0;
-        int last_G = 0;
+    };
+    // Occupied sites per region and kept draw (state names region_id, region_stats, region_draws).  G = 0: no map yet.
+    // The record's width is G counts (last_G: of the last completed call).
+    struct Regions : CallRecord<uint32_t> {
+        int G = 0, last_G = 0;
+        std::vector<int16_t> id;
+        int16_t *id_dev = nullptr;
         // probit handle: the chains' switches (its PbChain has no word for them) and the address of `rec`, in device memory
         std::vector<uint32_t> pb_on;
         uint32_t *pb_on_dev = nullptr;
         uint32_t **pb_rec = nullptr;
     } regions;
     // Posterior predictive check (state names ppc_stats, ppc_draws; logit models).  ready: a chain has been switched on once.
-    // launch: a chain has its switch on, so k_z_ob_ppc stands where k_z_ob stands.  rec: the four integer sums per chain and
-    // kept draw of the running occ_run on the device, [C][keep][PPC_NCOL], sized like rec_buf and grown between calls, zeroed
-    // on the stream when the call's window opens and copied out (pin) behind its last batch; last: those of the last
-    // completed occ_run on the host, for the chains whose switch was on during it (last_on).
-    struct Ppc {
-        bool ready = false, launch = false;
-        unsigned long long *rec = nullptr, *pin = nullptr;
-        size_t rec_cap = 0, pin_cap = 0, run_need = 0;
-        std::vector<unsigned long long> last;
-        std::vector<uint8_t> last_on;
-        int64_t last_keep = 0;
+    // The record's width is the PPC_NCOL integer sums.
+    struct Ppc : CallRecord<unsigned long long> {
+        bool ready = false;
     } ppc;
-    // the kind whose z-update kernel runs: Z_OB_PPC while a chain keeps the predictive check; else Z_OB_OCC while a chain
-    // counts regions; else, of the kinds of sums with a chain switched on, the one of highest rank; -1: k_z_ob itself
-    int z_ob_kind() const
-    {
-        if (ppc.launch) return Z_OB_PPC;
-        if (regions.launch) return Z_OB_OCC;
-        int top = -1;
-        for (int k = 0; k < N_SUMS; ++k)
-            if (sums[k].launch && (top < 0 || SUMS[k].rank > SUMS[top].rank)) top = k;
-        return top;
-    }
     std::vector<ChainScalars> snap_sc;
     // fixed problem arrays on the device, in upload order: what a group broadcasts from its root (occ_create_group /
     // occ_create_distributed); defer_fixed: allocate only, the bytes arrive by broadcast
@@ -435,14 +407,13 @@ int set_error(occ_sampler *s, int code, const char *msg)
     return code;
 }
 
-// Boolean fields of the engine set for the length of a scope; what they held comes back at its end, whichever way it ends.
-struct ScopedFlags {
-    bool *field[4], old[4];
-    int n = 0;
-    ScopedFlags(bool *f, bool value) { set(f, value); }
-    ScopedFlags(const ScopedFlags &) = delete;
-    ~ScopedFlags() { while (n > 0) { --n; *field[n] = old[n]; } }
-    void set(bool *f, bool value) { field[n] = f; old[n++] = *f; *f = value; }
+// A field of the engine set for the length of a scope; what it held comes back at its end, whichever way it ends.
+template <class T>
+struct Scoped {
+    T *field, old;
+    Scoped(T *f, T value) : field(f), old(*f) { *f = value; }
+    Scoped(const Scoped &) = delete;
+    ~Scoped() { *field = old; }
 };
 
 // A buffer an occ_run needs `need` elements of, kept between calls and GROWN BETWEEN CALLS ONLY: the stream is waited for
@@ -479,6 +450,7 @@ void split_rows(const double *rec, int C, int64_t keep, int q, int p, double *ou
 }
 
 using KernelE = void (*)(const Ctx *, ChainScalars *, Slot *, int, int);
+using KernelEI = void (*)(const Ctx *, ChainScalars *, Slot *, int, int, int);
 
 KernelEI pick_beta_partial(int p)
 {
@@ -516,11 +488,11 @@ KernelRsr pick_rsr_solve(int m)
         default: return k_rsr_solve<8>;
     }
 }
-KernelEI pick_z_ob(int p) { return OCC_PICK_P(k_z_ob, p); }
-KernelEI pick_z_ob_stats(int p) { return OCC_PICK_P(k_z_ob_stats, p); }
-KernelEI pick_z_ob_ll(int p) { return OCC_PICK_P(k_z_ob_ll, p); }
-KernelEI pick_z_ob_occ(int p) { return OCC_PICK_P(k_z_ob_occ, p); }
-KernelEI pick_z_ob_ppc(int p) { return OCC_PICK_P(k_z_ob_ppc, p); }
+// the z-update families by level (occ_plan.hpp: output_level)
+KernelEI (*const Z_OB_FAMILY[N_OUTPUTS + 1])(int p) = {
+    [](int p) -> KernelEI { return OCC_PICK_P(k_z_ob, p); }, [](int p) -> KernelEI { return OCC_PICK_P(k_z_ob_stats, p); },
+    [](int p) -> KernelEI { return OCC_PICK_P(k_z_ob_ll, p); }, [](int p) -> KernelEI { return OCC_PICK_P(k_z_ob_occ, p); },
+    [](int p) -> KernelEI { return OCC_PICK_P(k_z_ob_ppc, p); }};
 KernelEI pick_omega_a(int q)
 {
     switch (q) {
@@ -562,8 +534,7 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
     const dim3 blk((unsigned)P.tpb), gs((unsigned)c.nb_n, (unsigned)c.C), gr((unsigned)c.nb_r, (unsigned)c.C);
     const int tp = P.generic ? 0 : c.p, tq = P.generic ? 0 : c.q;  // template arguments: 0 = the generic (run-time) instantiation
     const size_t lds_p = P.generic ? generic_lds_bytes(nacc(c.p), P.tpb) : 0, lds_q = P.generic ? generic_lds_bytes(nacc(c.q), P.tpb) : 0;
-    const int zk = s->z_ob_kind();  // (a kind of per-site sums is switched on: its kernel where k_z_ob stands)
-    const KernelEI z_ob = zk < 0 ? pick_z_ob(tp) : zk == Z_OB_PPC ? pick_z_ob_ppc(tp) : zk == Z_OB_OCC ? pick_z_ob_occ(tp) : SUMS[zk].z_ob(tp);
+    const KernelEI z_ob = Z_OB_FAMILY[s->z_ob_kind()](tp);  // (an output is switched on: its family where k_z_ob stands)
     switch (kind) {
         case K_OMEGA_B: hipLaunchKernelGGL(pick_omega_b(tp), gs, blk, 0, st, OCC_ARGS); break;
         case K_NOISE:
@@ -772,7 +743,7 @@ int eager_sequence(occ_sampler *s)
         if (prc) return prc;
     }
     // one stream, reference order: stream order is the synchronisation, the hand-over counters stay untouched
-    ScopedFlags no_sync(&s->launch_sync, false);
+    Scoped<bool> no_sync(&s->launch_sync, false);
     const int rc = walk(s, s->stream, seq_eager(), seq_solve(s, true), s->parity);
     if (rc) return rc;
     s->parity ^= 1;
@@ -866,7 +837,7 @@ int build_graph(occ_sampler *s, int cap)
     if (!seq_mode_runs(mode, seq_solve(s, false)))
         return set_error(s, OCC_E_HIP, "hand-overs by device counters need a solve of one launch or the reduced-rank model: no graph to capture");
     const int n_seq = sequences_per_enqueue(mode);
-    ScopedFlags sync(&s->launch_sync, mode == SEQ_RSR_ONE_STREAM ? false : s->launch_sync);  // one stream: its order is the synchronisation
+    Scoped<bool> sync(&s->launch_sync, mode == SEQ_RSR_ONE_STREAM ? false : s->launch_sync);  // one stream: its order is the synchronisation
     if (mode == SEQ_COUNTERS) {
         // No event nodes: the kernels hand over through the device counters of Ctx::sync.  The counters restart with the
         // capture: the main stream's sequence numbers live in two words indexed by the sequence PARITY, and a capture that
@@ -978,7 +949,7 @@ int open_window(occ_sampler *s, int64_t n_iter, int64_t burnin, int64_t keep, bo
         for (int k = 0; k < N_SUMS; ++k) {  // the per-site sums are part of what the call is re-run from: no iteration is counted twice
             occ_sampler::SumsRun &r = s->sums[k];
             const size_t nsum = (size_t)SUMS[k].nacc * Cn;
-            r.snapped = r.launch;
+            r.snapped = (s->outputs_on & SUMS[k].bit) != 0u;
             if (!r.snapped) continue;
             if (!r.snap && (rc = dev_alloc(s, &r.snap, nsum + (size_t)c.C, false))) return rc;
             HIP_TRY(hipMemcpyAsync(r.snap, c.*SUMS[k].acc, sizeof(double) * nsum, hipMemcpyDeviceToDevice, s->stream));
@@ -1288,95 +1259,59 @@ int residency_probe(occ_sampler *s, bool *ok)
 
 }  // namespace
 
-// ---- occupied sites per region and draw: the record of one occ_run (both models) ---------------------------------------
+// ---- the record of one occ_run (occ_sampler::CallRecord: the regions' counts, both models; the predictive check's sums) ----
 namespace {
 
-// Head of an occ_run with `keep` recorded rows: the device record holds C keep G counts (grown between calls: nothing is in
-// flight to the old one) and is zeroed on the stream in front of the call's kernels -- also when a call is re-run after a
-// run-time fallback, so a re-run counts nothing twice.  What the last call left on the host is dropped: region_draws
-// speaks of the last COMPLETED call.  *moved: the record's address changed (the descriptors that hold it are the caller's).
-int regions_open(occ_sampler *s, int C, int64_t keep, bool *moved)
+// Head of an occ_run with `keep` recorded rows of `width` elements per chain (0: no chain has the output on).  The device
+// record is grown between calls (nothing is in flight to the old one) and zeroed on the stream in front of the call's
+// kernels -- also when a call is re-run after a run-time fallback, so a re-run counts nothing twice.  What the last call
+// left on the host is dropped: the *_draws names speak of the last COMPLETED call.  The descriptors that hold the record's
+// address are the caller's.
+template <class T>
+int record_open(occ_sampler *s, occ_sampler::CallRecord<T> &r, int C, int64_t keep, size_t width)
 {
-    occ_sampler::Regions &rg = s->regions;
-    *moved = false;
-    rg.last.clear();
-    rg.last_on.assign((size_t)C, 0);
-    rg.last_keep = 0;
-    rg.run_need = rg.launch ? (size_t)C * (size_t)keep * (size_t)rg.G : 0;
-    if (!rg.run_need) return OCC_OK;
+    r.last.clear();
+    r.last_on.assign((size_t)C, 0);
+    r.last_keep = 0;
+    r.run_need = (size_t)C * (size_t)keep * width;
+    if (!r.run_need) return OCC_OK;
     int rc;
-    if ((rc = grow_device(s, &rg.rec, &rg.rec_cap, rg.run_need, moved))) return rc;
-    if ((rc = grow_pinned(s, &rg.pin, &rg.pin_cap, rg.run_need))) return rc;
-    HIP_TRY(hipMemsetAsync(rg.rec, 0, sizeof(uint32_t) * rg.run_need, s->stream));
+    if ((rc = grow_device(s, &r.rec, &r.rec_cap, r.run_need))) return rc;
+    if ((rc = grow_pinned(s, &r.pin, &r.pin_cap, r.run_need))) return rc;
+    HIP_TRY(hipMemsetAsync(r.rec, 0, sizeof(T) * r.run_need, s->stream));
     return OCC_OK;
 }
 // Behind the call's last batch, with the recorded rows: the copy to the page-locked staging buffer
-int regions_copy_out(occ_sampler *s)
+template <class T>
+int record_copy_out(occ_sampler *s, const occ_sampler::CallRecord<T> &r)
 {
-    const occ_sampler::Regions &rg = s->regions;
-    if (rg.run_need) HIP_TRY(hipMemcpyAsync(rg.pin, rg.rec, sizeof(uint32_t) * rg.run_need, hipMemcpyDeviceToHost, s->stream));
+    if (r.run_need) HIP_TRY(hipMemcpyAsync(r.pin, r.rec, sizeof(T) * r.run_need, hipMemcpyDeviceToHost, s->stream));
     return OCC_OK;
 }
-// Clean end of the call (the stream has been waited for): what region_draws answers from now on.  on[c]: chain c's switch
+// Clean end of the call (the stream has been waited for): what the *_draws name answers from now on.  on[c]: chain c's switch
+template <class T>
+void record_close(occ_sampler::CallRecord<T> &r, int64_t keep, const std::vector<uint8_t> &on)
+{
+    if (!r.run_need) return;
+    r.last.assign(r.pin, r.pin + r.run_need);
+    r.last_on = on;
+    r.last_keep = keep;
+}
+int regions_open(occ_sampler *s, int C, int64_t keep)
+{
+    return record_open(s, s->regions, C, keep, (s->outputs_on & OUT_REGION) ? (size_t)s->regions.G : 0);
+}
 void regions_close(occ_sampler *s, int64_t keep, const std::vector<uint8_t> &on)
 {
-    occ_sampler::Regions &rg = s->regions;
-    if (!rg.run_need) return;
-    rg.last.assign(rg.pin, rg.pin + rg.run_need);
-    rg.last_on = on;
-    rg.last_keep = keep;
-    rg.last_G = rg.G;
+    record_close(s->regions, keep, on);
+    s->regions.last_G = s->regions.G;
 }
-
-}  // namespace
-
-// ---- posterior predictive check: the record of one occ_run (logit models) ---------------------------------------------
-namespace {
-
-// regions_open / regions_copy_out / regions_close for the four sums per chain and kept draw
-int ppc_open(occ_sampler *s, int C, int64_t keep, bool *moved)
+// the chains whose `bit` of site_on is set
+std::vector<uint8_t> chains_on(const std::vector<ChainScalars> &h, uint32_t bit)
 {
-    occ_sampler::Ppc &pc = s->ppc;
-    *moved = false;
-    pc.last.clear();
-    pc.last_on.assign((size_t)C, 0);
-    pc.last_keep = 0;
-    pc.run_need = pc.launch ? (size_t)C * (size_t)keep * (size_t)PPC_NCOL : 0;
-    if (!pc.run_need) return OCC_OK;
-    if (pc.run_need > pc.rec_cap) {
-        WAIT_TRY(s->stream);
-        if (pc.rec) HIP_TRY(hipFree(pc.rec));
-        pc.rec = nullptr;
-        pc.rec_cap = 0;
-        HIP_TRY(hipMalloc((void **)&pc.rec, sizeof(unsigned long long) * pc.run_need));
-        pc.rec_cap = pc.run_need;
-        *moved = true;
-    }
-    if (pc.run_need > pc.pin_cap) {
-        WAIT_TRY(s->stream);
-        if (pc.pin) HIP_TRY(hipHostFree(pc.pin));
-        pc.pin = nullptr;
-        pc.pin_cap = 0;
-        const size_t cap = std::max<size_t>(pc.run_need, 4096);
-        HIP_TRY(hipHostMalloc((void **)&pc.pin, sizeof(unsigned long long) * cap, hipHostMallocDefault));
-        pc.pin_cap = cap;
-    }
-    HIP_TRY(hipMemsetAsync(pc.rec, 0, sizeof(unsigned long long) * pc.run_need, s->stream));
-    return OCC_OK;
-}
-int ppc_copy_out(occ_sampler *s)
-{
-    const occ_sampler::Ppc &pc = s->ppc;
-    if (pc.run_need) HIP_TRY(hipMemcpyAsync(pc.pin, pc.rec, sizeof(unsigned long long) * pc.run_need, hipMemcpyDeviceToHost, s->stream));
-    return OCC_OK;
-}
-void ppc_close(occ_sampler *s, int64_t keep, const std::vector<uint8_t> &on)
-{
-    occ_sampler::Ppc &pc = s->ppc;
-    if (!pc.run_need) return;
-    pc.last.assign(pc.pin, pc.pin + pc.run_need);
-    pc.last_on = on;
-    pc.last_keep = keep;
+    std::vector<uint8_t> on(h.size());
+    for (size_t c = 0; c < h.size(); ++c) on[c] = (h[c].site_on & bit) != 0u;
+    return on;
 }
 
 }  // namespace
@@ -1409,7 +1344,7 @@ int pb_launch_role(occ_sampler *s, hipStream_t st, int role)
             }
             break;
         case PB_Z:
-            if (s->regions.launch) {  // (a chain counts the occupied sites per region: the twin, one chain per workgroup)
+            if (s->outputs_on & OUT_REGION) {  // (a chain counts the occupied sites per region: the twin, one chain per workgroup)
                 const PbRegions rg = {s->regions.id_dev, s->regions.pb_on_dev, s->regions.pb_rec, s->regions.G};
                 hipLaunchKernelGGL(k_pb_z_occ, dim3((unsigned)((A.n + PB_WG - 1) / PB_WG), (unsigned)A.C), dim3(PB_WG), 0, st, A, rg);
             } else {
@@ -1606,8 +1541,7 @@ int pb_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, do
     for (PbChain &c : h) { c.rec_first = c.it + (uint32_t)burnin; c.rec_keep = (uint32_t)keep; }
     if ((rc = pb_write_chains(s, h))) return rc;
     HIP_TRY(copy_on(s, A.rec, &s->rec_buf, sizeof(double *), hipMemcpyHostToDevice));
-    bool moved = false;
-    if ((rc = regions_open(s, A.C, keep, &moved))) return rc;
+    if ((rc = regions_open(s, A.C, keep))) return rc;
     if (s->regions.run_need) HIP_TRY(copy_on(s, s->regions.pb_rec, &s->regions.rec, sizeof(uint32_t *), hipMemcpyHostToDevice));
     if (!s->pb_exec) {  // one linear graph of PB_GRAPH_SEQ iterations, captured once (the kernels take nothing that changes)
         HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
@@ -1631,7 +1565,7 @@ int pb_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, do
         ++s->eager_iterations;
     }
     HIP_TRY(hipEventRecord(s->ev1, s->stream));
-    if ((rc = regions_copy_out(s))) return rc;
+    if ((rc = record_copy_out(s, s->regions))) return rc;
     WAIT_TRY(s->stream);
     float ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
@@ -1785,7 +1719,7 @@ int pb_profile(occ_sampler *s, int reps, int64_t counts[OCC_N_KERNEL_KINDS], dou
 {
     for (int k = 0; k < OCC_N_KERNEL_KINDS; ++k) { counts[k] = 0; total_us[k] = 0.0; }
     // (the timing loops launch k_pb_z itself, never the twin that counts the occupied sites per region)
-    ScopedFlags plain_z(&s->regions.launch, false);
+    Scoped<uint32_t> plain_z(&s->outputs_on, 0u);
     std::vector<PbChain> saved;
     int rc = pb_read_chains(s, saved);
     if (rc) return rc;
@@ -2702,9 +2636,9 @@ static int finish_marks(occ_sampler *s, bool last, size_t n_rec)
     const int grc = grow_pinned(s, &s->pin_rec, &s->pin_rec_cap, n_rec);
     if (grc) return grc;
     if (n_rec) HIP_TRY(hipMemcpyAsync(s->pin_rec, s->rec_buf, sizeof(double) * n_rec, hipMemcpyDeviceToHost, s->stream));
-    const int rrc = regions_copy_out(s);
+    const int rrc = record_copy_out(s, s->regions);
     if (rrc) return rrc;
-    const int prc = ppc_copy_out(s);
+    const int prc = record_copy_out(s, s->ppc);
     if (prc) return prc;
     s->marks_done = true;
     return OCC_OK;
@@ -2719,10 +2653,8 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     const size_t need = (size_t)C * keep * rw;
     int rc = grow_device(s, &s->rec_buf, &s->rec_cap, need);  // (its address lives in the device descriptor)
     if (rc) return rc;
-    bool occ_moved = false;
-    if ((rc = regions_open(s, C, keep, &occ_moved))) return rc;  // (zeroed here, in front of the window: also when the call is re-run)
-    bool ppc_moved = false;
-    if ((rc = ppc_open(s, C, keep, &ppc_moved))) return rc;
+    if ((rc = regions_open(s, C, keep))) return rc;  // (zeroed here, in front of the window: also when the call is re-run)
+    if ((rc = record_open(s, s->ppc, C, keep, (s->outputs_on & OUT_PPC) ? (size_t)PPC_NCOL : 0))) return rc;
     if (c.rec != s->rec_buf || c.occ_rec != s->regions.rec || c.ppc_rec != s->ppc.rec) {
         c.rec = s->rec_buf;
         c.occ_rec = s->regions.rec;
@@ -2862,12 +2794,8 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     s->clean_exit = true;
 
     split_rows(s->pin_rec, C, keep, q, p, out_alpha, out_beta, out_tau);
-    std::vector<uint8_t> occ_on((size_t)C, 0);
-    for (int ch = 0; ch < C; ++ch) occ_on[(size_t)ch] = (h[ch].site_on & REGION_BIT) ? 1 : 0;
-    regions_close(s, keep, occ_on);
-    std::vector<uint8_t> ppc_on((size_t)C, 0);
-    for (int ch = 0; ch < C; ++ch) ppc_on[(size_t)ch] = (h[ch].site_on & PPC_BIT) ? 1 : 0;
-    ppc_close(s, keep, ppc_on);
+    regions_close(s, keep, chains_on(h, OUT_REGION));
+    record_close(s->ppc, keep, chains_on(h, OUT_PPC));
     return OCC_OK;
 }
 
@@ -3059,10 +2987,41 @@ static int sums_refused(occ_sampler *s, const SumsKind &k)
     return set_error(s, OCC_E_STATE, (std::string(k.what) + " are not available for the probit model").c_str());
 }
 
+// One chain's switch of one output goes on or off, in the scalars `h` the caller has read (probit handle: in regions.pb_on;
+// `h` is not used).  Writes them, recomputes occ_sampler::outputs_on, and drops the captured graphs, which the choice of
+// kernel is baked into, if the level that must run changed.  Validation, allocation and the wait for the side stream are
+// the caller's, in front of this.
+static int flip_output(occ_sampler *s, std::vector<ChainScalars> &h, int chain, uint32_t bit, bool on)
+{
+    const int level_before = s->z_ob_kind();
+    s->outputs_on = 0u;
+    if (s->probit) {
+        std::vector<uint32_t> &pb_on = s->regions.pb_on;
+        pb_on[(size_t)chain] = on;
+        HIP_TRY(copy_on(s, s->regions.pb_on_dev, pb_on.data(), sizeof(uint32_t) * pb_on.size(), hipMemcpyHostToDevice));
+        for (uint32_t o : pb_on) s->outputs_on |= o ? bit : 0u;
+    } else {
+        h[(size_t)chain].site_on = (h[(size_t)chain].site_on & ~bit) | (on ? bit : 0u);
+        const int rc = write_scalars(s, h);
+        if (rc) return rc;
+        for (const ChainScalars &sc : h) s->outputs_on |= sc.site_on;
+    }
+    if (s->z_ob_kind() == level_before) return OCC_OK;
+    if (!s->probit) {
+        destroy_graph(s);
+        return OCC_OK;
+    }
+    if (s->pb_exec) (void)hipGraphExecDestroy(s->pb_exec);
+    if (s->pb_graph) (void)hipGraphDestroy(s->pb_graph);
+    s->pb_exec = nullptr;
+    s->pb_graph = nullptr;
+    return OCC_OK;
+}
+
 // occ_set_state of those names.  The switch = 1: allocate at first use, zero the chain's sums and count, switch on;
 // 0: switch off (the sums stay readable).  The sums and the count themselves (checkpoint restore): only while the switch is on.
-// Which z kernel is launched follows "is any chain on", kind by kind (occ_sampler::z_ob_kind); a change of kernel drops the
-// captured graphs (rebuilt by the next occ_run).  The kinds' switches are independent of each other.
+// Which z kernel is launched follows "is any chain on" (flip_output); a change of kernel drops the captured graphs (rebuilt
+// by the next occ_run).  The kinds' switches are independent of each other.
 // Nothing of the chain's state changes: omega_b of the coming iteration is NOT redrawn.
 static int set_site_state(occ_sampler *s, int chain, int kind, int field, const double *in, int64_t len)
 {
@@ -3098,14 +3057,7 @@ static int set_site_state(occ_sampler *s, int chain, int kind, int field, const 
         for (int q = 0; q < k.nacc; ++q) HIP_TRY(fill_on(s, c.*k.acc + (size_t)q * Cn + chain * n, 0, sizeof(double) * n));
         HIP_TRY(fill_on(s, c.*k.count + chain, 0, sizeof(double)));
     }
-    h[chain].site_on = (h[chain].site_on & ~k.bit) | (on ? k.bit : 0u);
-    if ((rc = write_scalars(s, h))) return rc;
-    uint32_t any = 0u;
-    for (const auto &sc : h) any |= sc.site_on;
-    const int z_ob_before = s->z_ob_kind();
-    for (int j = 0; j < N_SUMS; ++j) s->sums[j].launch = (any & SUMS[j].bit) != 0u;
-    if (s->z_ob_kind() != z_ob_before) destroy_graph(s);
-    return OCC_OK;
+    return flip_output(s, h, chain, k.bit, on);
 }
 
 // ---- occ_get_state / occ_set_state of the region names (both models) --------------------------------------------------
@@ -3113,12 +3065,12 @@ static int set_site_state(occ_sampler *s, int chain, int kind, int field, const 
 // (at least 1); set only while no chain counts; allocates at first use.  region_stats (1): the chain's switch, 0 or 1.
 // region_draws (keep G, read-only): the chain's counts of the last completed occ_run, row-major [t][g]; length 0 if its
 // switch was off during that call.  Before the first region_id every name answers OCC_E_STATE.  Nothing of a chain's state
-// changes: nothing is redrawn.  Which z kernel is launched follows "is any chain on" (occ_sampler::z_ob_kind): a change
+// changes: nothing is redrawn.  Which z kernel is launched follows "is any chain on" (flip_output): a change
 // drops the captured graphs.
 enum : int { REGION_NONE = -1, REGION_ID = 0, REGION_SWITCH = 1, REGION_DRAWS = 2 };
 static int region_field(const std::string &nm)
 {
-    return nm == "region_id" ? REGION_ID : nm == "region_stats" ? REGION_SWITCH : nm == "region_draws" ? REGION_DRAWS : REGION_NONE;
+    return nm == "region_id" ? REGION_ID : nm == output_of(OUT_REGION).sw ? REGION_SWITCH : nm == "region_draws" ? REGION_DRAWS : REGION_NONE;
 }
 static int regions_unset(occ_sampler *s)
 {
@@ -3135,7 +3087,7 @@ static int region_switches(occ_sampler *s, std::vector<uint8_t> &on, std::vector
     std::vector<ChainScalars> h;
     const int rc = read_scalars(s, h);
     if (rc) return rc;
-    for (size_t c = 0; c < on.size(); ++c) on[c] = (h[c].site_on & REGION_BIT) != 0u;
+    on = chains_on(h, OUT_REGION);
     if (scalars) scalars->swap(h);
     return OCC_OK;
 }
@@ -3203,28 +3155,8 @@ static int set_region_state(occ_sampler *s, int chain, int field, const double *
     }
     if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
     if (in[0] != 0.0 && in[0] != 1.0) return set_error(s, OCC_E_BADARG, "region_stats is 0 or 1");
-    on[(size_t)chain] = in[0] != 0.0;
-    bool any = false;
-    for (uint8_t o : on) any = any || o;
     WAIT_TRY(s->side);
-    if (s->probit) {
-        rg.pb_on[(size_t)chain] = on[(size_t)chain];
-        HIP_TRY(copy_on(s, rg.pb_on_dev, rg.pb_on.data(), sizeof(uint32_t) * rg.pb_on.size(), hipMemcpyHostToDevice));
-        if (any != rg.launch) {  // (the choice of kernel is baked into the captured graph)
-            if (s->pb_exec) (void)hipGraphExecDestroy(s->pb_exec);
-            if (s->pb_graph) (void)hipGraphDestroy(s->pb_graph);
-            s->pb_exec = nullptr;
-            s->pb_graph = nullptr;
-        }
-        rg.launch = any;
-        return OCC_OK;
-    }
-    h[chain].site_on = (h[chain].site_on & ~REGION_BIT) | (on[(size_t)chain] ? REGION_BIT : 0u);
-    if ((rc = write_scalars(s, h))) return rc;
-    const int z_ob_before = s->z_ob_kind();
-    rg.launch = any;
-    if (s->z_ob_kind() != z_ob_before) destroy_graph(s);
-    return OCC_OK;
+    return flip_output(s, h, chain, OUT_REGION, in[0] != 0.0);
 }
 
 // ---- occ_get_state / occ_set_state of the predictive check's names (logit models) -------------------------------------
@@ -3232,9 +3164,9 @@ static int set_region_state(occ_sampler *s, int chain, int field, const double *
 // the chain's rows of the last completed occ_run as doubles, columns 0 and 1 times 2^-32 (exact below 2^53 quanta,
 // otherwise rounded to nearest); length 0 if its switch was off during that call.  Before the first switch-on both names
 // answer OCC_E_STATE.  Nothing of a chain's state changes: nothing is redrawn.  Which z kernel is launched follows "is any
-// chain on" (occ_sampler::z_ob_kind): a change drops the captured graphs.
+// chain on" (flip_output): a change drops the captured graphs.
 enum : int { PPC_NONE = -1, PPC_SWITCH = 0, PPC_DRAWS = 1 };
-static int ppc_field(const std::string &nm) { return nm == "ppc_stats" ? PPC_SWITCH : nm == "ppc_draws" ? PPC_DRAWS : PPC_NONE; }
+static int ppc_field(const std::string &nm) { return nm == output_of(OUT_PPC).sw ? PPC_SWITCH : nm == "ppc_draws" ? PPC_DRAWS : PPC_NONE; }
 static int ppc_refused(occ_sampler *s)
 {
     if (s->probit) return set_error(s, OCC_E_STATE, "posterior predictive checks are not available for the probit model");
@@ -3248,7 +3180,7 @@ static int get_ppc_state(occ_sampler *s, int chain, int field, std::vector<doubl
         std::vector<ChainScalars> h;
         const int rc = read_scalars(s, h);
         if (rc) return rc;
-        v.assign(1, (h[chain].site_on & PPC_BIT) ? 1.0 : 0.0);
+        v.assign(1, (h[chain].site_on & OUT_PPC) ? 1.0 : 0.0);
         return OCC_OK;
     }
     v.clear();
@@ -3271,14 +3203,8 @@ static int set_ppc_state(occ_sampler *s, int chain, int field, const double *in,
     int rc;
     if ((rc = read_scalars(s, h))) return rc;
     WAIT_TRY(s->side);
-    h[chain].site_on = (h[chain].site_on & ~PPC_BIT) | (in[0] != 0.0 ? PPC_BIT : 0u);
-    if ((rc = write_scalars(s, h))) return rc;
-    bool any = false;
-    for (const ChainScalars &sc : h) any = any || (sc.site_on & PPC_BIT);
-    const int z_ob_before = s->z_ob_kind();
-    pc.launch = any;
+    if ((rc = flip_output(s, h, chain, OUT_PPC, in[0] != 0.0))) return rc;
     pc.ready = true;
-    if (s->z_ob_kind() != z_ob_before) destroy_graph(s);
     return OCC_OK;
 }
 
@@ -3537,9 +3463,7 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     if (s->probit) return pb_profile(s, reps, counts, total_us);
     // (the timing loops always launch k_z_ob itself, never the twin that keeps the per-site sums; no captured graph of the
     // handle is replayed here)
-    ScopedFlags plain_z_ob(&s->regions.launch, false);
-    plain_z_ob.set(&s->ppc.launch, false);
-    for (int k = 0; k < N_SUMS; ++k) plain_z_ob.set(&s->sums[k].launch, false);
+    Scoped<uint32_t> plain_z_ob(&s->outputs_on, 0u);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops
     if (rc) return rc;
     // The fused iteration kernel first, IN SITU: `reps` real iterations continue the chains from where they are
@@ -3557,7 +3481,7 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
         const bool one_stream = std::getenv("OCC_EAGER_ONLY") != nullptr || !s->plan.side_enabled;
         const bool flags = s->run.flag_sync && !one_stream;
         const bool ev = !flags && !one_stream;
-        ScopedFlags in_situ(&s->launch_sync, flags);
+        Scoped<bool> in_situ(&s->launch_sync, flags);
         if (ev) HIP_TRY(hipEventRecord(s->ev_z[s->parity ^ 1], s->stream));
         hipEvent_t pev[2] = {nullptr, nullptr};
         HIP_TRY(hipEventCreate(&pev[0]));
@@ -3606,7 +3530,7 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     const int e = s->parity;
     double us = 0.0;
     // the kernels below are replayed out of sequence: no waits, no counter updates
-    ScopedFlags no_sync(&s->launch_sync, false);
+    Scoped<bool> no_sync(&s->launch_sync, false);
     auto timed = [&](int kind, int extra) -> int {
         int r = time_kernel_graph(s, kind, reps, e, extra, &us);
         counts[kind] = reps;

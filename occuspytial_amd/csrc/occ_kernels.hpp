@@ -111,9 +111,9 @@ struct ChainScalars {
     uint32_t bar_base;         // arrivals counted so far by the chain's barrier counter (occ_iter.hpp), never reset
     int32_t err;               // OCC_E_* raised on device
     int32_t minres_itn_last;
-    uint32_t site_on;          // bit 0: per-site posterior sums (Ctx::site_acc) are kept for this chain; bit 1: the log-likelihood
-                               // sums (Ctx::ll_acc); bit 2: the occupied sites per region and draw (Ctx::occ_rec); bit 3: the
-                               // posterior predictive check (Ctx::ppc_rec); sits where the layout had padding
+    uint32_t site_on;          // OUT_SITE: per-site posterior sums (Ctx::site_acc) are kept for this chain; OUT_LL: the log-likelihood
+                               // sums (Ctx::ll_acc); OUT_REGION: the occupied sites per region and draw (Ctx::occ_rec); OUT_PPC: the
+                               // posterior predictive check (Ctx::ppc_rec) -- occ_plan.hpp; sits where the layout had padding
     unsigned long long krylov_total, krylov_sq_total, solves, carries;
 };
 
@@ -2059,12 +2059,12 @@ __global__ void __launch_bounds__(512) k_alpha_draw(OCC_KARGS, int sync_on)
 
 // Last kernel of a launch sequence.  Every wave first draws beta ~ N(A^-1 r, A^-1) from the partial sums
 // of k_beta_partial (logit.py:232, distributions.pyx:42-110; redundantly, in registers -- cheaper than a
-// kernel of its own).  Blocks [0, nb_n): z update of the current iteration (logit.py:234-252), record
-// (alpha, beta, tau) (base.py:238-239), hand the control word to the next sequence.  Blocks [nb_n, 2 nb_n):
-// omega_b of the NEXT iteration, which needs only beta and eta of this one -- one launch, two independent
-// roles, so the two run concurrently without a second stream.
-// The z update of one site (logit.py:234-252) and the record of one iteration (base.py:238-239): shared by k_z_ob
-// and by the last phase of k_iter (occ_iter.hpp), contractions explicit so that both evaluate the same operations.
+// kernel of its own).  The two roles alternate by block parity (z_ob_body).  Even blocks: z update of the current
+// iteration (logit.py:234-252), record (alpha, beta, tau) (base.py:238-239); block 0 hands the control word to the
+// next sequence.  Odd blocks: omega_b of the NEXT iteration, which needs only beta and eta of this one -- one launch,
+// two independent roles, so the two run concurrently without a second stream.
+// The z update of one site (logit.py:234-252) and the record of one iteration (base.py:238-239): shared by the five
+// k_z_ob families and k_cond_beta_z, contractions explicit so that all evaluate the same operations.
 // One iteration's terms of the per-site sums (Ctx::site_acc): the site's own thread, plain read-modify-writes in iteration
 // order -- the sums do not depend on block size, path or placement.  (eta^2 enters by one fused multiply-add, stated.)
 enum : int { SITE_PSI = 0, SITE_OCC = 1, SITE_Z = 2, SITE_ETA = 3, SITE_ETA2 = 4, SITE_NACC = 5 };
@@ -2254,7 +2254,7 @@ __device__ __forceinline__ void region_count(uint32_t *__restrict__ row, int G, 
 __device__ __forceinline__ uint32_t *region_row(const Ctx &c, const ChainScalars &sc, int chain, uint32_t it)
 {
     const uint32_t rel = it - sc.it_base;
-    if (!(sc.site_on & 4u) || c.occ_rec == nullptr || rel < sc.burnin || rel - sc.burnin >= sc.keep) return nullptr;
+    if (!(sc.site_on & OUT_REGION) || c.occ_rec == nullptr || rel < sc.burnin || rel - sc.burnin >= sc.keep) return nullptr;
     return c.occ_rec + ((size_t)chain * sc.keep + (rel - sc.burnin)) * (size_t)c.region_G;
 }
 
@@ -2315,7 +2315,7 @@ __device__ __forceinline__ void ppc_count(unsigned long long *__restrict__ row, 
 __device__ __forceinline__ unsigned long long *ppc_row(const Ctx &c, const ChainScalars &sc, int chain, uint32_t it)
 {
     const uint32_t rel = it - sc.it_base;
-    if (!(sc.site_on & 8u) || c.ppc_rec == nullptr || rel < sc.burnin || rel - sc.burnin >= sc.keep) return nullptr;
+    if (!(sc.site_on & OUT_PPC) || c.ppc_rec == nullptr || rel < sc.burnin || rel - sc.burnin >= sc.keep) return nullptr;
     return c.ppc_rec + ((size_t)chain * sc.keep + (rel - sc.burnin)) * (size_t)PPC_NCOL;
 }
 // The z update of one site of a chain and iteration whose detections are replicated (ppc_row is not null): z_update_site
@@ -2524,7 +2524,7 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
         // the two kinds of sums, the region counts and the predictive check, each where the chain's bit is on.  As below, no
         // thread leaves before the barriers of the two reductions, and `row` / `prow` are uniform over the workgroup
         const uint32_t on = sc.site_on;
-        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & OUT_SITE) && kept, ll_on = (on & OUT_LL) && kept;
         if (debug_skip & 1) return;
         if (writer && stats_on) c.site_count[chain] += 1.0;
         if (writer && ll_on) c.ll_count[chain] += 1.0;
@@ -2562,7 +2562,7 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
         // the two kinds of sums and the region counts, each where the chain's bit is on.  No thread leaves before the
         // counts' barriers: one past n, or of a site with a detection, comes back from the update with its z
         const uint32_t on = sc.site_on;
-        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & OUT_SITE) && kept, ll_on = (on & OUT_LL) && kept;
         if (debug_skip & 1) return;
         if (writer && stats_on) c.site_count[chain] += 1.0;
         if (writer && ll_on) c.ll_count[chain] += 1.0;
@@ -2574,7 +2574,7 @@ __device__ __forceinline__ void z_ob_body(const Ctx &c, ChainScalars *__restrict
     } else if constexpr (STATS == 2) {
         // both kinds of sums, each where the chain's bit is on: the same iterations count for either
         const uint32_t on = sc.site_on;
-        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & OUT_SITE) && kept, ll_on = (on & OUT_LL) && kept;
         if (writer && stats_on && !(debug_skip & 1)) c.site_count[chain] += 1.0;
         if (writer && ll_on && !(debug_skip & 1)) c.ll_count[chain] += 1.0;
         if (i >= n || (debug_skip & 1)) return;
@@ -2685,7 +2685,7 @@ __device__ __forceinline__ void z_ob_body_g(const Ctx &c, ChainScalars *__restri
     const int n = c.n, i = (blk >> 1) * blockDim.x + threadIdx.x;
     if constexpr (STATS == 4) {
         const uint32_t on = sc.site_on;
-        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & OUT_SITE) && kept, ll_on = (on & OUT_LL) && kept;
         if (debug_skip & 1) return;
         if (writer && stats_on) c.site_count[chain] += 1.0;
         if (writer && ll_on) c.ll_count[chain] += 1.0;
@@ -2718,7 +2718,7 @@ __device__ __forceinline__ void z_ob_body_g(const Ctx &c, ChainScalars *__restri
         if (prow != nullptr) ppc_count(prow, term);
     } else if constexpr (STATS == 3) {
         const uint32_t on = sc.site_on;
-        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & OUT_SITE) && kept, ll_on = (on & OUT_LL) && kept;
         if (debug_skip & 1) return;
         if (writer && stats_on) c.site_count[chain] += 1.0;
         if (writer && ll_on) c.ll_count[chain] += 1.0;
@@ -2729,7 +2729,7 @@ __device__ __forceinline__ void z_ob_body_g(const Ctx &c, ChainScalars *__restri
         if (row != nullptr) region_count(row, c.region_G, g, zi);
     } else if constexpr (STATS == 2) {
         const uint32_t on = sc.site_on;
-        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & 1u) && kept, ll_on = (on & 2u) && kept;
+        const bool kept = it - sc.it_base >= sc.burnin, stats_on = (on & OUT_SITE) && kept, ll_on = (on & OUT_LL) && kept;
         if (writer && stats_on && !(debug_skip & 1)) c.site_count[chain] += 1.0;
         if (writer && ll_on && !(debug_skip & 1)) c.ll_count[chain] += 1.0;
         if (i >= n || (debug_skip & 1)) return;
@@ -2783,6 +2783,7 @@ __global__ void __launch_bounds__(256) k_beta_draw(OCC_KARGS)
     }
 }
 
+// Launched while no chain of the handle has an output on (level 0 of occ_plan.hpp's OUTPUTS).
 // (three workgroups per CU: at two -- no spilled registers -- k_z_ob takes 19 us instead of 14 at the headline and 76 instead of 61
 // at 500x500, measured in round 4 with the new sampler as in round 2 with the old one)
 template <int P>
@@ -2800,8 +2801,9 @@ __global__ void __launch_bounds__(256, 3) k_z_ob(OCC_KARGS, int flags)  // bit 0
     }
 }
 
-// k_z_ob with the per-site posterior sums (Ctx::site_acc): launched in k_z_ob's place while a chain of the handle has its
-// switch on.  A kernel of its own, so that k_z_ob itself -- register-sensitive, see above -- stays the code it was.
+// k_z_ob with the per-site posterior sums (Ctx::site_acc): launched in k_z_ob's place while a chain of the handle has
+// OUT_SITE on (level 1 of occ_plan.hpp's OUTPUTS).  A kernel of its own, so that k_z_ob itself -- register-sensitive, see
+// above -- stays the code it was.
 template <int P>
 __global__ void __launch_bounds__(256, 3) k_z_ob_stats(OCC_KARGS, int flags)  // flags: k_z_ob's
 {
@@ -2817,7 +2819,7 @@ __global__ void __launch_bounds__(256, 3) k_z_ob_stats(OCC_KARGS, int flags)  //
 }
 
 // k_z_ob with the log-likelihood sums of streaming WAIC (Ctx::ll_acc) AND the per-site posterior sums, each for the chains
-// whose bit of ChainScalars::site_on is set: launched in k_z_ob's place while a chain of the handle has bit 1 on.  A third
+// whose bit of ChainScalars::site_on is set: launched in k_z_ob's place while a chain of the handle has OUT_LL on.  A third
 // kernel family, so that k_z_ob and k_z_ob_stats stay the code they were.
 template <int P>
 __global__ void __launch_bounds__(256, 3) k_z_ob_ll(OCC_KARGS, int flags)  // flags: k_z_ob's
@@ -2835,7 +2837,7 @@ __global__ void __launch_bounds__(256, 3) k_z_ob_ll(OCC_KARGS, int flags)  // fl
 
 // k_z_ob with the occupied sites per region and draw (Ctx::occ_rec), the log-likelihood sums and the per-site posterior sums,
 // each for the chains whose bit of ChainScalars::site_on is set: launched in k_z_ob's place while a chain of the handle has
-// bit 2 on.  A fourth kernel family, so that the three above stay the code they were.
+// OUT_REGION on.  A fourth kernel family, so that the three above stay the code they were.
 template <int P>
 __global__ void __launch_bounds__(256, 3) k_z_ob_occ(OCC_KARGS, int flags)  // flags: k_z_ob's
 {
@@ -2852,7 +2854,7 @@ __global__ void __launch_bounds__(256, 3) k_z_ob_occ(OCC_KARGS, int flags)  // f
 
 // k_z_ob with the posterior predictive check of the detection histories (Ctx::ppc_rec), the occupied sites per region, the
 // log-likelihood sums and the per-site posterior sums, each for the chains whose bit of ChainScalars::site_on is set:
-// launched in k_z_ob's place while a chain of the handle has bit 3 on.  A fifth kernel family, so that the four above stay
+// launched in k_z_ob's place while a chain of the handle has OUT_PPC on.  A fifth kernel family, so that the four above stay
 // the code they were.
 template <int P>
 __global__ void __launch_bounds__(256, 3) k_z_ob_ppc(OCC_KARGS, int flags)  // flags: k_z_ob's

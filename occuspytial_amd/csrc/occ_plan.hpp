@@ -368,4 +368,26 @@ constexpr SeqParts seq_parts(SeqMode m, SeqWhere w)
 // with omega_a / alpha moved up front -- stream order is the synchronisation
 constexpr SeqParts seq_eager() { return SeqParts{3, {PART_SIDE, PART_SOLVE, PART_TAIL}}; }
 
+// ---- the z update's optional OUTPUTS ---------------------------------------------------------------------------------
+// Each is switched per chain by a state name and is a bit of ChainScalars::site_on.  Its LEVEL is the STATS value of the
+// kernel family that serves it where k_z_ob stands (0: k_z_ob itself); a family also serves every output below its own.
+// probit: the probit model has the output too.  tests/test_outputs_cpu.py pins the table and output_level.
+constexpr uint32_t OUT_SITE = 1u, OUT_LL = 2u, OUT_REGION = 4u, OUT_PPC = 8u;
+struct Output { uint32_t bit; int level; const char *sw; bool probit; };
+constexpr int N_OUTPUTS = 4;
+constexpr Output OUTPUTS[N_OUTPUTS] = {{OUT_SITE, 1, "site_stats", false},      // per-site posterior sums: k_z_ob_stats
+                                       {OUT_LL, 2, "ll_stats", false},          // log-likelihood sums of streaming WAIC: k_z_ob_ll
+                                       {OUT_REGION, 3, "region_stats", true},   // occupied sites per region and draw: k_z_ob_occ
+                                       {OUT_PPC, 4, "ppc_stats", false}};       // posterior predictive check: k_z_ob_ppc
+constexpr const Output &output_of(uint32_t bit) { return OUTPUTS[bit == OUT_SITE ? 0 : bit == OUT_LL ? 1 : bit == OUT_REGION ? 2 : 3]; }
+static_assert(output_of(OUT_SITE).bit == OUT_SITE && output_of(OUT_LL).bit == OUT_LL && output_of(OUT_REGION).bit == OUT_REGION && output_of(OUT_PPC).bit == OUT_PPC, "output_of");
+// The level that must run while the OR of every chain's site_on is `on`: the highest whose bit is set (unknown bits: none)
+constexpr int output_level(uint32_t on)
+{
+    int level = 0;
+    for (int k = 0; k < N_OUTPUTS; ++k)
+        if ((on & OUTPUTS[k].bit) && OUTPUTS[k].level > level) level = OUTPUTS[k].level;
+    return level;
+}
+
 }  // namespace occ

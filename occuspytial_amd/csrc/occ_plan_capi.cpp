@@ -1,5 +1,6 @@
-// occ_plan_capi.cpp -- the planner and the launch order (occ_plan.hpp) and the problem layout (occ_layout.hpp) behind C entry
-// points for tests/test_plan_cpu.py, tests/test_order_cpu.py and tests/test_layout_cpu.py (ctypes).  Test infrastructure:
+// occ_plan_capi.cpp -- the planner, the launch order and the z update's outputs (occ_plan.hpp) and the problem layout
+// (occ_layout.hpp) behind C entry points for tests/test_plan_cpu.py, tests/test_order_cpu.py, tests/test_outputs_cpu.py and
+// tests/test_layout_cpu.py (ctypes).  Test infrastructure:
 // `make plan` builds it with g++ into build/; it is never linked into libocc_gibbs.so.
 #include <cstdio>
 #include <cstring>
@@ -75,6 +76,16 @@ int32_t occ_order_launches(int32_t mode, int32_t where, int32_t solve, int32_t p
         }
     return n <= max ? n : -1;
 }
+
+// The z update's outputs (OUTPUTS): how many; row k's bit with its level, switch name and whether the probit model has it;
+// the level that runs while the OR of the chains' site_on is `on`.
+int32_t occ_output_count(void) { return N_OUTPUTS; }
+uint32_t occ_output_row(int32_t k, int32_t *level, const char **sw, int32_t *probit)
+{
+    *level = OUTPUTS[k].level; *sw = OUTPUTS[k].sw; *probit = OUTPUTS[k].probit;
+    return OUTPUTS[k].bit;
+}
+int32_t occ_output_level(uint32_t on) { return output_level(on); }
 
 // The layout of a logit problem, by build_layout's steps in its order (occ_gibbs.hip), plus the probit model's row_t.
 // A handle for occ_layout_array / occ_layout_peer, or null with the refusal in err.
