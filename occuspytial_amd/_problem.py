@@ -97,10 +97,19 @@ class FlatProblem:
         self.probit = None   # set by enable_probit(): ProbitRSRGibbs (the reduced-rank basis plus its eigenvectors)
 
     # ---- reduced-rank spatial effects (reference gibbs/logit.py:413-460) --------------------------------
-    def enable_rsr(self, r=0.5, q=None, default_tau_shape=True):
+    def enable_rsr(self, r=0.5, q=None, default_tau_shape=True, basis='host', device=0):
         """Moran-operator basis ``K`` (n x m) of the reference's ``_configure_rsr``, the reduced precision
         ``K'QK`` and its eigenfactor ``E`` (``E E' = K'QK``, ``_EtaRSRPosterior.__init__``).  ``q`` fixes the
-        number of columns, else eigenvalues ``>= r`` are kept.  Dense n x n linear algebra on the host, once."""
+        number of columns, else eigenvalues ``>= r`` are kept.  ``basis='host'``: dense n x n linear algebra on the host,
+        once.  ``basis='device'``: the same eigenvectors by a filtered block subspace iteration on HIP device ``device``
+        (``occuspytial_amd.basis.moran_basis``), with no n x n array; K's columns are then defined up to sign and up to a
+        rotation inside a cluster of near-equal eigenvalues -- the model depends on span(K) alone."""
+        if basis not in ('host', 'device'):
+            raise ValueError("basis must be 'host' or 'device'")
+        if basis == 'device':
+            from .basis import moran_basis
+            K = moran_basis(self.Q, self.X, r=r, q=q, device=device)
+            return self._set_rsr(K, default_tau_shape)
         X = self.X
         chol = np.linalg.cholesky(X.T @ X)
         zi = solve_triangular(chol, np.eye(self.p), lower=True)
@@ -121,7 +130,10 @@ class FlatProblem:
             if not m:
                 raise ValueError('The Moran Operator Matrix of the data has no positive '
                                  'eigenvalues. Set threshold to a lower value')
-        K = np.ascontiguousarray(v[:, -m:])
+        return self._set_rsr(np.ascontiguousarray(v[:, -m:]), default_tau_shape)
+
+    def _set_rsr(self, K, default_tau_shape):
+        m = K.shape[1]
         Qr = np.ascontiguousarray(K.T @ (self.Q @ K))
         s, u = np.linalg.eigh(Qr)
         E = np.ascontiguousarray(u * np.sqrt(np.clip(s, 0.0, None)))
@@ -132,13 +144,13 @@ class FlatProblem:
             self.hparams['tau_shape'] = self.tau_shape
         return self.rsr
 
-    def enable_probit(self, r=0.5, q=None, default_tau_shape=True):
+    def enable_probit(self, r=0.5, q=None, default_tau_shape=True, basis='host', device=0):
         """The probit model's basis (ProbitRSRGibbs): the reference's K, ``Qr = K'QK`` and ``KTK = K'K`` -- its
         ``_configure`` computes the same K as ``LogitRSRGibbs`` -- plus what makes the device's theta update factor-free:
         the generalized eigenvectors ``G`` of ``Qr G = KTK G diag(lam)`` with ``G' KTK G = I`` (``lam < 0`` from rounding
         clamped to 0) and ``Phi = K G``.  Then ``(KTK + tau Qr)^-1 = G diag(1 / (1 + tau lam)) G'``."""
         from scipy.linalg import eigh
-        rsr = self.enable_rsr(r=r, q=q, default_tau_shape=default_tau_shape)
+        rsr = self.enable_rsr(r=r, q=q, default_tau_shape=default_tau_shape, basis=basis, device=device)
         K = rsr['K']
         KTK = K.T @ K
         lam, G = eigh(rsr['Q'], KTK)

@@ -322,15 +322,19 @@ class LogitRSRGibbs(LogitICARGibbs):
     n x n linear algebra, once (as the reference does); per iteration the device forms
     :math:`K^\top\Omega K + \tau K^\top QK` and solves the q x q system (``csrc/occ_rsr.hpp``: in LDS and registers up to
     128 basis columns, panel by panel in device memory up to 4096 -- the reference's default threshold keeps about 13 % of a
-    lattice's sites: 1 280 columns at 100x100).  ``device`` selects the HIP device.
+    lattice's sites: 1 280 columns at 100x100).  ``device`` selects the HIP device.  ``basis='device'`` builds the basis on
+    that device too, without any n x n array (``occuspytial_amd.basis.moran_basis``): the same span, columns defined up to sign
+    and up to a rotation inside a cluster of near-equal eigenvalues; any value but ``'host'`` and ``'device'`` is refused.
     """
 
-    def __init__(self, Q, W, X, y, hparams=None, random_state=None, r=0.5, q=None, device=0, devices=None):
+    def __init__(self, Q, W, X, y, hparams=None, random_state=None, r=0.5, q=None, device=0, devices=None, basis='host'):
+        if basis not in ('host', 'device'):
+            raise ValueError("basis must be 'host' or 'device'")
         super().__init__(Q, W, X, y, hparams, random_state, device=device, devices=devices, prior_draw='edge')
-        self._configure_rsr(r, q, hparams)
+        self._configure_rsr(r, q, hparams, basis)
 
-    def _configure_rsr(self, r, q, hparams):
-        rsr = self._problem.enable_rsr(r=r, q=q, default_tau_shape=not hparams)
+    def _configure_rsr(self, r, q, hparams, basis='host'):
+        rsr = self._problem.enable_rsr(r=r, q=q, default_tau_shape=not hparams, basis=basis, device=self.device)
         if rsr['dim'] > 4096:
             raise ValueError(f'{rsr["dim"]} basis columns selected; the device path supports at most 4096 '
                              '(raise the threshold `r` or pass `q`)')

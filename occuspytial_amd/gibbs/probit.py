@@ -26,21 +26,25 @@ class ProbitRSRGibbs(GibbsBase):
     (:math:`\omega_b, \tau, \epsilon, \theta, \beta, \omega_a, \alpha, z`); the beta precision is never overwritten and the
     truncated normals are drawn stably for any location.  Per iteration the device makes two passes over one n x m matrix
     and no factorisation (``csrc/occ_probit.hpp``).  ``device`` selects the HIP device; the chains of one ``sample`` call run
-    batched on it.  At most 4 096 basis columns and 8 covariates of each kind.
+    batched on it.  At most 4 096 basis columns and 8 covariates of each kind.  ``basis='device'`` builds K on the device
+    without any n x n array (``occuspytial_amd.basis.moran_basis``; the same span, columns defined up to sign and up to a
+    rotation inside a cluster of near-equal eigenvalues); any value but ``'host'`` and ``'device'`` is refused.
     """
 
-    def __init__(self, Q, W, X, y, hparams=None, random_state=None, r=0.5, q=None, device=0):
+    def __init__(self, Q, W, X, y, hparams=None, random_state=None, r=0.5, q=None, device=0, basis='host'):
+        if basis not in ('host', 'device'):
+            raise ValueError("basis must be 'host' or 'device'")
         super().__init__(Q, W, X, y, hparams, random_state)
         self.devices = None
         self.device = device
-        self._configure(Q, hparams, q, r)
+        self._configure(Q, hparams, q, r, basis)
 
-    def _configure(self, Q, hparams, q, r):
+    def _configure(self, Q, hparams, q, r, basis='host'):
         super()._configure(Q, hparams, prior_draw='edge')
         prob = self._problem
         if prob.p > 8 or prob.q > 8:
             raise ValueError('the probit model takes at most 8 occupancy and 8 detection covariates')
-        pb = prob.enable_probit(r=r, q=q, default_tau_shape=not hparams)
+        pb = prob.enable_probit(r=r, q=q, default_tau_shape=not hparams, basis=basis, device=self.device)
         m = pb['dim']
         if m > MAX_BASIS:
             raise ValueError(f'{m} basis columns selected; the device path supports at most {MAX_BASIS} '
