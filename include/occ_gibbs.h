@@ -208,7 +208,32 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  * "posterior predictive checks are not available for the probit model".  Nothing is redrawn; occ_set_start and occ_set_keys
  * do not touch the switch; a call that is re-run after a device-side wait gave up counts nothing twice; occ_step, occ_profile
  * and the occ_cond_* entry points never count.  alpha, beta, tau, eta, z, the site_* and ll_* sums and region_draws are
- * bit-identical with the switch on or off, and the four switches are independent of each other. */
+ * bit-identical with the switch on or off, and the four switches are independent of each other.
+ *
+ * Spatial residual check (logit models; ICAR and reduced rank): did the spatial term absorb the spatial structure?  Per KEPT
+ * draw of occ_run -- row t as above -- of a chain whose switch is on, with beta, eta (reduced rank: K theta) and the NEW z of
+ * the iteration, two kernels launched directly behind the z update form, with weights w_ij = -Q_ij (i != j):
+ *   psi_i = expit(x_i beta + eta_i), as site_psi forms it;   r_i = z_i - psi_i;
+ *   u_i = the uniform of Philox stream 14 (STREAM_SPATIAL) at sub-stream index i, the site, block 0, first 64-bit word: what
+ *         occ_draw(kind 3, key, iteration, 14, n) returns, so a caller can re-draw it;
+ *   z*_i = [u_i < psi_i];   r*_i = z*_i - psi_i;   d_i = sum_j w_ij (column order);   S0 = sum_i d_i;
+ *   A = sum_i r_i sum_j w_ij r_j,   B = sum_i d_i r_i,   C = sum_i r_i,   D = sum_i r_i^2,   and A*, B*, C*, D* of r*.
+ * A row holds eight SIGNED 64-bit integers [A, B, C, D, A*, B*, C*, D*], each the sum over the sites of fx(term) =
+ * llrint(term 2^32), added with integer atomics in two's complement: the same values whatever the path, the placement or the
+ * order of addition.  Moran's I, centred at rbar = C / n:  I = (n / S0) (A - 2 rbar B + rbar^2 S0) / (D - n rbar^2).
+ * Checked at the handle's first switch-on, OCC_E_BADARG otherwise: every off-diagonal of Q <= 0 (a Q that came with a
+ * prior_factor may hold positive ones: refused here), 0 < S0 < 2^30 and n < 2^30, so that every column stays below 2^62.
+ *   moran_stats(1)
+ *       a word of the handle per chain that says whether the chain's kept draws are recorded: 1 or 0, any other value is
+ *       OCC_E_BADARG.  It is not one of the z update's outputs above.  The first 1 allocates (the weights, 16 n bytes per chain).
+ *   moran_draws(keep 8)
+ *       read-only: the chain's rows of the last completed occ_run, row-major [t][column], as doubles multiplied by 2^-32 (exact
+ *       below 2^53 quanta, otherwise rounded to nearest); length 0 if the chain's switch was off during that call.
+ * Both names answer OCC_E_STATE before the handle's first switch-on (switching a chain off before that is accepted), and a
+ * probit handle answers them with OCC_E_STATE, "the spatial residual check is not available for the probit model".  Nothing
+ * is redrawn; occ_set_start and occ_set_keys do not touch it; a call that is re-run after a device-side wait gave up counts
+ * nothing twice; occ_step, occ_profile and the occ_cond_* entry points never count.  alpha, beta, tau, eta, z, the site_* and
+ * ll_* sums, region_draws and ppc_draws are bit-identical with it on or off, and it is independent of the four outputs. */
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len);
 int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double *in, int64_t len);
 
@@ -346,7 +371,8 @@ int occ_cond_z(occ_sampler *s, int32_t chain, const double *u, double *z_out);
  * prior term, 5 beta's normals [coefficient], 6 omega_a [visit row], 7 alpha's normals [coefficient], 8 the uniform of the z
  * update [site], 10 the normals of the reference-form prior draw [column of the factor], 11 and 12 the probit model's eps
  * [site] and coefficient normals [basis column], 13 (STREAM_PPC) the uniform of a replicated detection of the posterior
- * predictive check [flat visit row].
+ * predictive check [flat visit row], 14 (STREAM_SPATIAL) the uniform of a replicated occupancy of the spatial residual check
+ * [site].
  * Errors are reported through occ_last_error(NULL). */
 int occ_draw(int32_t device, int32_t kind, uint64_t key, uint32_t iteration, uint32_t stream, int64_t n, const double *param,
              double *out);

@@ -121,6 +121,8 @@ class Engine:
         self._region_on = False
         # posterior predictive check: the switch; until it is first set, no call about it reaches the library
         self._ppc_on = False
+        # spatial residual check: the switch; until it is first set, no call about it reaches the library
+        self._moran_on = False
         _LIVE.add(self)
         return self
 
@@ -217,6 +219,8 @@ class Engine:
             out['region_stats'] = np.full(self.n_chains, float(self._region_on))
         if self._ppc_on:   # the switch; the draws belong to a call
             out['ppc_stats'] = np.ones(self.n_chains)
+        if self._moran_on:   # likewise
+            out['moran_stats'] = np.ones(self.n_chains)
         return out
 
     def restore(self, ckpt):
@@ -254,6 +258,23 @@ class Engine:
             self.ppc_stats(True)
         elif self._ppc_on:
             self.ppc_stats(False)
+        if 'moran_stats' in ckpt and np.all(np.asarray(ckpt['moran_stats']) != 0):
+            self.moran_stats(True)
+        elif self._moran_on:
+            self.moran_stats(False)
+
+    # ---- spatial residual check (state names moran_*, include/occ_gibbs.h) ----
+    def moran_stats(self, on):
+        """Switch the spatial residual check of every chain.  While on, every kept draw of ``run`` records the sums of
+        Moran's I of the occupancy residuals z - psi and of one replicate of them (:meth:`moran_draws`)."""
+        for c in range(self.n_chains):
+            self.set('moran_stats', 1.0 if on else 0.0, c)
+        self._moran_on = bool(on)
+
+    def moran_draws(self, chain=0):
+        """``(keep, 8)`` rows of one chain from the last ``run`` -- A, B, C, D of the residuals, then of their replicate
+        (``occuspytial_amd.spatial``) -- ``(0, 8)`` if its switch was off during that call."""
+        return self.get('moran_draws', chain).reshape(-1, 8)
 
     # ---- posterior predictive check (state names ppc_*, include/occ_gibbs.h) ----
     def ppc_stats(self, on):
@@ -533,6 +554,19 @@ class EngineGroup:
     def ppc_draws(self, chain=0):
         g, i = self.where[chain]
         return self.engines[g].ppc_draws(i)
+
+    # spatial residual check: the switch on every device, the draws routed by chain
+    @property
+    def _moran_on(self):
+        return any(getattr(e, '_moran_on', False) for e in self.engines)
+
+    def moran_stats(self, on):
+        for e in self.engines:
+            e.moran_stats(on)
+
+    def moran_draws(self, chain=0):
+        g, i = self.where[chain]
+        return self.engines[g].moran_draws(i)
 
     # (the entry points by name are Engine's own: each only names its kind)
     site_stats, site_sums, loglik_stats, loglik_sums = Engine.site_stats, Engine.site_sums, Engine.loglik_stats, Engine.loglik_sums

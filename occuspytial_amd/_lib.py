@@ -24,6 +24,9 @@ REGION_FIELDS = ('region_id', 'region_stats', 'region_draws')
 # the posterior predictive check: the chain's switch, the chain's rows of the last occ_run (keep 4: T_obs, T_rep, replicated
 # detections, replicated sites with a detection)
 PPC_FIELDS = ('ppc_stats', 'ppc_draws')
+# the spatial residual check: the chain's switch (a word of the handle), the chain's rows of the last occ_run (keep 8: the sums
+# A, B, C, D of Moran's I of z - psi, then those of its replicate)
+MORAN_FIELDS = ('moran_stats', 'moran_draws')
 KERNEL_KINDS = ('omega_b', 'noise', 'eta_init', 'minres', 'beta_partial', 'omega_a', 'alpha_draw', 'z_ob', 'iter')
 
 

@@ -23,6 +23,7 @@
 #include "occ_tiles.hpp"
 #include "occ_rsr.hpp"
 #include "occ_probit.hpp"
+#include "occ_spatial.hpp"
 #include "occ_layout.hpp"
 
 using namespace occ;
@@ -166,6 +167,18 @@ struct occ_sampler {
     struct Ppc : CallRecord<unsigned long long> {
         bool ready = false;
     } ppc;
+    // Spatial residual check (state names moran_stats, moran_draws; logit models; occ_spatial.hpp).  ready: a chain has been
+    // switched on once -- the off-diagonal CSR of Q, the residuals' buffer and the switches are on the device.  The switch is a
+    // word of the handle per chain (on, on_dev), not a bit of ChainScalars::site_on; any: their OR, which decides whether the
+    // two kernels are launched behind the z update (baked into captured graphs: a change drops them).  The record's width is
+    // the SP_NCOL signed integer sums; args: the kernels' argument block (its `rec` follows the record).
+    struct Spatial : CallRecord<long long> {
+        bool ready = false;
+        uint32_t any = 0u;
+        std::vector<uint32_t> on;
+        uint32_t *on_dev = nullptr;
+        SpArgs args{};
+    } spatial;
     std::vector<ChainScalars> snap_sc;
     // fixed problem arrays on the device, in upload order: what a group broadcasts from its root (occ_create_group /
     // occ_create_distributed); defer_fixed: allocate only, the bytes arrive by broadcast
@@ -625,6 +638,8 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
                 hipLaunchKernelGGL(z_ob, dim3((unsigned)c.nb_n * 2, (unsigned)c.C), blk, 0, st, OCC_ARGS,
                                    (s->launch_sync ? 1 : 0) | P.zob_flags | (P.beta_split ? 4 : 0));
             }
+            if (s->spatial.any)  // the spatial residual check, directly behind the z update: stream order is the synchronisation
+                sp_launch(s->spatial.args, s->ctx.sc, c.C, e, st);
             break;
     }
     const hipError_t le = hipGetLastError();
@@ -1794,6 +1809,8 @@ int occ_destroy(occ_sampler *s)
             if (s->regions.pin) (void)hipHostFree(s->regions.pin);
             if (s->ppc.rec) (void)hipFree(s->ppc.rec);
             if (s->ppc.pin) (void)hipHostFree(s->ppc.pin);
+            if (s->spatial.rec) (void)hipFree(s->spatial.rec);
+            if (s->spatial.pin) (void)hipHostFree(s->spatial.pin);
             if (s->pin_sc) (void)hipHostFree(s->pin_sc);
             if (s->pin_rec) (void)hipHostFree(s->pin_rec);
             for (hipEvent_t ev : {s->ev0, s->ev1, s->ev_z[0], s->ev_z[1], s->ev_side[0], s->ev_side[1]})
@@ -2640,6 +2657,8 @@ static int finish_marks(occ_sampler *s, bool last, size_t n_rec)
     if (rrc) return rrc;
     const int prc = record_copy_out(s, s->ppc);
     if (prc) return prc;
+    const int src = record_copy_out(s, s->spatial);
+    if (src) return src;
     s->marks_done = true;
     return OCC_OK;
 }
@@ -2655,6 +2674,13 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     if (rc) return rc;
     if ((rc = regions_open(s, C, keep))) return rc;  // (zeroed here, in front of the window: also when the call is re-run)
     if ((rc = record_open(s, s->ppc, C, keep, (s->outputs_on & OUT_PPC) ? (size_t)PPC_NCOL : 0))) return rc;
+    if ((rc = record_open(s, s->spatial, C, keep, s->spatial.any ? (size_t)SP_NCOL : 0))) return rc;
+    if (s->spatial.args.rec != s->spatial.rec) {  // (the record grew: its address travels by value in the captured launches)
+        WAIT_TRY(s->stream);
+        WAIT_TRY(s->side);
+        destroy_graph(s);
+        s->spatial.args.rec = s->spatial.rec;
+    }
     if (c.rec != s->rec_buf || c.occ_rec != s->regions.rec || c.ppc_rec != s->ppc.rec) {
         c.rec = s->rec_buf;
         c.occ_rec = s->regions.rec;
@@ -2796,6 +2822,7 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     split_rows(s->pin_rec, C, keep, q, p, out_alpha, out_beta, out_tau);
     regions_close(s, keep, chains_on(h, OUT_REGION));
     record_close(s->ppc, keep, chains_on(h, OUT_PPC));
+    record_close(s->spatial, keep, std::vector<uint8_t>(s->spatial.on.begin(), s->spatial.on.end()));
     return OCC_OK;
 }
 
@@ -3208,6 +3235,116 @@ static int set_ppc_state(occ_sampler *s, int chain, int field, const double *in,
     return OCC_OK;
 }
 
+// ---- occ_get_state / occ_set_state of the spatial residual check's names (logit models) --------------------------------
+// moran_stats (1): the chain's switch, 0 or 1, a word of the handle.  moran_draws (keep 8, read-only): the chain's rows of the
+// last completed occ_run as doubles times 2^-32; length 0 if its switch was off during that call.  Before the first
+// switch-on both names answer OCC_E_STATE (switching a chain OFF before that is accepted and does nothing).  Nothing of a
+// chain's state changes.  Whether the two kernels are launched behind the z update follows "is any chain on": a change
+// drops the captured graphs, as flip_output does for a change of level.
+enum : int { MORAN_NONE = -1, MORAN_SWITCH = 0, MORAN_DRAWS = 1 };
+static int moran_field(const std::string &nm) { return nm == "moran_stats" ? MORAN_SWITCH : nm == "moran_draws" ? MORAN_DRAWS : MORAN_NONE; }
+static int moran_refused(occ_sampler *s)
+{
+    if (s->probit) return set_error(s, OCC_E_STATE, "the spatial residual check is not available for the probit model");
+    return set_error(s, OCC_E_STATE, "the spatial residual check has not been switched on for this handle (set moran_stats first)");
+}
+// First switch-on: the weights w_ij = -Q_ij as an off-diagonal CSR, from the handle's copy of Q -- its SELL-64 arrays on the
+// device, which hold the off-diagonals of every row in column order (occ_layout.hpp; a slot of value 0 is padding, or a
+// stored zero that weighs nothing) and which every handle has, a peer of a group included -- with the bounds the fixed-point
+// sums need; then the residuals' buffer and the switches.
+static int moran_init(occ_sampler *s)
+{
+    Ctx &c = s->ctx;
+    occ_sampler::Spatial &sp = s->spatial;
+    const int n = c.n, nslice = (n + 63) / 64;
+    std::vector<int> sell_ptr((size_t)nslice + 1);
+    HIP_TRY(copy_on(s, sell_ptr.data(), c.sell_ptr, sizeof(int) * sell_ptr.size(), hipMemcpyDeviceToHost));
+    const size_t nslot = (size_t)sell_ptr[nslice];
+    std::vector<int> sell_col(nslot);
+    std::vector<double> sell_val(nslot);
+    if (nslot) {
+        HIP_TRY(copy_on(s, sell_col.data(), c.sell_col, sizeof(int) * nslot, hipMemcpyDeviceToHost));
+        HIP_TRY(copy_on(s, sell_val.data(), c.sell_val, sizeof(double) * nslot, hipMemcpyDeviceToHost));
+    }
+    std::vector<int> ptr((size_t)n + 1, 0), col;
+    std::vector<double> val;
+    double S0 = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int base = sell_ptr[i / 64], width = (sell_ptr[i / 64 + 1] - base) / 64;
+        double d = 0.0;
+        for (int kk = 0; kk < width; ++kk) {
+            const size_t at = (size_t)base + (size_t)kk * 64 + (size_t)(i % 64);
+            const double qv = sell_val[at];
+            if (qv == 0.0) continue;
+            if (qv > 0.0) return set_error(s, OCC_E_BADARG, "the spatial residual check needs every off-diagonal of Q to be <= 0 (weights w_ij = -Q_ij)");
+            if (sell_col[at] < 0 || sell_col[at] >= n) return set_error(s, OCC_E_HIP, "internal: a column of the handle's Q is out of range");
+            col.push_back(sell_col[at]);
+            val.push_back(-qv);
+            d += -qv;
+        }
+        ptr[(size_t)i + 1] = (int)col.size();
+        S0 += d;
+    }
+    if (!(S0 > 0.0) || !(S0 < 0x1.0p30) || n >= (1 << 30))
+        return set_error(s, OCC_E_BADARG, "the spatial residual check needs 0 < S0 = sum of the weights -Q_ij < 2^30 (and n < 2^30): its sums are 64-bit fixed point");
+    int rc;
+    int *ptr_dev = nullptr, *col_dev = nullptr;
+    double *val_dev = nullptr;
+    if ((rc = dev_alloc(s, &ptr_dev, ptr.size(), false))) return rc;
+    if ((rc = dev_alloc(s, &col_dev, col.size(), false))) return rc;
+    if ((rc = dev_alloc(s, &val_dev, val.size(), false))) return rc;
+    HIP_TRY(copy_on(s, ptr_dev, ptr.data(), sizeof(int) * ptr.size(), hipMemcpyHostToDevice));
+    HIP_TRY(copy_on(s, col_dev, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice));
+    HIP_TRY(copy_on(s, val_dev, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice));
+    double2 *res = nullptr;
+    if ((rc = dev_alloc(s, &res, (size_t)c.C * n))) return rc;
+    if ((rc = dev_alloc(s, &sp.on_dev, (size_t)c.C))) return rc;
+    sp.on.assign((size_t)c.C, 0u);
+    sp.args.n = n, sp.args.p = c.p;
+    sp.args.Xt = c.Xt, sp.args.eta = c.eta, sp.args.z = c.z;
+    sp.args.ptr = ptr_dev, sp.args.col = col_dev, sp.args.val = val_dev;
+    sp.args.res = res, sp.args.rec = sp.rec, sp.args.on = sp.on_dev;
+    sp.ready = true;
+    return OCC_OK;
+}
+static int get_moran_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
+{
+    const occ_sampler::Spatial &sp = s->spatial;
+    if (s->probit || !sp.ready) return moran_refused(s);
+    if (field == MORAN_SWITCH) {
+        v.assign(1, sp.on[(size_t)chain] ? 1.0 : 0.0);
+        return OCC_OK;
+    }
+    v.clear();
+    if ((size_t)chain < sp.last_on.size() && sp.last_on[(size_t)chain]) {
+        const size_t per = (size_t)sp.last_keep * (size_t)SP_NCOL;
+        v.resize(per);
+        const long long *row = sp.last.data() + (size_t)chain * per;
+        for (size_t k = 0; k < per; ++k) v[k] = (double)row[k] * 0x1.0p-32;
+    }
+    return OCC_OK;
+}
+static int set_moran_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+{
+    occ_sampler::Spatial &sp = s->spatial;
+    if (s->probit) return moran_refused(s);
+    if (field == MORAN_DRAWS) return sp.ready ? set_error(s, OCC_E_STATE, "moran_draws is read-only") : moran_refused(s);
+    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
+    if (in[0] != 0.0 && in[0] != 1.0) return set_error(s, OCC_E_BADARG, "moran_stats is 0 or 1");
+    const bool on = in[0] != 0.0;
+    if (!on && !sp.ready) return OCC_OK;  // never switched on: nothing to switch off
+    int rc;
+    WAIT_TRY(s->side);
+    if (!sp.ready && (rc = moran_init(s))) return rc;
+    sp.on[(size_t)chain] = on ? 1u : 0u;
+    HIP_TRY(copy_on(s, sp.on_dev, sp.on.data(), sizeof(uint32_t) * sp.on.size(), hipMemcpyHostToDevice));
+    uint32_t any = 0u;
+    for (uint32_t o : sp.on) any |= o;
+    if (any != sp.any) destroy_graph(s);
+    sp.any = any;
+    return OCC_OK;
+}
+
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len)
 {
     if (!s || !name || !len) return OCC_E_BADARG;
@@ -3226,6 +3363,10 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     if (ppc_field(nm) != PPC_NONE) {
         const int prc = get_ppc_state(s, chain, ppc_field(nm), v);
         return prc ? prc : give_state(s, v, out, cap, len);
+    }
+    if (moran_field(nm) != MORAN_NONE) {
+        const int mrc = get_moran_state(s, chain, moran_field(nm), v);
+        return mrc ? mrc : give_state(s, v, out, cap, len);
     }
     int sums_kind = SUMS_SITE;
     const int site_q = site_field(nm, &sums_kind);
@@ -3294,6 +3435,7 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     const std::string nm(name);
     if (region_field(nm) != REGION_NONE) return set_region_state(s, chain, region_field(nm), in, len);
     if (ppc_field(nm) != PPC_NONE) return set_ppc_state(s, chain, ppc_field(nm), in, len);
+    if (moran_field(nm) != MORAN_NONE) return set_moran_state(s, chain, moran_field(nm), in, len);
     int sums_kind = SUMS_SITE;
     const int sums_q = site_field(nm, &sums_kind);
     if (sums_q != SITE_NONE) return set_site_state(s, chain, sums_kind, sums_q, in, len);
@@ -3464,6 +3606,7 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     // (the timing loops always launch k_z_ob itself, never the twin that keeps the per-site sums; no captured graph of the
     // handle is replayed here)
     Scoped<uint32_t> plain_z_ob(&s->outputs_on, 0u);
+    Scoped<uint32_t> no_spatial(&s->spatial.any, 0u);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops
     if (rc) return rc;
     // The fused iteration kernel first, IN SITU: `reps` real iterations continue the chains from where they are

@@ -42,14 +42,10 @@
 
 #include "occ_plan.hpp"
 #include "occ_rng.hpp"
+#include "occ_state.hpp"  // the chains' scalars and the few device functions a second translation unit shares
 
 namespace occ {
 
-constexpr int NACC_MAX = MAXC * (MAXC + 1) / 2 + MAXC;  // 44
-constexpr int MAXG = 32;                            // OCC_MAX_COVARIATES: the generic path (P = 0 instantiations, run-time p and q)
-constexpr int NACC_G = MAXG * (MAXG + 1) / 2 + MAXG;    // 560
-constexpr int NSLOT = 4;
-constexpr int MAX_WAVES = 4;  // threads per block <= 256
 
 // MINRES scalar state of one chain; slot s is written by step s and read by step s+1.
 #ifndef OCC_SLOT_ALIGN
@@ -86,38 +82,6 @@ __device__ __forceinline__ void slot_store(Slot *p, const Slot &s)
 #undef X
 }
 
-struct Ctl {
-    uint32_t it;    // Gibbs iteration number (Philox counter word 2)
-    uint32_t koff;  // Krylov launches already spent on the current eta solve by earlier graph replays:
-                    // 0 normally; > 0 when a replay ran out of captured launches and the NEXT replay
-                    // continues the same solve (no host involvement, same arithmetic)
-};
-
-// Control words are handed over between kernels, never updated in place: the kernels of launch
-// sequence ("slot") number s read ctl[s & 1]; k_z_ob, the last kernel of the slot, writes ctl[(s+1) & 1];
-// k_beta_partial publishes the carry decision of the slot in mid[s & 1].  No kernel reads a word that
-// another block of the same kernel writes.
-struct ChainScalars {
-    double alpha[MAXG], beta[MAXG];
-    double tau;
-    double tau_gamma[2];       // the standard gamma variate of tau's draw of iteration t in [t & 1] (logit.py:209): it depends on
-                               // nothing but (key, t), so k_noise draws it one iteration ahead, off the critical path
-    double beta_eps[2][MAXG];  // likewise the p standard normals of beta's draw of iteration t in [t & 1] (distributions.pyx:95-96):
-                               // block_normal(key, k, 0, t, STREAM_BETA), drawn by k_noise beside tau_gamma, read by every beta
-                               // draw of a running chain (k_z_ob, k_z_ob_stats, k_beta_draw); the INJ kernels keep their own
-    uint64_t key;
-    Ctl ctl[2], mid[2];
-    uint32_t it_stop, it_base, burnin, keep;
-    uint32_t bar_base;         // arrivals counted so far by the chain's barrier counter (occ_iter.hpp), never reset
-    int32_t err;               // OCC_E_* raised on device
-    int32_t minres_itn_last;
-    uint32_t site_on;          // OUT_SITE: per-site posterior sums (Ctx::site_acc) are kept for this chain; OUT_LL: the log-likelihood
-                               // sums (Ctx::ll_acc); OUT_REGION: the occupied sites per region and draw (Ctx::occ_rec); OUT_PPC: the
-                               // posterior predictive check (Ctx::ppc_rec) -- occ_plan.hpp; sits where the layout had padding
-    unsigned long long krylov_total, krylov_sq_total, solves, carries;
-};
-
-static_assert(sizeof(ChainScalars) == 640 + 2 * MAXG * 8, "ChainScalars: the layout every kernel was compiled against");
 
 // Variates handed in by the caller instead of the chain's Philox streams: the per-conditional entry points of the C ABI
 // (occ_cond_*, include/occ_gibbs.h) run the kernels below in their INJ instantiation, which take the standard gamma variate
@@ -561,20 +525,9 @@ __device__ __forceinline__ void slice_of(const Ctx &c, int i, int &base, int &wi
 
 
 
-__device__ __forceinline__ double expit(double x)
-{
-    if (x < 0.0) { const double e = exp(x); return e / (1.0 + e); }
-    return 1.0 / (1.0 + exp(-x));
-}
 
 // ---- site-level arithmetic shared by the stand-alone kernels and the fused iteration kernel (occ_iter.hpp):
 // written with explicit contractions so that both evaluate the same operations.
-__device__ __forceinline__ double xdot(const double *Xt, int n, int i, const double *coef, int p)
-{
-    double acc = 0.0;
-    for (int a = 0; a < p; ++a) acc = fma(Xt[(size_t)a * n + i], coef[a], acc);
-    return acc;
-}
 // right-hand side of the eta system at one site: k - omega x'beta + sqrt(omega) eps_1 + sqrt(tau) u   (logit.py:76-78, 213)
 __device__ __forceinline__ double eta_rhs_site(double om, double xb, double z, double en, double up, double sqrt_tau)
 {
@@ -2268,26 +2221,6 @@ __device__ __forceinline__ uint32_t *region_row(const Ctx &c, const ChainScalars
 enum : int { PPC_T_OBS = 0, PPC_T_REP = 1, PPC_DET_REP = 2, PPC_SITES_REP = 3, PPC_NCOL = 4 };
 __device__ __forceinline__ unsigned long long ppc_fx(double x) { return __double2ull_rn(x * 0x1.0p32); }
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned long long dpp_shifted_u64(unsigned long long b)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, ROW_MASK, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, ROW_MASK, 0xf, false);
-    return ((unsigned long long)hi << 32) | lo;
-}
-// wave_sum's levels on 64-bit integers; the total is uniform (lane 63's)
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
-{
-    v += dpp_shifted_u64<0xB1, 0xf>(v);
-    v += dpp_shifted_u64<0x4E, 0xf>(v);
-    v += dpp_shifted_u64<0x141, 0xf>(v);
-    v += dpp_shifted_u64<0x140, 0xf>(v);
-    v += dpp_shifted_u64<0x142, 0xa>(v);
-    v += dpp_shifted_u64<0x143, 0xc>(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
-    return ((unsigned long long)hi << 32) | lo;
-}
 // One workgroup's sites into the four sums of one chain and kept draw, `row`.  EVERY thread of the workgroup comes here (the
 // barriers), one without a surveyed site with zeros: the wave's sums by DPP, the workgroup's in LDS, then one 64-bit
 // integer add to device memory per column that is not zero.

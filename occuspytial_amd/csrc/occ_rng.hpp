@@ -29,7 +29,8 @@ enum : uint32_t {
     STREAM_ETA_DENSE = 10, // the standard normals of the reference-form prior draw: c0 = column of the factor
     STREAM_PB_EPS = 11,    // probit model (occ_probit.hpp): the site noise eps, c0 = site ...
     STREAM_PB_XI = 12,     // ... and the normals of the coefficients c, c0 = basis column
-    STREAM_PPC = 13        // posterior predictive check: the uniform of a replicated detection, c0 = flat visit row
+    STREAM_PPC = 13,       // posterior predictive check: the uniform of a replicated detection, c0 = flat visit row
+    STREAM_SPATIAL = 14    // spatial residual check (occ_spatial.hpp): the uniform of a replicated occupancy, c0 = site
 };
 
 constexpr double kPi = 3.14159265358979323846;

@@ -1,0 +1,87 @@
+// occ_state.hpp -- what more than one translation unit of the engine reads: the limits, the chains' scalars (ChainScalars, Ctl)
+// and a few device functions -- expit, the covariate dot product, the 64-bit integer wave sum.  occ_kernels.hpp includes
+// it; occ_spatial.hip is a unit of its own and includes nothing else of the kernels (occ_kernels.hpp defines kernels, which
+// must exist once per library).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "occ_plan.hpp"
+
+namespace occ {
+
+constexpr int NACC_MAX = MAXC * (MAXC + 1) / 2 + MAXC;  // 44
+constexpr int MAXG = 32;                            // OCC_MAX_COVARIATES: the generic path (P = 0 instantiations, run-time p and q)
+constexpr int NACC_G = MAXG * (MAXG + 1) / 2 + MAXG;    // 560
+constexpr int NSLOT = 4;
+constexpr int MAX_WAVES = 4;  // threads per block <= 256
+
+struct Ctl {
+    uint32_t it;    // Gibbs iteration number (Philox counter word 2)
+    uint32_t koff;  // Krylov launches already spent on the current eta solve by earlier graph replays:
+                    // 0 normally; > 0 when a replay ran out of captured launches and the NEXT replay
+                    // continues the same solve (no host involvement, same arithmetic)
+};
+
+// Control words are handed over between kernels, never updated in place: the kernels of launch
+// sequence ("slot") number s read ctl[s & 1]; k_z_ob, the last kernel of the slot, writes ctl[(s+1) & 1];
+// k_beta_partial publishes the carry decision of the slot in mid[s & 1].  No kernel reads a word that
+// another block of the same kernel writes.
+struct ChainScalars {
+    double alpha[MAXG], beta[MAXG];
+    double tau;
+    double tau_gamma[2];       // the standard gamma variate of tau's draw of iteration t in [t & 1] (logit.py:209): it depends on
+                               // nothing but (key, t), so k_noise draws it one iteration ahead, off the critical path
+    double beta_eps[2][MAXG];  // likewise the p standard normals of beta's draw of iteration t in [t & 1] (distributions.pyx:95-96):
+                               // block_normal(key, k, 0, t, STREAM_BETA), drawn by k_noise beside tau_gamma, read by every beta
+                               // draw of a running chain (k_z_ob, k_z_ob_stats, k_beta_draw); the INJ kernels keep their own
+    uint64_t key;
+    Ctl ctl[2], mid[2];
+    uint32_t it_stop, it_base, burnin, keep;
+    uint32_t bar_base;         // arrivals counted so far by the chain's barrier counter (occ_iter.hpp), never reset
+    int32_t err;               // OCC_E_* raised on device
+    int32_t minres_itn_last;
+    uint32_t site_on;          // OUT_SITE: per-site posterior sums (Ctx::site_acc) are kept for this chain; OUT_LL: the log-likelihood
+                               // sums (Ctx::ll_acc); OUT_REGION: the occupied sites per region and draw (Ctx::occ_rec); OUT_PPC: the
+                               // posterior predictive check (Ctx::ppc_rec) -- occ_plan.hpp; sits where the layout had padding
+    unsigned long long krylov_total, krylov_sq_total, solves, carries;
+};
+
+static_assert(sizeof(ChainScalars) == 640 + 2 * MAXG * 8, "ChainScalars: the layout every kernel was compiled against");
+
+__device__ __forceinline__ double expit(double x)
+{
+    if (x < 0.0) { const double e = exp(x); return e / (1.0 + e); }
+    return 1.0 / (1.0 + exp(-x));
+}
+
+// x_i . coef over the structure-of-arrays design (explicit contractions: every caller evaluates the same operations)
+__device__ __forceinline__ double xdot(const double *Xt, int n, int i, const double *coef, int p)
+{
+    double acc = 0.0;
+    for (int a = 0; a < p; ++a) acc = fma(Xt[(size_t)a * n + i], coef[a], acc);
+    return acc;
+}
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long dpp_shifted_u64(unsigned long long b)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, ROW_MASK, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, ROW_MASK, 0xf, false);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// wave_sum's levels on 64-bit integers; the total is uniform (lane 63's)
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+    v += dpp_shifted_u64<0xB1, 0xf>(v);
+    v += dpp_shifted_u64<0x4E, 0xf>(v);
+    v += dpp_shifted_u64<0x141, 0xf>(v);
+    v += dpp_shifted_u64<0x140, 0xf>(v);
+    v += dpp_shifted_u64<0x142, 0xa>(v);
+    v += dpp_shifted_u64<0x143, 0xc>(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+}  // namespace occ

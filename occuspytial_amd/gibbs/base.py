@@ -16,6 +16,7 @@ from ..data import Data
 from ..posterior import PosteriorParameter
 from ..ppc import ppc_flag
 from ..regions import region_ids
+from ..spatial import spatial_flag
 from ..utils import get_generator
 from .parallel import sample_parallel
 from .state import FixedState, State
@@ -117,7 +118,7 @@ class GibbsBase:
         return self.chain
 
     def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False, waic=False, regions=None,
-               ppc=False):
+               ppc=False, spatial_check=False):
         """Draw ``size`` iterations per chain and return the kept ``alpha``, ``beta``, ``tau`` draws.
 
         Same contract as the reference (``base.py:243-291``): ``burnin < size`` else ``ValueError``;
@@ -142,6 +143,10 @@ class GibbsBase:
         site's detections from the draw's z and alpha and records the Freeman-Tukey discrepancy of the observed and of the
         replicated data; ``out.ppc`` is a :class:`~occuspytial_amd.ppc.PredictiveCheck` (Bayesian p-value, lack-of-fit
         ratio; ``None`` otherwise).  ``out.summary`` and the chains are unchanged.
+
+        ``spatial_check=True`` (likewise): per kept draw the device forms Moran's I of the occupancy residuals
+        ``z - psi`` and of one replicate of them; ``out.spatial_check`` is a
+        :class:`~occuspytial_amd.spatial.SpatialCheck` (tail probability, excess autocorrelation; ``None`` otherwise).
         """
         if burnin >= size:
             raise ValueError('burnin value cannot be larger than sample size')
@@ -158,6 +163,9 @@ class GibbsBase:
         if ppc_flag(ppc):
             self._refuse_ppc()
             extra['ppc'] = True
+        if spatial_flag(spatial_check):
+            self._refuse_spatial_check()
+            extra['spatial_check'] = True
         samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start,
                                   progressbar=progressbar, **extra)
         out = PosteriorParameter(*samples)
@@ -168,12 +176,20 @@ class GibbsBase:
             out.regions = self._region_result(ids, out)
         if 'ppc' in extra:
             out.ppc = self.__dict__.pop('_ppc')
+        if 'spatial_check' in extra:
+            out.spatial_check = self.__dict__.pop('_spatial_check')
         return out
 
     def _refuse_ppc(self):
         """The detections are replicated by the engine's z update: a sampler with a Python ``step`` has none."""
         if not hasattr(self, '_run_chains'):
             raise NotImplementedError(f'{self.__class__.__name__} steps in Python: posterior predictive checks are formed by '
+                                      'the device engine only')
+
+    def _refuse_spatial_check(self):
+        """The residuals' sums are formed on the device behind the engine's z update: a sampler with a Python ``step`` has none."""
+        if not hasattr(self, '_run_chains'):
+            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: the spatial residual check is formed by '
                                       'the device engine only')
 
     def _refuse_regions(self):

@@ -7,6 +7,7 @@ from ..chain import Chain
 from ..ppc import PredictiveCheck, ppc_flag
 from ..regions import region_ids
 from ..sites import SiteSummary
+from ..spatial import SpatialCheck, spatial_flag
 from ..waic import WAIC
 from .base import GibbsBase
 
@@ -146,7 +147,14 @@ class LogitICARGibbs(GibbsBase):
         except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
             raise ValueError(f'the loaded engine library has no posterior predictive check ({exc}): rebuild it') from None
 
-    def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False, regions=None, ppc=False):
+    def _moran_switch(self, eng, on):
+        try:
+            eng.moran_stats(on)
+        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
+            raise ValueError(f'the loaded engine library has no spatial residual check ({exc}): rebuild it') from None
+
+    def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False, regions=None, ppc=False,
+               spatial_check=False):
         """Continue the chains of ``checkpoint`` (a dict from :meth:`checkpoint` or the path of its ``.npz``)
         for ``size`` more iterations on this sampler's problem.  Returns a ``PosteriorParameter`` of the new
         draws; every chain's ``Chain`` is the continuation (use ``Chain.expand`` / ``append`` to join them to
@@ -155,7 +163,8 @@ class LogitICARGibbs(GibbsBase):
         every iteration accumulated so far, those before the checkpoint included.  ``waic=True``: the same for the
         log-likelihood sums and the result's ``waic``.  ``regions`` (as in :meth:`sample`): the occupied sites per region of
         the new draws, ``out['occupied']`` and ``out.regions``; the draws belong to a call, so nothing of them is carried.
-        ``ppc=True``: the posterior predictive check of the new draws, ``out.ppc``; likewise nothing of it is carried."""
+        ``ppc=True``: the posterior predictive check of the new draws, ``out.ppc``; likewise nothing of it is carried.
+        ``spatial_check=True``: the spatial residual check of the new draws, ``out.spatial_check``; likewise."""
         from ..posterior import PosteriorParameter
         from tqdm.auto import tqdm
         if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, '__fspath__'):
@@ -169,6 +178,9 @@ class LogitICARGibbs(GibbsBase):
         ppc = ppc_flag(ppc)
         if ppc:
             self._refuse_ppc()
+        spatial_check = spatial_flag(spatial_check)
+        if spatial_check:
+            self._refuse_spatial_check()
         C = int(checkpoint['n_chains'])
         self.__dict__['_stepping'] = False
         eng = self._get_engine([int(k) for k in np.asarray(checkpoint['keys'])])
@@ -186,6 +198,11 @@ class LogitICARGibbs(GibbsBase):
             ppc_rows = np.zeros((C, size, 4))
         elif getattr(eng, '_ppc_on', False):   # (the checkpoint's switch was on: this call did not ask)
             eng.ppc_stats(False)
+        if spatial_check:
+            self._moran_switch(eng, True)
+            moran_rows = np.zeros((C, size, 8))
+        elif getattr(eng, '_moran_on', False):   # (the checkpoint's switch was on: this call did not ask)
+            eng.moran_stats(False)
         alpha = np.zeros((C, size, self._problem.q))
         beta = np.zeros((C, size, self._problem.p))
         tau = np.zeros((C, size))
@@ -199,6 +216,8 @@ class LogitICARGibbs(GibbsBase):
                 occupied[:, done:done + step] = [eng.region_draws(c) for c in range(C)]
             if ppc:
                 ppc_rows[:, done:done + step] = [eng.ppc_draws(c) for c in range(C)]
+            if spatial_check:
+                moran_rows[:, done:done + step] = [eng.moran_draws(c) for c in range(C)]
             done += step
             bar.update(step)
         bar.close()
@@ -214,11 +233,13 @@ class LogitICARGibbs(GibbsBase):
             out.regions = self._region_result(ids, out)
         if ppc:
             out.ppc = PredictiveCheck.from_problem(self._problem, ppc_rows)
+        if spatial_check:
+            out.spatial_check = SpatialCheck.from_problem(self._problem, moran_rows)
         return out
 
     # ------------------------------------------------------------------ batched chains
     def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False, waic=False, regions=None,
-                    ppc=False):
+                    ppc=False, spatial_check=False):
         """All chains of one ``sample`` call as one device batch.
 
         Mirrors ``GibbsBase._run`` (base.py:214-241) per chain: start values from the chain's own
@@ -231,6 +252,9 @@ class LogitICARGibbs(GibbsBase):
         chunk's rows are appended to the chains' ``occupied``.  With the default no call about it reaches the engine.
         ``ppc``: the posterior predictive check, switched in the same way; every chunk's rows are appended and the
         :class:`~occuspytial_amd.ppc.PredictiveCheck` made of them is left for ``sample``.  With the default no call about
+        it reaches the engine.
+        ``spatial_check``: the spatial residual check, switched in the same way; every chunk's rows are appended and the
+        :class:`~occuspytial_amd.spatial.SpatialCheck` made of them is left for ``sample``.  With the default no call about
         it reaches the engine.
         """
         from tqdm.auto import tqdm
@@ -256,12 +280,15 @@ class LogitICARGibbs(GibbsBase):
             eng.region_stats(False)
         if ppc or getattr(eng, '_ppc_on', False):   # (off during burn-in; a reused engine that an earlier call left on)
             self._ppc_switch(eng, False)
+        if spatial_check or getattr(eng, '_moran_on', False):   # (likewise)
+            self._moran_switch(eng, False)
         sums_on = False
 
         C = len(samplers)
         keep = size - burnin
         extra = {'occupied': np.zeros((C, keep, max(int(regions.max()) + 1, 1)))} if regions is not None else {}
         ppc_rows = np.zeros((C, keep, 4)) if ppc else None
+        moran_rows = np.zeros((C, keep, 8)) if spatial_check else None
         alpha = np.zeros((C, keep, self._problem.q))
         beta = np.zeros((C, keep, self._problem.p))
         tau = np.zeros((C, keep))
@@ -281,6 +308,8 @@ class LogitICARGibbs(GibbsBase):
                         eng.region_stats(True)
                     if ppc:
                         eng.ppc_stats(True)
+                    if spatial_check:
+                        eng.moran_stats(True)
                     sums_on = True
                 a_, b_, t_ = eng.run(step, b)
                 m = step - b
@@ -289,6 +318,8 @@ class LogitICARGibbs(GibbsBase):
                     extra['occupied'][:, kept:kept + m] = [eng.region_draws(c) for c in range(C)]
                 if ppc:
                     ppc_rows[:, kept:kept + m] = [eng.ppc_draws(c) for c in range(C)]
+                if spatial_check:
+                    moran_rows[:, kept:kept + m] = [eng.moran_draws(c) for c in range(C)]
                 kept += m
             done += step
             for bar in bars:
@@ -307,6 +338,8 @@ class LogitICARGibbs(GibbsBase):
             self.__dict__['_' + _lib.SUMS_KINDS[kind].result] = SUMS_RESULT[kind].from_engine(eng)
         if ppc:
             self.__dict__['_ppc'] = PredictiveCheck.from_problem(self._problem, ppc_rows)
+        if spatial_check:
+            self.__dict__['_spatial_check'] = SpatialCheck.from_problem(self._problem, moran_rows)
         return chains
 
 

@@ -111,6 +111,10 @@ class ProbitRSRGibbs(GibbsBase):
         # (its detection part is a probit regression on the auxiliary scale: a check of it is out of scope so far)
         raise NotImplementedError('posterior predictive checks are not available for the probit model')
 
+    def _refuse_spatial_check(self):
+        # (its psi is the modelling decision DESIGN 11 leaves open)
+        raise NotImplementedError('the spatial residual check is not available for the probit model')
+
     step = LogitICARGibbs.step
     checkpoint = LogitICARGibbs.checkpoint
     resume = LogitICARGibbs.resume

@@ -43,6 +43,7 @@ class PosteriorParameter:
     waic = None    # a WAIC when sample(..., waic=True) asked for the streaming log-likelihood sums
     regions = None  # a RegionOccupancy when sample(..., regions=...) asked for the occupied sites per region and draw
     ppc = None     # a PredictiveCheck when sample(..., ppc=True) asked for the posterior predictive check
+    spatial_check = None  # a SpatialCheck when sample(..., spatial_check=True) asked for Moran's I of the occupancy residuals
 
     def __init__(self, *chains):
         self.data = self._create_inference_data(chains)
