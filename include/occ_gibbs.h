@@ -233,7 +233,34 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  * probit handle answers them with OCC_E_STATE, "the spatial residual check is not available for the probit model".  Nothing
  * is redrawn; occ_set_start and occ_set_keys do not touch it; a call that is re-run after a device-side wait gave up counts
  * nothing twice; occ_step, occ_profile and the occ_cond_* entry points never count.  alpha, beta, tau, eta, z, the site_* and
- * ll_* sums, region_draws and ppc_draws are bit-identical with it on or off, and it is independent of the four outputs. */
+ * ll_* sums, region_draws and ppc_draws are bit-identical with it on or off, and it is independent of the four outputs.
+ *
+ * Per-site intervals (logit models; ICAR and reduced rank): how sure is the model about psi at a site?  psi lives in (0, 1), so
+ * a histogram per site with B equal bins answers every quantile of psi_i to within 1 / B, with an exact bracket, and the
+ * chains' histograms merge exactly by addition; the draws are not needed.  Per iteration past the call's burn-in -- the rule of
+ * the per-site sums above: `keep` does not matter, so occ_step counts as well -- of a chain whose switch is on, with beta and
+ * eta (reduced rank: K theta) of the iteration, one kernel launched directly behind the z update forms
+ *   psi_i = expit(x_i beta + eta_i), as the z update forms it;   b = min(B - 1, (int)(psi_i B));
+ * and adds 1 to the chain's 32-bit count of (bin b, site i), and 1 to the chain's count of accumulated iterations.  Integer
+ * counts: the same values whatever the path, the placement or the block size.  4 B bytes per site and chain.
+ *   hist_stats(1)
+ *       a word of the handle per chain: 0 is off, B with 4 <= B <= 1024 is on with B bins, any other value is OCC_E_BADARG.  It
+ *       is not one of the z update's outputs above.  The first switch-on allocates; switching on ZEROES the chain's histograms
+ *       and count; 0 keeps everything readable.  B belongs to the handle: a chain that asks for another B while any chain is on
+ *       gets OCC_E_BADARG (the message names the handle's B); with every chain off a new B frees and reallocates, and every
+ *       chain's histograms start from zero.
+ *   hist_count(1)
+ *       the chain's count of accumulated iterations.
+ *   hist_counts(B n)
+ *       the chain's histograms, bin-major [bin][site], as doubles (32-bit counts: exact).
+ * hist_count and hist_counts are writable while the chain's switch is on (checkpoint restore): whole numbers in [0, 2^32),
+ * OCC_E_BADARG otherwise.  The handle keeps, per chain, an upper bound on every count -- the iterations past burn-in of every
+ * call since the last zeroing, raised to what a write holds -- and occ_run / occ_step refuse with OCC_E_BADARG a call that
+ * could take a count past 2^32 - 1.  All three names answer OCC_E_STATE before the handle's first switch-on (switching a chain
+ * off before that is accepted), and a probit handle answers them with OCC_E_STATE, "per-site intervals are not available for
+ * the probit model".  Nothing is redrawn; occ_set_start and occ_set_keys do not touch them; a call that is re-run after a
+ * device-side wait gave up counts nothing twice; occ_profile and the occ_cond_* entry points never count.  alpha, beta, tau,
+ * eta, z, every sum and every record above are bit-identical with the switch on or off. */
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len);
 int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double *in, int64_t len);
 

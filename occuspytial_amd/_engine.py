@@ -123,6 +123,9 @@ class Engine:
         self._ppc_on = False
         # spatial residual check: the switch; until it is first set, no call about it reaches the library
         self._moran_on = False
+        # per-site intervals: the number of bins while switched on, 0 while off; until it is first set, no call about them
+        # reaches the library
+        self._hist_bins = 0
         _LIVE.add(self)
         return self
 
@@ -221,6 +224,11 @@ class Engine:
             out['ppc_stats'] = np.ones(self.n_chains)
         if self._moran_on:   # likewise
             out['moran_stats'] = np.ones(self.n_chains)
+        if self._hist_bins:   # the switch (the number of bins), the counts of accumulated iterations and the histograms
+            parts = [self.hist_counts(c) for c in range(self.n_chains)]
+            out['hist_stats'] = np.full(self.n_chains, float(self._hist_bins))
+            out['hist_count'] = np.array([p['count'] for p in parts], dtype=np.int64)
+            out['hist_counts'] = np.stack([p['counts'] for p in parts])
         return out
 
     def restore(self, ckpt):
@@ -262,6 +270,32 @@ class Engine:
             self.moran_stats(True)
         elif self._moran_on:
             self.moran_stats(False)
+        if 'hist_stats' in ckpt and np.all(np.asarray(ckpt['hist_stats']) != 0):
+            self.hist_stats(int(np.asarray(ckpt['hist_stats']).ravel()[0]))
+            for c in range(self.n_chains):
+                self.set('hist_count', float(np.asarray(ckpt['hist_count'])[c]), c)
+                self.set('hist_counts', np.asarray(ckpt['hist_counts'])[c].ravel(), c)
+        elif self._hist_bins:
+            self.hist_stats(0)
+
+    # ---- per-site intervals (state names hist_*, include/occ_gibbs.h) ----
+    def hist_stats(self, bins):
+        """Switch the per-site histograms of every chain: ``bins`` from 4 to 1024 is on with that many equal bins on (0, 1)
+        (which ZEROES them and their counts), 0 or False is off (they stay readable).  While on, every iteration past a
+        call's burn-in adds one count per site, in the bin of the iteration's psi (:meth:`hist_counts`).  The number of bins
+        belongs to the handle: for another one every chain is switched off first."""
+        bins = 64 if bins is True else bins
+        if bins and self._hist_bins and bins != self._hist_bins:
+            self.hist_stats(0)
+        for c in range(self.n_chains):
+            self.set('hist_stats', float(bins), c)
+        self._hist_bins = int(bins)
+
+    def hist_counts(self, chain=0):
+        """``{'bins': B, 'count': iterations accumulated, 'counts': (B, n) uint32}`` of one chain."""
+        counts = self.get('hist_counts', chain)
+        B = counts.size // self.prob.n
+        return {'bins': B, 'count': int(self.get('hist_count', chain)[0]), 'counts': counts.reshape(B, self.prob.n).astype(np.uint32)}
 
     # ---- spatial residual check (state names moran_*, include/occ_gibbs.h) ----
     def moran_stats(self, on):
@@ -567,6 +601,19 @@ class EngineGroup:
     def moran_draws(self, chain=0):
         g, i = self.where[chain]
         return self.engines[g].moran_draws(i)
+
+    # per-site intervals: the switch on every device, the histograms routed by chain
+    @property
+    def _hist_bins(self):
+        return max(getattr(e, '_hist_bins', 0) for e in self.engines)
+
+    def hist_stats(self, bins):
+        for e in self.engines:
+            e.hist_stats(bins)
+
+    def hist_counts(self, chain=0):
+        g, i = self.where[chain]
+        return self.engines[g].hist_counts(i)
 
     # (the entry points by name are Engine's own: each only names its kind)
     site_stats, site_sums, loglik_stats, loglik_sums = Engine.site_stats, Engine.site_sums, Engine.loglik_stats, Engine.loglik_sums

@@ -27,6 +27,9 @@ PPC_FIELDS = ('ppc_stats', 'ppc_draws')
 # the spatial residual check: the chain's switch (a word of the handle), the chain's rows of the last occ_run (keep 8: the sums
 # A, B, C, D of Moran's I of z - psi, then those of its replicate)
 MORAN_FIELDS = ('moran_stats', 'moran_draws')
+# per-site intervals: the chain's switch (a word of the handle: 0 off, B on with B bins), its count of accumulated iterations,
+# its histograms of psi (B n, bin-major)
+HIST_FIELDS = ('hist_stats', 'hist_count', 'hist_counts')
 KERNEL_KINDS = ('omega_b', 'noise', 'eta_init', 'minres', 'beta_partial', 'omega_a', 'alpha_draw', 'z_ob', 'iter')
 
 

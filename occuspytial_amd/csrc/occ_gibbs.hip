@@ -24,6 +24,7 @@
 #include "occ_rsr.hpp"
 #include "occ_probit.hpp"
 #include "occ_spatial.hpp"
+#include "occ_hist.hpp"
 #include "occ_layout.hpp"
 
 using namespace occ;
@@ -179,6 +180,22 @@ struct occ_sampler {
         uint32_t *on_dev = nullptr;
         SpArgs args{};
     } spatial;
+    // Per-site intervals (state names hist_stats, hist_count, hist_counts; logit models; occ_hist.hpp).  ready: a chain has been
+    // switched on once -- the histograms [C][B][n], the counts [C] and the switches are on the device.  B belongs to the
+    // handle.  The switch is a word of the handle per chain (on, on_dev), as the spatial residual check's; any: their OR, which
+    // decides whether the kernel is launched behind the z update (baked into captured graphs with B and the addresses: a
+    // change drops them).  bound: per chain an upper bound on every count -- the iterations past burn-in of every call since
+    // the last zeroing or write -- which keeps the 32-bit counts from wrapping.  snap: [C B n] counts, then [C] count words,
+    // part of what a call is re-run from; snapped: taken for the running call.
+    struct Hist {
+        bool ready = false, snapped = false;
+        uint32_t any = 0u;
+        std::vector<uint32_t> on;
+        std::vector<uint64_t> bound;
+        uint32_t *on_dev = nullptr, *snap = nullptr;
+        HistArgs args{};
+        size_t words(int C) const { return (size_t)C * (size_t)args.B * (size_t)args.n; }
+    } hist;
     std::vector<ChainScalars> snap_sc;
     // fixed problem arrays on the device, in upload order: what a group broadcasts from its root (occ_create_group /
     // occ_create_distributed); defer_fixed: allocate only, the bytes arrive by broadcast
@@ -640,6 +657,8 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
             }
             if (s->spatial.any)  // the spatial residual check, directly behind the z update: stream order is the synchronisation
                 sp_launch(s->spatial.args, s->ctx.sc, c.C, e, st);
+            if (s->hist.any)  // the per-site intervals, likewise
+                hist_launch(s->hist.args, s->ctx.sc, c.C, e, st);
             break;
     }
     const hipError_t le = hipGetLastError();
@@ -969,6 +988,14 @@ int open_window(occ_sampler *s, int64_t n_iter, int64_t burnin, int64_t keep, bo
             if (!r.snap && (rc = dev_alloc(s, &r.snap, nsum + (size_t)c.C, false))) return rc;
             HIP_TRY(hipMemcpyAsync(r.snap, c.*SUMS[k].acc, sizeof(double) * nsum, hipMemcpyDeviceToDevice, s->stream));
             HIP_TRY(hipMemcpyAsync(r.snap + nsum, c.*SUMS[k].count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
+        }
+        occ_sampler::Hist &hs = s->hist;  // ... and so are the histograms of the per-site intervals
+        hs.snapped = hs.any != 0u;
+        if (hs.snapped) {
+            const size_t nw = hs.words(c.C);
+            if (!hs.snap && (rc = dev_alloc(s, &hs.snap, nw + (size_t)c.C, false))) return rc;
+            HIP_TRY(hipMemcpyAsync(hs.snap, hs.args.cnt, sizeof(uint32_t) * nw, hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(hs.snap + nw, hs.args.count, sizeof(uint32_t) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
         }
         hipLaunchKernelGGL(k_snapshot, dim3((unsigned)std::min<size_t>((Cn + 255) / 256, 2048)), dim3(256), 0, s->stream, c.eta, s->snap_eta, c.z, s->snap_z, c.Xv, s->snap_x,
                            (unsigned long long)Cn, s->rsr.m > 0 ? s->rsr.theta : nullptr, s->snap_theta, (unsigned long long)c.C * (unsigned long long)std::max(s->rsr.m, 0),
@@ -2877,6 +2904,11 @@ static int fallback_to_launch_per_step(occ_sampler *s)
         HIP_TRY(copy_on(s, c.*SUMS[k].acc, s->sums[k].snap, sizeof(double) * nsum, hipMemcpyDeviceToDevice));
         HIP_TRY(copy_on(s, c.*SUMS[k].count, s->sums[k].snap + nsum, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
     }
+    if (s->hist.snapped) {
+        const size_t nw = s->hist.words(c.C);
+        HIP_TRY(copy_on(s, s->hist.args.cnt, s->hist.snap, sizeof(uint32_t) * nw, hipMemcpyDeviceToDevice));
+        HIP_TRY(copy_on(s, s->hist.args.count, s->hist.snap + nw, sizeof(uint32_t) * (size_t)c.C, hipMemcpyDeviceToDevice));
+    }
     for (auto &sc : s->snap_sc) sc.err = 0;
     if ((rc = write_scalars(s, s->snap_sc))) return rc;
     s->parity = s->snap_parity;
@@ -2957,6 +2989,21 @@ static int refresh_paths(occ_sampler *s)
     return OCC_OK;
 }
 
+// Per-site intervals: a call that accumulates `add` iterations is admitted only if no count of a chain whose switch is on
+// could pass 2^32 - 1 (occ_sampler::Hist::bound); an admitted call raises the bounds -- once, also when it is re-run.
+static int hist_admit(occ_sampler *s, int64_t add)
+{
+    occ_sampler::Hist &hs = s->hist;
+    if (!hs.any) return OCC_OK;
+    for (size_t ch = 0; ch < hs.on.size(); ++ch)
+        if (hs.on[ch] && hs.bound[ch] + (uint64_t)add > 0xffffffffull)
+            return set_error(s, OCC_E_BADARG, ("this call could take a count of the per-site histograms of chain " + std::to_string(ch) +
+                                               " past 2^32 - 1: read hist_counts and set hist_stats again first").c_str());
+    for (size_t ch = 0; ch < hs.on.size(); ++ch)
+        if (hs.on[ch]) hs.bound[ch] += (uint64_t)add;
+    return OCC_OK;
+}
+
 int occ_step(occ_sampler *s)
 {
     if (!s) return OCC_E_BADARG;
@@ -2964,6 +3011,7 @@ int occ_step(occ_sampler *s)
     HIP_TRY(hipSetDevice(s->device));
     if (s->probit) return pb_step(s);
     int rc;
+    if ((rc = hist_admit(s, 1))) return rc;
     if ((rc = refresh_paths(s))) return rc;
     const bool fused = (s->fused() && s->rsr.m == 0) || s->run.flag_sync;  // paths with device-side waits: re-run without them if one gives up
     s->device_timeout = false;
@@ -2984,6 +3032,7 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
     HIP_TRY(hipSetDevice(s->device));
     if (s->probit) return pb_run(s, n_iter, burnin, out_alpha, out_beta, out_tau);
     int rc;
+    if ((rc = hist_admit(s, n_iter - burnin))) return rc;
     if ((rc = refresh_paths(s))) return rc;
     const bool fused = (s->fused() && s->rsr.m == 0) || s->run.flag_sync;
     s->device_timeout = false;
@@ -3345,6 +3394,120 @@ static int set_moran_state(occ_sampler *s, int chain, int field, const double *i
     return OCC_OK;
 }
 
+// ---- occ_get_state / occ_set_state of the per-site intervals' names (logit models) -------------------------------------
+// hist_stats (1): the chain's switch, a word of the handle: 0 off, B in [HIST_BINS_MIN, HIST_BINS_MAX] on with B bins; B
+// belongs to the handle.  hist_count (1): the chain's count of accumulated iterations.  hist_counts (B n): the chain's
+// histograms bin-major [bin][site] as doubles (32-bit counts: exact).  The first switch-on allocates; switching on zeroes
+// the chain's part; 0 keeps everything readable.  The count and the counts are writable while the chain's switch is on
+// (checkpoint restore).  Before the first switch-on every name answers OCC_E_STATE (switching a chain OFF before that is
+// accepted and does nothing).  Nothing of a chain's state changes.  Whether the kernel is launched behind the z update
+// follows "is any chain on"; a change of that, of B or of the histograms' address drops the captured graphs.
+enum : int { HIST_NONE = -1, HIST_SWITCH = 0, HIST_COUNT = 1, HIST_COUNTS = 2 };
+static int hist_field(const std::string &nm)
+{
+    return nm == "hist_stats" ? HIST_SWITCH : nm == "hist_count" ? HIST_COUNT : nm == "hist_counts" ? HIST_COUNTS : HIST_NONE;
+}
+static int hist_refused(occ_sampler *s)
+{
+    if (s->probit) return set_error(s, OCC_E_STATE, "per-site intervals are not available for the probit model");
+    return set_error(s, OCC_E_STATE, "per-site intervals have not been switched on for this handle (set hist_stats first)");
+}
+// The histograms for B bins: at the handle's first switch-on, and again for another B while every chain is off (the old ones
+// are freed: nothing is in flight to them, both streams have been waited for).  Every chain's counts start at zero.
+static int hist_alloc(occ_sampler *s, int B)
+{
+    Ctx &c = s->ctx;
+    occ_sampler::Hist &hs = s->hist;
+    int rc;
+    WAIT_TRY(s->stream);
+    destroy_graph(s);  // (the addresses and B travel by value in the captured launches)
+    for (uint32_t **old : {&hs.args.cnt, &hs.snap}) {
+        if (!*old) continue;
+        s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), (void *)*old), s->allocs.end());
+        HIP_TRY(hipFree(*old));
+        *old = nullptr;
+    }
+    hs.snapped = false;
+    hs.args.n = c.n, hs.args.p = c.p, hs.args.B = B;
+    hs.args.Xt = c.Xt, hs.args.eta = c.eta;
+    if ((rc = dev_alloc(s, &hs.args.cnt, hs.words(c.C)))) return rc;
+    if (!hs.ready) {
+        if ((rc = dev_alloc(s, &hs.args.count, (size_t)c.C))) return rc;
+        if ((rc = dev_alloc(s, &hs.on_dev, (size_t)c.C))) return rc;
+        hs.on.assign((size_t)c.C, 0u);
+        hs.bound.assign((size_t)c.C, 0ull);
+        hs.args.on = hs.on_dev;
+    } else {
+        HIP_TRY(fill_on(s, hs.args.count, 0, sizeof(uint32_t) * (size_t)c.C));
+        hs.bound.assign((size_t)c.C, 0ull);
+    }
+    hs.ready = true;
+    return OCC_OK;
+}
+static int get_hist_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
+{
+    const occ_sampler::Hist &hs = s->hist;
+    if (s->probit || !hs.ready) return hist_refused(s);
+    if (field == HIST_SWITCH) {
+        v.assign(1, hs.on[(size_t)chain] ? (double)hs.args.B : 0.0);
+        return OCC_OK;
+    }
+    const size_t per = field == HIST_COUNT ? (size_t)1 : (size_t)hs.args.B * (size_t)hs.args.n;
+    const uint32_t *src = field == HIST_COUNT ? hs.args.count + chain : hs.args.cnt + (size_t)chain * per;
+    std::vector<uint32_t> w(per);
+    HIP_TRY(copy_on(s, w.data(), src, sizeof(uint32_t) * per, hipMemcpyDeviceToHost));
+    v.assign(w.begin(), w.end());
+    return OCC_OK;
+}
+static int set_hist_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+{
+    occ_sampler::Hist &hs = s->hist;
+    if (s->probit) return hist_refused(s);
+    if (field != HIST_SWITCH) {
+        if (!hs.ready) return hist_refused(s);
+        if (!hs.on[(size_t)chain]) return set_error(s, OCC_E_STATE, "per-site intervals are switched off for this chain (set hist_stats first)");
+        const size_t per = field == HIST_COUNT ? (size_t)1 : (size_t)hs.args.B * (size_t)hs.args.n;
+        if ((size_t)len != per) return set_error(s, OCC_E_STATE, "wrong length");
+        std::vector<uint32_t> w(per);
+        uint64_t top = 0;
+        for (size_t k = 0; k < per; ++k) {
+            if (!(in[k] >= 0.0) || !(in[k] < 0x1.0p32) || in[k] != std::floor(in[k]))
+                return set_error(s, OCC_E_BADARG, "hist_count and hist_counts are whole numbers in [0, 2^32)");
+            w[k] = (uint32_t)in[k];
+            top = std::max<uint64_t>(top, w[k]);
+        }
+        uint32_t *dst = field == HIST_COUNT ? hs.args.count + chain : hs.args.cnt + (size_t)chain * per;
+        HIP_TRY(copy_on(s, dst, w.data(), sizeof(uint32_t) * per, hipMemcpyHostToDevice));
+        hs.bound[(size_t)chain] = std::max(hs.bound[(size_t)chain], top);  // (still an upper bound on every count of the chain)
+        return OCC_OK;
+    }
+    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
+    const double b = in[0];
+    if (b != 0.0 && !(b >= (double)HIST_BINS_MIN && b <= (double)HIST_BINS_MAX && b == std::floor(b)))
+        return set_error(s, OCC_E_BADARG, "hist_stats is 0 or a number of bins from 4 to 1024");
+    const int B = (int)b;
+    if (B == 0 && !hs.ready) return OCC_OK;  // never switched on: nothing to switch off
+    int rc;
+    WAIT_TRY(s->side);
+    if (B != 0 && hs.ready && B != hs.args.B && hs.any)
+        return set_error(s, OCC_E_BADARG, ("the handle's per-site histograms have " + std::to_string(hs.args.B) +
+                                           " bins while a chain is switched on: switch every chain off before asking for another number").c_str());
+    if (B != 0 && (!hs.ready || B != hs.args.B) && (rc = hist_alloc(s, B))) return rc;
+    if (B != 0) {  // switching on zeroes the chain's part, as site_stats does
+        const size_t per = (size_t)B * (size_t)hs.args.n;
+        HIP_TRY(fill_on(s, hs.args.cnt + (size_t)chain * per, 0, sizeof(uint32_t) * per));
+        HIP_TRY(fill_on(s, hs.args.count + chain, 0, sizeof(uint32_t)));
+        hs.bound[(size_t)chain] = 0ull;
+    }
+    hs.on[(size_t)chain] = B != 0 ? 1u : 0u;
+    HIP_TRY(copy_on(s, hs.on_dev, hs.on.data(), sizeof(uint32_t) * hs.on.size(), hipMemcpyHostToDevice));
+    uint32_t any = 0u;
+    for (uint32_t o : hs.on) any |= o;
+    if (any != hs.any) destroy_graph(s);
+    hs.any = any;
+    return OCC_OK;
+}
+
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len)
 {
     if (!s || !name || !len) return OCC_E_BADARG;
@@ -3367,6 +3530,10 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     if (moran_field(nm) != MORAN_NONE) {
         const int mrc = get_moran_state(s, chain, moran_field(nm), v);
         return mrc ? mrc : give_state(s, v, out, cap, len);
+    }
+    if (hist_field(nm) != HIST_NONE) {
+        const int hrc = get_hist_state(s, chain, hist_field(nm), v);
+        return hrc ? hrc : give_state(s, v, out, cap, len);
     }
     int sums_kind = SUMS_SITE;
     const int site_q = site_field(nm, &sums_kind);
@@ -3436,6 +3603,7 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     if (region_field(nm) != REGION_NONE) return set_region_state(s, chain, region_field(nm), in, len);
     if (ppc_field(nm) != PPC_NONE) return set_ppc_state(s, chain, ppc_field(nm), in, len);
     if (moran_field(nm) != MORAN_NONE) return set_moran_state(s, chain, moran_field(nm), in, len);
+    if (hist_field(nm) != HIST_NONE) return set_hist_state(s, chain, hist_field(nm), in, len);
     int sums_kind = SUMS_SITE;
     const int sums_q = site_field(nm, &sums_kind);
     if (sums_q != SITE_NONE) return set_site_state(s, chain, sums_kind, sums_q, in, len);
@@ -3607,6 +3775,7 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     // handle is replayed here)
     Scoped<uint32_t> plain_z_ob(&s->outputs_on, 0u);
     Scoped<uint32_t> no_spatial(&s->spatial.any, 0u);
+    Scoped<uint32_t> no_hist(&s->hist.any, 0u);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops
     if (rc) return rc;
     // The fused iteration kernel first, IN SITU: `reps` real iterations continue the chains from where they are

@@ -13,6 +13,7 @@ from .. import _lib
 from .._problem import FlatProblem, default_start
 from ..chain import Chain
 from ..data import Data
+from ..intervals import interval_bins
 from ..posterior import PosteriorParameter
 from ..ppc import ppc_flag
 from ..regions import region_ids
@@ -118,7 +119,7 @@ class GibbsBase:
         return self.chain
 
     def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False, waic=False, regions=None,
-               ppc=False, spatial_check=False):
+               ppc=False, spatial_check=False, site_intervals=False):
         """Draw ``size`` iterations per chain and return the kept ``alpha``, ``beta``, ``tau`` draws.
 
         Same contract as the reference (``base.py:243-291``): ``burnin < size`` else ``ValueError``;
@@ -147,7 +148,13 @@ class GibbsBase:
         ``spatial_check=True`` (likewise): per kept draw the device forms Moran's I of the occupancy residuals
         ``z - psi`` and of one replicate of them; ``out.spatial_check`` is a
         :class:`~occuspytial_amd.spatial.SpatialCheck` (tail probability, excess autocorrelation; ``None`` otherwise).
+
+        ``site_intervals=True`` (likewise; or a number of bins from 4 to 1024, ``True`` is 64): over the kept iterations
+        the device keeps, per site, a histogram of the occupancy probability psi; ``out.site_intervals`` is a
+        :class:`~occuspytial_amd.intervals.SiteIntervals` (credible intervals, quantiles and exceedance probabilities of
+        psi per site, to within one bin; ``None`` otherwise).
         """
+        bins = interval_bins(site_intervals)
         if burnin >= size:
             raise ValueError('burnin value cannot be larger than sample size')
         if chains < 1:
@@ -166,6 +173,9 @@ class GibbsBase:
         if spatial_flag(spatial_check):
             self._refuse_spatial_check()
             extra['spatial_check'] = True
+        if bins:
+            self._refuse_site_intervals()
+            extra['site_intervals'] = bins
         samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start,
                                   progressbar=progressbar, **extra)
         out = PosteriorParameter(*samples)
@@ -178,6 +188,8 @@ class GibbsBase:
             out.ppc = self.__dict__.pop('_ppc')
         if 'spatial_check' in extra:
             out.spatial_check = self.__dict__.pop('_spatial_check')
+        if 'site_intervals' in extra:
+            out.site_intervals = self.__dict__.pop('_site_intervals')
         return out
 
     def _refuse_ppc(self):
@@ -191,6 +203,12 @@ class GibbsBase:
         if not hasattr(self, '_run_chains'):
             raise NotImplementedError(f'{self.__class__.__name__} steps in Python: the spatial residual check is formed by '
                                       'the device engine only')
+
+    def _refuse_site_intervals(self):
+        """The histograms are kept on the device behind the engine's z update: a sampler with a Python ``step`` has none."""
+        if not hasattr(self, '_run_chains'):
+            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: site intervals are accumulated by the '
+                                      'device engine only')
 
     def _refuse_regions(self):
         """The occupied sites per region are counted by the engine's z update: a sampler with a Python ``step`` has none."""

@@ -4,6 +4,7 @@ import numpy as np
 from .. import _lib
 from .._engine import Engine, EngineGroup
 from ..chain import Chain
+from ..intervals import SiteIntervals, interval_bins
 from ..ppc import PredictiveCheck, ppc_flag
 from ..regions import region_ids
 from ..sites import SiteSummary
@@ -153,8 +154,14 @@ class LogitICARGibbs(GibbsBase):
         except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
             raise ValueError(f'the loaded engine library has no spatial residual check ({exc}): rebuild it') from None
 
+    def _hist_switch(self, eng, bins):
+        try:
+            eng.hist_stats(bins)
+        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
+            raise ValueError(f'the loaded engine library has no site intervals ({exc}): rebuild it') from None
+
     def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False, regions=None, ppc=False,
-               spatial_check=False):
+               spatial_check=False, site_intervals=False):
         """Continue the chains of ``checkpoint`` (a dict from :meth:`checkpoint` or the path of its ``.npz``)
         for ``size`` more iterations on this sampler's problem.  Returns a ``PosteriorParameter`` of the new
         draws; every chain's ``Chain`` is the continuation (use ``Chain.expand`` / ``append`` to join them to
@@ -164,9 +171,13 @@ class LogitICARGibbs(GibbsBase):
         log-likelihood sums and the result's ``waic``.  ``regions`` (as in :meth:`sample`): the occupied sites per region of
         the new draws, ``out['occupied']`` and ``out.regions``; the draws belong to a call, so nothing of them is carried.
         ``ppc=True``: the posterior predictive check of the new draws, ``out.ppc``; likewise nothing of it is carried.
-        ``spatial_check=True``: the spatial residual check of the new draws, ``out.spatial_check``; likewise."""
+        ``spatial_check=True``: the spatial residual check of the new draws, ``out.spatial_check``; likewise.
+        ``site_intervals`` (as in :meth:`sample`): the per-site histograms of psi go on from those the checkpoint holds
+        (from zero if it holds none, or holds another number of bins); ``out.site_intervals`` covers every iteration
+        accumulated so far."""
         from ..posterior import PosteriorParameter
         from tqdm.auto import tqdm
+        bins = interval_bins(site_intervals)
         if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, '__fspath__'):
             with np.load(checkpoint) as f:
                 checkpoint = {k: f[k] for k in f.files}
@@ -181,6 +192,8 @@ class LogitICARGibbs(GibbsBase):
         spatial_check = spatial_flag(spatial_check)
         if spatial_check:
             self._refuse_spatial_check()
+        if bins:
+            self._refuse_site_intervals()
         C = int(checkpoint['n_chains'])
         self.__dict__['_stepping'] = False
         eng = self._get_engine([int(k) for k in np.asarray(checkpoint['keys'])])
@@ -203,6 +216,11 @@ class LogitICARGibbs(GibbsBase):
             moran_rows = np.zeros((C, size, 8))
         elif getattr(eng, '_moran_on', False):   # (the checkpoint's switch was on: this call did not ask)
             eng.moran_stats(False)
+        if bins:
+            if getattr(eng, '_hist_bins', 0) != bins:   # (the checkpoint holds none, or of another number of bins: from zero)
+                self._hist_switch(eng, bins)
+        elif getattr(eng, '_hist_bins', 0):   # (the checkpoint's switch was on: this call did not ask)
+            eng.hist_stats(0)
         alpha = np.zeros((C, size, self._problem.q))
         beta = np.zeros((C, size, self._problem.p))
         tau = np.zeros((C, size))
@@ -235,11 +253,13 @@ class LogitICARGibbs(GibbsBase):
             out.ppc = PredictiveCheck.from_problem(self._problem, ppc_rows)
         if spatial_check:
             out.spatial_check = SpatialCheck.from_problem(self._problem, moran_rows)
+        if bins:
+            out.site_intervals = SiteIntervals.from_engine(eng)
         return out
 
     # ------------------------------------------------------------------ batched chains
     def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False, waic=False, regions=None,
-                    ppc=False, spatial_check=False):
+                    ppc=False, spatial_check=False, site_intervals=False):
         """All chains of one ``sample`` call as one device batch.
 
         Mirrors ``GibbsBase._run`` (base.py:214-241) per chain: start values from the chain's own
@@ -256,6 +276,10 @@ class LogitICARGibbs(GibbsBase):
         ``spatial_check``: the spatial residual check, switched in the same way; every chunk's rows are appended and the
         :class:`~occuspytial_amd.spatial.SpatialCheck` made of them is left for ``sample``.  With the default no call about
         it reaches the engine.
+        ``site_intervals`` (a number of bins, or False): the per-site histograms of psi, switched as the site sums are -- off
+        during burn-in chunks, on (which zeroes them) before the first chunk that keeps a draw; they accumulate on the
+        device and the :class:`~occuspytial_amd.intervals.SiteIntervals` read from the engine at the end is left for
+        ``sample``.  With the default no call about them reaches the engine.
         """
         from tqdm.auto import tqdm
 
@@ -282,6 +306,8 @@ class LogitICARGibbs(GibbsBase):
             self._ppc_switch(eng, False)
         if spatial_check or getattr(eng, '_moran_on', False):   # (likewise)
             self._moran_switch(eng, False)
+        if site_intervals or getattr(eng, '_hist_bins', 0):   # (likewise)
+            self._hist_switch(eng, 0)
         sums_on = False
 
         C = len(samplers)
@@ -310,6 +336,8 @@ class LogitICARGibbs(GibbsBase):
                         eng.ppc_stats(True)
                     if spatial_check:
                         eng.moran_stats(True)
+                    if site_intervals:
+                        eng.hist_stats(site_intervals)
                     sums_on = True
                 a_, b_, t_ = eng.run(step, b)
                 m = step - b
@@ -340,6 +368,8 @@ class LogitICARGibbs(GibbsBase):
             self.__dict__['_ppc'] = PredictiveCheck.from_problem(self._problem, ppc_rows)
         if spatial_check:
             self.__dict__['_spatial_check'] = SpatialCheck.from_problem(self._problem, moran_rows)
+        if site_intervals:
+            self.__dict__['_site_intervals'] = SiteIntervals.from_engine(eng)
         return chains
 
 
