@@ -260,7 +260,34 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  * off before that is accepted), and a probit handle answers them with OCC_E_STATE, "per-site intervals are not available for
  * the probit model".  Nothing is redrawn; occ_set_start and occ_set_keys do not touch them; a call that is re-run after a
  * device-side wait gave up counts nothing twice; occ_profile and the occ_cond_* entry points never count.  alpha, beta, tau,
- * eta, z, every sum and every record above are bit-identical with the switch on or off. */
+ * eta, z, every sum and every record above are bit-identical with the switch on or off.
+ *
+ * Per-site convergence diagnostics (logit models; ICAR and reduced rank): have the chains converged at a site?  R-hat needs
+ * each chain's mean and variance, ESS and the Monte-Carlo standard error need the variance of batch means: a handful of
+ * running sums per site; the draws are not needed.  Per iteration past the call's burn-in -- the rule of the per-site
+ * intervals above, so occ_step counts as well -- of a chain whose switch is on, one kernel launched directly behind the z
+ * update does, per site i and for v = psi_i = expit(x_i beta + eta_i) and for v = eta_i (reduced rank: K theta), with
+ * m = cnt the site's own count and L the batch length:
+ *   if (m == 0) ref = v;   d = v - ref;   s1 += d;   s2 += d d;   run += d;   if ((m + 1) % L == 0) { bsq += run run; run = 0; }
+ * then cnt = m + 1, and it adds 1 to the chain's count of accumulated iterations.  A column belongs to one thread and
+ * additions run in iteration order: the same values whatever the path, the placement, the block size or the split into
+ * calls (an unfinished batch stays in `run` across calls).  88 bytes per site and chain.
+ *   conv_stats(1)
+ *       a word of the handle per chain: 0 is off, L with 1 <= L <= 2^30 is on with batch length L, any other value is
+ *       OCC_E_BADARG.  It is not one of the z update's outputs above.  The first switch-on allocates; switching on ZEROES the
+ *       chain's sums and count; 0 keeps everything readable.  L belongs to the handle: a chain that asks for another L while
+ *       any chain is on gets OCC_E_BADARG (the message names the handle's L); with every chain off a new L is accepted.
+ *   conv_count(1)
+ *       the chain's count of accumulated iterations.
+ *   conv_sums(11 n)
+ *       the chain's sums, slot-major [slot][site]: cnt, then ref, s1, s2, run, bsq of psi, then the same five of eta.
+ * conv_count and conv_sums are writable while the chain's switch is on (checkpoint restore): the count and every cnt are
+ * whole numbers >= 0 and every cnt of a written conv_sums is the same, OCC_E_BADARG otherwise.  All three names answer
+ * OCC_E_STATE before the handle's first switch-on (switching a chain off before that is accepted), and a probit handle answers
+ * them with OCC_E_STATE, "per-site convergence diagnostics are not available for the probit model".  Nothing is redrawn;
+ * occ_set_start and occ_set_keys do not touch them; a call that is re-run after a device-side wait gave up counts nothing
+ * twice; occ_profile and the occ_cond_* entry points never count.  alpha, beta, tau, eta, z, every sum and every record above
+ * are bit-identical with the switch on or off. */
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len);
 int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double *in, int64_t len);
 

@@ -126,6 +126,9 @@ class Engine:
         # per-site intervals: the number of bins while switched on, 0 while off; until it is first set, no call about them
         # reaches the library
         self._hist_bins = 0
+        # per-site convergence diagnostics: the batch length while switched on, 0 while off; likewise
+        self._conv_batch = 0
+        self._conv_last = 0   # (the batch length of the sums that stay readable after switching off)
         _LIVE.add(self)
         return self
 
@@ -229,6 +232,11 @@ class Engine:
             out['hist_stats'] = np.full(self.n_chains, float(self._hist_bins))
             out['hist_count'] = np.array([p['count'] for p in parts], dtype=np.int64)
             out['hist_counts'] = np.stack([p['counts'] for p in parts])
+        if self._conv_batch:   # the switch (the batch length), the counts of accumulated iterations and the batch-means sums
+            parts = [self.conv_sums(c) for c in range(self.n_chains)]
+            out['conv_stats'] = np.full(self.n_chains, float(self._conv_batch))
+            out['conv_count'] = np.array([p['count'] for p in parts], dtype=np.int64)
+            out['conv_sums'] = np.stack([p['sums'] for p in parts])
         return out
 
     def restore(self, ckpt):
@@ -277,6 +285,35 @@ class Engine:
                 self.set('hist_counts', np.asarray(ckpt['hist_counts'])[c].ravel(), c)
         elif self._hist_bins:
             self.hist_stats(0)
+        if 'conv_stats' in ckpt and np.all(np.asarray(ckpt['conv_stats']) != 0):
+            self.conv_stats(int(np.asarray(ckpt['conv_stats']).ravel()[0]))
+            for c in range(self.n_chains):
+                self.set('conv_count', float(np.asarray(ckpt['conv_count'])[c]), c)
+                self.set('conv_sums', np.asarray(ckpt['conv_sums'], dtype=np.float64)[c].ravel(), c)
+        elif self._conv_batch:
+            self.conv_stats(0)
+
+    # ---- per-site convergence diagnostics (state names conv_*, include/occ_gibbs.h) ----
+    def conv_stats(self, batch):
+        """Switch the per-site batch-means sums of every chain: ``batch`` from 1 to 2^30 is on with that batch length (which
+        ZEROES them and their counts), 0 or False is off (they stay readable).  While on, every iteration past a call's
+        burn-in updates the sums of psi and of eta at every site (:meth:`conv_sums`).  The batch length belongs to the
+        handle: for another one every chain is switched off first."""
+        batch = int(batch)
+        if batch and self._conv_batch and batch != self._conv_batch:
+            self.conv_stats(0)
+        for c in range(self.n_chains):
+            self.set('conv_stats', float(batch), c)
+        self._conv_batch = batch
+        self._conv_last = batch or self._conv_last
+
+    def conv_sums(self, chain=0):
+        """``{'batch': L, 'count': iterations accumulated, 'sums': (11, n) float64}`` of one chain: per site ``cnt``, then
+        ``ref, s1, s2, run, bsq`` of psi, then the same five of eta."""
+        batch = self._conv_batch or self._conv_last   # (neither is set when the switch was set by name: ask the handle)
+        batch = batch or int(max(self.get('conv_stats', c)[0] for c in range(self.n_chains)))
+        return {'batch': batch, 'count': int(self.get('conv_count', chain)[0]),
+                'sums': self.get('conv_sums', chain).reshape(11, self.prob.n)}
 
     # ---- per-site intervals (state names hist_*, include/occ_gibbs.h) ----
     def hist_stats(self, bins):
@@ -614,6 +651,19 @@ class EngineGroup:
     def hist_counts(self, chain=0):
         g, i = self.where[chain]
         return self.engines[g].hist_counts(i)
+
+    # per-site convergence diagnostics: the switch on every device, the sums routed by chain
+    @property
+    def _conv_batch(self):
+        return max(getattr(e, '_conv_batch', 0) for e in self.engines)
+
+    def conv_stats(self, batch):
+        for e in self.engines:
+            e.conv_stats(batch)
+
+    def conv_sums(self, chain=0):
+        g, i = self.where[chain]
+        return self.engines[g].conv_sums(i)
 
     # (the entry points by name are Engine's own: each only names its kind)
     site_stats, site_sums, loglik_stats, loglik_sums = Engine.site_stats, Engine.site_sums, Engine.loglik_stats, Engine.loglik_sums

@@ -30,6 +30,9 @@ MORAN_FIELDS = ('moran_stats', 'moran_draws')
 # per-site intervals: the chain's switch (a word of the handle: 0 off, B on with B bins), its count of accumulated iterations,
 # its histograms of psi (B n, bin-major)
 HIST_FIELDS = ('hist_stats', 'hist_count', 'hist_counts')
+# per-site convergence diagnostics: the chain's switch (a word of the handle: 0 off, L on with batch length L), its count of
+# accumulated iterations, its batch-means sums (11 n, slot-major: cnt, then ref, s1, s2, run, bsq of psi, then of eta)
+CONV_FIELDS = ('conv_stats', 'conv_count', 'conv_sums')
 KERNEL_KINDS = ('omega_b', 'noise', 'eta_init', 'minres', 'beta_partial', 'omega_a', 'alpha_draw', 'z_ob', 'iter')
 
 

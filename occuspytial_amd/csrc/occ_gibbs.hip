@@ -25,6 +25,7 @@
 #include "occ_probit.hpp"
 #include "occ_spatial.hpp"
 #include "occ_hist.hpp"
+#include "occ_conv.hpp"
 #include "occ_layout.hpp"
 
 using namespace occ;
@@ -196,6 +197,21 @@ struct occ_sampler {
         HistArgs args{};
         size_t words(int C) const { return (size_t)C * (size_t)args.B * (size_t)args.n; }
     } hist;
+    // Per-site convergence diagnostics (state names conv_stats, conv_count, conv_sums; logit models; occ_conv.hpp).  ready: a
+    // chain has been switched on once -- the sums [11][C n], the counts [C] and the switches are on the device.  The batch
+    // length L belongs to the handle.  The switch is a word of the handle per chain (on, on_dev), as the per-site intervals';
+    // any: their OR, which decides whether the kernel is launched behind the z update (baked into captured graphs with L and
+    // the addresses: a change drops them).  snap: [11 C n] sums, then [C] counts, part of what a call is re-run from; snapped:
+    // taken for the running call.
+    struct Conv {
+        bool ready = false, snapped = false;
+        uint32_t any = 0u;
+        std::vector<uint32_t> on;
+        uint32_t *on_dev = nullptr;
+        double *snap = nullptr;
+        ConvArgs args{};
+        size_t words() const { return (size_t)CONV_SLOTS * args.Cn; }
+    } conv;
     std::vector<ChainScalars> snap_sc;
     // fixed problem arrays on the device, in upload order: what a group broadcasts from its root (occ_create_group /
     // occ_create_distributed); defer_fixed: allocate only, the bytes arrive by broadcast
@@ -659,6 +675,8 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
                 sp_launch(s->spatial.args, s->ctx.sc, c.C, e, st);
             if (s->hist.any)  // the per-site intervals, likewise
                 hist_launch(s->hist.args, s->ctx.sc, c.C, e, st);
+            if (s->conv.any)  // the per-site convergence diagnostics, likewise
+                conv_launch(s->conv.args, s->ctx.sc, c.C, e, st);
             break;
     }
     const hipError_t le = hipGetLastError();
@@ -996,6 +1014,14 @@ int open_window(occ_sampler *s, int64_t n_iter, int64_t burnin, int64_t keep, bo
             if (!hs.snap && (rc = dev_alloc(s, &hs.snap, nw + (size_t)c.C, false))) return rc;
             HIP_TRY(hipMemcpyAsync(hs.snap, hs.args.cnt, sizeof(uint32_t) * nw, hipMemcpyDeviceToDevice, s->stream));
             HIP_TRY(hipMemcpyAsync(hs.snap + nw, hs.args.count, sizeof(uint32_t) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
+        }
+        occ_sampler::Conv &cv = s->conv;  // ... and the sums of the per-site convergence diagnostics
+        cv.snapped = cv.any != 0u;
+        if (cv.snapped) {
+            const size_t nw = cv.words();
+            if (!cv.snap && (rc = dev_alloc(s, &cv.snap, nw + (size_t)c.C, false))) return rc;
+            HIP_TRY(hipMemcpyAsync(cv.snap, cv.args.sums, sizeof(double) * nw, hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(cv.snap + nw, cv.args.count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
         }
         hipLaunchKernelGGL(k_snapshot, dim3((unsigned)std::min<size_t>((Cn + 255) / 256, 2048)), dim3(256), 0, s->stream, c.eta, s->snap_eta, c.z, s->snap_z, c.Xv, s->snap_x,
                            (unsigned long long)Cn, s->rsr.m > 0 ? s->rsr.theta : nullptr, s->snap_theta, (unsigned long long)c.C * (unsigned long long)std::max(s->rsr.m, 0),
@@ -2909,6 +2935,11 @@ static int fallback_to_launch_per_step(occ_sampler *s)
         HIP_TRY(copy_on(s, s->hist.args.cnt, s->hist.snap, sizeof(uint32_t) * nw, hipMemcpyDeviceToDevice));
         HIP_TRY(copy_on(s, s->hist.args.count, s->hist.snap + nw, sizeof(uint32_t) * (size_t)c.C, hipMemcpyDeviceToDevice));
     }
+    if (s->conv.snapped) {
+        const size_t nw = s->conv.words();
+        HIP_TRY(copy_on(s, s->conv.args.sums, s->conv.snap, sizeof(double) * nw, hipMemcpyDeviceToDevice));
+        HIP_TRY(copy_on(s, s->conv.args.count, s->conv.snap + nw, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
+    }
     for (auto &sc : s->snap_sc) sc.err = 0;
     if ((rc = write_scalars(s, s->snap_sc))) return rc;
     s->parity = s->snap_parity;
@@ -3508,6 +3539,116 @@ static int set_hist_state(occ_sampler *s, int chain, int field, const double *in
     return OCC_OK;
 }
 
+// ---- occ_get_state / occ_set_state of the per-site convergence diagnostics' names (logit models) ------------------------
+// conv_stats (1): the chain's switch, a word of the handle: 0 off, L in [1, 2^30] on with batch length L; L belongs to the
+// handle.  conv_count (1): the chain's count of accumulated iterations.  conv_sums (11 n): the chain's slots, slot-major
+// [slot][site].  The first switch-on allocates; switching on zeroes the chain's part; 0 keeps everything readable.  The count
+// and the sums are writable while the chain's switch is on (checkpoint restore).  Before the first switch-on every name
+// answers OCC_E_STATE (switching a chain OFF before that is accepted and does nothing).  Nothing of a chain's state changes.
+// Whether the kernel is launched behind the z update follows "is any chain on"; a change of that, of L or of the sums'
+// address drops the captured graphs.
+enum : int { CONV_NONE = -1, CONV_SWITCH = 0, CONV_COUNT = 1, CONV_SUMS = 2 };
+static int conv_field(const std::string &nm)
+{
+    return nm == "conv_stats" ? CONV_SWITCH : nm == "conv_count" ? CONV_COUNT : nm == "conv_sums" ? CONV_SUMS : CONV_NONE;
+}
+static int conv_refused(occ_sampler *s)
+{
+    if (s->probit) return set_error(s, OCC_E_STATE, "per-site convergence diagnostics are not available for the probit model");
+    return set_error(s, OCC_E_STATE, "per-site convergence diagnostics have not been switched on for this handle (set conv_stats first)");
+}
+// The sums, at the handle's first switch-on: their size does not depend on L, so they are allocated once.
+static int conv_alloc(occ_sampler *s)
+{
+    Ctx &c = s->ctx;
+    occ_sampler::Conv &cv = s->conv;
+    int rc;
+    WAIT_TRY(s->stream);
+    destroy_graph(s);  // (the addresses and L travel by value in the captured launches)
+    cv.args.n = c.n, cv.args.p = c.p;
+    cv.args.Cn = (size_t)c.C * (size_t)c.n;
+    cv.args.Xt = c.Xt, cv.args.eta = c.eta;
+    if ((rc = dev_alloc(s, &cv.args.sums, cv.words()))) return rc;
+    if ((rc = dev_alloc(s, &cv.args.count, (size_t)c.C))) return rc;
+    if ((rc = dev_alloc(s, &cv.on_dev, (size_t)c.C))) return rc;
+    cv.on.assign((size_t)c.C, 0u);
+    cv.args.on = cv.on_dev;
+    cv.ready = true;
+    return OCC_OK;
+}
+static int get_conv_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
+{
+    const occ_sampler::Conv &cv = s->conv;
+    if (s->probit || !cv.ready) return conv_refused(s);
+    if (field == CONV_SWITCH) {
+        v.assign(1, cv.on[(size_t)chain] ? (double)cv.args.L : 0.0);
+        return OCC_OK;
+    }
+    if (field == CONV_COUNT) {
+        v.resize(1);
+        HIP_TRY(copy_on(s, v.data(), cv.args.count + chain, sizeof(double), hipMemcpyDeviceToHost));
+        return OCC_OK;
+    }
+    const size_t n = (size_t)cv.args.n;
+    v.resize((size_t)CONV_SLOTS * n);
+    for (int k = 0; k < CONV_SLOTS; ++k)  // the chain's part of every slot
+        HIP_TRY(copy_on(s, v.data() + (size_t)k * n, cv.args.sums + (size_t)k * cv.args.Cn + (size_t)chain * n, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return OCC_OK;
+}
+static int set_conv_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+{
+    occ_sampler::Conv &cv = s->conv;
+    if (s->probit) return conv_refused(s);
+    const auto whole = [](double x) { return x >= 0.0 && x < 0x1.0p53 && x == std::floor(x); };
+    if (field != CONV_SWITCH) {
+        if (!cv.ready) return conv_refused(s);
+        if (!cv.on[(size_t)chain]) return set_error(s, OCC_E_STATE, "per-site convergence diagnostics are switched off for this chain (set conv_stats first)");
+        const size_t n = (size_t)cv.args.n;
+        if ((size_t)len != (field == CONV_COUNT ? (size_t)1 : (size_t)CONV_SLOTS * n)) return set_error(s, OCC_E_STATE, "wrong length");
+        if (field == CONV_COUNT) {
+            if (!whole(in[0])) return set_error(s, OCC_E_BADARG, "conv_count is a whole number >= 0");
+            HIP_TRY(copy_on(s, cv.args.count + chain, in, sizeof(double), hipMemcpyHostToDevice));
+            return OCC_OK;
+        }
+        for (size_t i = 0; i < n; ++i)  // slot 0 is cnt: the sites of a chain have counted the same iterations
+            if (!whole(in[i]) || in[i] != in[0])
+                return set_error(s, OCC_E_BADARG, "the cnt slot of conv_sums holds one whole number >= 0 at every site");
+        for (int k = 0; k < CONV_SLOTS; ++k)
+            HIP_TRY(copy_on(s, cv.args.sums + (size_t)k * cv.args.Cn + (size_t)chain * n, in + (size_t)k * n, sizeof(double) * n, hipMemcpyHostToDevice));
+        return OCC_OK;
+    }
+    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
+    const double b = in[0];
+    if (b != 0.0 && !(b >= 1.0 && b <= (double)CONV_BATCH_MAX && b == std::floor(b)))
+        return set_error(s, OCC_E_BADARG, "conv_stats is 0 or a batch length from 1 to 2^30");
+    const int L = (int)b;
+    if (L == 0 && !cv.ready) return OCC_OK;  // never switched on: nothing to switch off
+    int rc;
+    WAIT_TRY(s->side);
+    if (L != 0 && cv.ready && L != cv.args.L && cv.any)
+        return set_error(s, OCC_E_BADARG, ("the handle's per-site convergence diagnostics have batch length " + std::to_string(cv.args.L) +
+                                           " while a chain is switched on: switch every chain off before asking for another length").c_str());
+    if (L != 0 && !cv.ready && (rc = conv_alloc(s))) return rc;
+    if (L != 0) {  // switching on zeroes the chain's part, as site_stats does
+        if (L != cv.args.L) {
+            WAIT_TRY(s->stream);
+            destroy_graph(s);
+            cv.args.L = L;
+        }
+        const size_t n = (size_t)cv.args.n;
+        for (int k = 0; k < CONV_SLOTS; ++k)
+            HIP_TRY(fill_on(s, cv.args.sums + (size_t)k * cv.args.Cn + (size_t)chain * n, 0, sizeof(double) * n));
+        HIP_TRY(fill_on(s, cv.args.count + chain, 0, sizeof(double)));
+    }
+    cv.on[(size_t)chain] = L != 0 ? 1u : 0u;
+    HIP_TRY(copy_on(s, cv.on_dev, cv.on.data(), sizeof(uint32_t) * cv.on.size(), hipMemcpyHostToDevice));
+    uint32_t any = 0u;
+    for (uint32_t o : cv.on) any |= o;
+    if (any != cv.any) destroy_graph(s);
+    cv.any = any;
+    return OCC_OK;
+}
+
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len)
 {
     if (!s || !name || !len) return OCC_E_BADARG;
@@ -3534,6 +3675,10 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     if (hist_field(nm) != HIST_NONE) {
         const int hrc = get_hist_state(s, chain, hist_field(nm), v);
         return hrc ? hrc : give_state(s, v, out, cap, len);
+    }
+    if (conv_field(nm) != CONV_NONE) {
+        const int crc = get_conv_state(s, chain, conv_field(nm), v);
+        return crc ? crc : give_state(s, v, out, cap, len);
     }
     int sums_kind = SUMS_SITE;
     const int site_q = site_field(nm, &sums_kind);
@@ -3604,6 +3749,7 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     if (ppc_field(nm) != PPC_NONE) return set_ppc_state(s, chain, ppc_field(nm), in, len);
     if (moran_field(nm) != MORAN_NONE) return set_moran_state(s, chain, moran_field(nm), in, len);
     if (hist_field(nm) != HIST_NONE) return set_hist_state(s, chain, hist_field(nm), in, len);
+    if (conv_field(nm) != CONV_NONE) return set_conv_state(s, chain, conv_field(nm), in, len);
     int sums_kind = SUMS_SITE;
     const int sums_q = site_field(nm, &sums_kind);
     if (sums_q != SITE_NONE) return set_site_state(s, chain, sums_kind, sums_q, in, len);
@@ -3776,6 +3922,7 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     Scoped<uint32_t> plain_z_ob(&s->outputs_on, 0u);
     Scoped<uint32_t> no_spatial(&s->spatial.any, 0u);
     Scoped<uint32_t> no_hist(&s->hist.any, 0u);
+    Scoped<uint32_t> no_conv(&s->conv.any, 0u);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops
     if (rc) return rc;
     // The fused iteration kernel first, IN SITU: `reps` real iterations continue the chains from where they are

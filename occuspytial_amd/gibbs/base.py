@@ -12,6 +12,7 @@ from scipy.sparse import csc_matrix, isspmatrix_csc
 from .. import _lib
 from .._problem import FlatProblem, default_start
 from ..chain import Chain
+from ..convergence import diagnostics_batch
 from ..data import Data
 from ..intervals import interval_bins
 from ..posterior import PosteriorParameter
@@ -119,7 +120,7 @@ class GibbsBase:
         return self.chain
 
     def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False, waic=False, regions=None,
-               ppc=False, spatial_check=False, site_intervals=False):
+               ppc=False, spatial_check=False, site_intervals=False, site_diagnostics=False):
         """Draw ``size`` iterations per chain and return the kept ``alpha``, ``beta``, ``tau`` draws.
 
         Same contract as the reference (``base.py:243-291``): ``burnin < size`` else ``ValueError``;
@@ -153,8 +154,14 @@ class GibbsBase:
         the device keeps, per site, a histogram of the occupancy probability psi; ``out.site_intervals`` is a
         :class:`~occuspytial_amd.intervals.SiteIntervals` (credible intervals, quantiles and exceedance probabilities of
         psi per site, to within one bin; ``None`` otherwise).
+
+        ``site_diagnostics=True`` (likewise; or a batch length from 1 to 2^30, ``True`` is ``floor(sqrt(size - burnin))``):
+        over the kept iterations the device keeps, per site, batch-means sums of psi and of the spatial effect eta;
+        ``out.site_diagnostics`` is a :class:`~occuspytial_amd.convergence.SiteDiagnostics` (R-hat across chains, effective
+        sample size and Monte-Carlo standard error per site, and the worst sites; ``None`` otherwise).
         """
         bins = interval_bins(site_intervals)
+        batch = diagnostics_batch(site_diagnostics, size - burnin)
         if burnin >= size:
             raise ValueError('burnin value cannot be larger than sample size')
         if chains < 1:
@@ -176,6 +183,9 @@ class GibbsBase:
         if bins:
             self._refuse_site_intervals()
             extra['site_intervals'] = bins
+        if batch:
+            self._refuse_site_diagnostics()
+            extra['site_diagnostics'] = batch
         samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start,
                                   progressbar=progressbar, **extra)
         out = PosteriorParameter(*samples)
@@ -190,6 +200,8 @@ class GibbsBase:
             out.spatial_check = self.__dict__.pop('_spatial_check')
         if 'site_intervals' in extra:
             out.site_intervals = self.__dict__.pop('_site_intervals')
+        if 'site_diagnostics' in extra:
+            out.site_diagnostics = self.__dict__.pop('_site_diagnostics')
         return out
 
     def _refuse_ppc(self):
@@ -208,6 +220,12 @@ class GibbsBase:
         """The histograms are kept on the device behind the engine's z update: a sampler with a Python ``step`` has none."""
         if not hasattr(self, '_run_chains'):
             raise NotImplementedError(f'{self.__class__.__name__} steps in Python: site intervals are accumulated by the '
+                                      'device engine only')
+
+    def _refuse_site_diagnostics(self):
+        """The batch-means sums are kept on the device behind the engine's z update: a sampler with a Python ``step`` has none."""
+        if not hasattr(self, '_run_chains'):
+            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: site diagnostics are accumulated by the '
                                       'device engine only')
 
     def _refuse_regions(self):

@@ -4,6 +4,7 @@ import numpy as np
 from .. import _lib
 from .._engine import Engine, EngineGroup
 from ..chain import Chain
+from ..convergence import SiteDiagnostics, diagnostics_batch
 from ..intervals import SiteIntervals, interval_bins
 from ..ppc import PredictiveCheck, ppc_flag
 from ..regions import region_ids
@@ -160,8 +161,14 @@ class LogitICARGibbs(GibbsBase):
         except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
             raise ValueError(f'the loaded engine library has no site intervals ({exc}): rebuild it') from None
 
+    def _conv_switch(self, eng, batch):
+        try:
+            eng.conv_stats(batch)
+        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
+            raise ValueError(f'the loaded engine library has no site diagnostics ({exc}): rebuild it') from None
+
     def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False, regions=None, ppc=False,
-               spatial_check=False, site_intervals=False):
+               spatial_check=False, site_intervals=False, site_diagnostics=False):
         """Continue the chains of ``checkpoint`` (a dict from :meth:`checkpoint` or the path of its ``.npz``)
         for ``size`` more iterations on this sampler's problem.  Returns a ``PosteriorParameter`` of the new
         draws; every chain's ``Chain`` is the continuation (use ``Chain.expand`` / ``append`` to join them to
@@ -174,10 +181,14 @@ class LogitICARGibbs(GibbsBase):
         ``spatial_check=True``: the spatial residual check of the new draws, ``out.spatial_check``; likewise.
         ``site_intervals`` (as in :meth:`sample`): the per-site histograms of psi go on from those the checkpoint holds
         (from zero if it holds none, or holds another number of bins); ``out.site_intervals`` covers every iteration
-        accumulated so far."""
+        accumulated so far.
+        ``site_diagnostics`` (as in :meth:`sample`): the per-site batch-means sums go on from those the checkpoint holds,
+        with the checkpoint's batch length whatever is asked for here (from zero if it holds none: ``True`` is then
+        ``floor(sqrt(size))``); ``out.site_diagnostics`` covers every iteration accumulated so far."""
         from ..posterior import PosteriorParameter
         from tqdm.auto import tqdm
         bins = interval_bins(site_intervals)
+        batch = diagnostics_batch(site_diagnostics, size)
         if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, '__fspath__'):
             with np.load(checkpoint) as f:
                 checkpoint = {k: f[k] for k in f.files}
@@ -194,6 +205,8 @@ class LogitICARGibbs(GibbsBase):
             self._refuse_spatial_check()
         if bins:
             self._refuse_site_intervals()
+        if batch:
+            self._refuse_site_diagnostics()
         C = int(checkpoint['n_chains'])
         self.__dict__['_stepping'] = False
         eng = self._get_engine([int(k) for k in np.asarray(checkpoint['keys'])])
@@ -221,6 +234,11 @@ class LogitICARGibbs(GibbsBase):
                 self._hist_switch(eng, bins)
         elif getattr(eng, '_hist_bins', 0):   # (the checkpoint's switch was on: this call did not ask)
             eng.hist_stats(0)
+        if batch:
+            if not getattr(eng, '_conv_batch', 0):   # (the checkpoint holds none: from zero; otherwise its batch length stays)
+                self._conv_switch(eng, batch)
+        elif getattr(eng, '_conv_batch', 0):   # (the checkpoint's switch was on: this call did not ask)
+            eng.conv_stats(0)
         alpha = np.zeros((C, size, self._problem.q))
         beta = np.zeros((C, size, self._problem.p))
         tau = np.zeros((C, size))
@@ -255,11 +273,13 @@ class LogitICARGibbs(GibbsBase):
             out.spatial_check = SpatialCheck.from_problem(self._problem, moran_rows)
         if bins:
             out.site_intervals = SiteIntervals.from_engine(eng)
+        if batch:
+            out.site_diagnostics = SiteDiagnostics.from_engine(eng)
         return out
 
     # ------------------------------------------------------------------ batched chains
     def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False, waic=False, regions=None,
-                    ppc=False, spatial_check=False, site_intervals=False):
+                    ppc=False, spatial_check=False, site_intervals=False, site_diagnostics=False):
         """All chains of one ``sample`` call as one device batch.
 
         Mirrors ``GibbsBase._run`` (base.py:214-241) per chain: start values from the chain's own
@@ -280,6 +300,9 @@ class LogitICARGibbs(GibbsBase):
         during burn-in chunks, on (which zeroes them) before the first chunk that keeps a draw; they accumulate on the
         device and the :class:`~occuspytial_amd.intervals.SiteIntervals` read from the engine at the end is left for
         ``sample``.  With the default no call about them reaches the engine.
+        ``site_diagnostics`` (a batch length, or False): the per-site batch-means sums of psi and eta, switched in the same
+        way; the :class:`~occuspytial_amd.convergence.SiteDiagnostics` read from the engine at the end is left for ``sample``.
+        With the default no call about them reaches the engine.
         """
         from tqdm.auto import tqdm
 
@@ -308,6 +331,8 @@ class LogitICARGibbs(GibbsBase):
             self._moran_switch(eng, False)
         if site_intervals or getattr(eng, '_hist_bins', 0):   # (likewise)
             self._hist_switch(eng, 0)
+        if site_diagnostics or getattr(eng, '_conv_batch', 0):   # (likewise)
+            self._conv_switch(eng, 0)
         sums_on = False
 
         C = len(samplers)
@@ -338,6 +363,8 @@ class LogitICARGibbs(GibbsBase):
                         eng.moran_stats(True)
                     if site_intervals:
                         eng.hist_stats(site_intervals)
+                    if site_diagnostics:
+                        eng.conv_stats(site_diagnostics)
                     sums_on = True
                 a_, b_, t_ = eng.run(step, b)
                 m = step - b
@@ -370,6 +397,8 @@ class LogitICARGibbs(GibbsBase):
             self.__dict__['_spatial_check'] = SpatialCheck.from_problem(self._problem, moran_rows)
         if site_intervals:
             self.__dict__['_site_intervals'] = SiteIntervals.from_engine(eng)
+        if site_diagnostics:
+            self.__dict__['_site_diagnostics'] = SiteDiagnostics.from_engine(eng)
         return chains
 
 

@@ -119,6 +119,10 @@ class ProbitRSRGibbs(GibbsBase):
         # (its psi is the modelling decision DESIGN 11 leaves open)
         raise NotImplementedError('site intervals are not available for the probit model')
 
+    def _refuse_site_diagnostics(self):
+        # (likewise)
+        raise NotImplementedError('site diagnostics are not available for the probit model')
+
     step = LogitICARGibbs.step
     checkpoint = LogitICARGibbs.checkpoint
     resume = LogitICARGibbs.resume
