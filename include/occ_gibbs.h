@@ -287,7 +287,43 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  * them with OCC_E_STATE, "per-site convergence diagnostics are not available for the probit model".  Nothing is redrawn;
  * occ_set_start and occ_set_keys do not touch them; a call that is re-run after a device-side wait gave up counts nothing
  * twice; occ_profile and the occ_cond_* entry points never count.  alpha, beta, tau, eta, z, every sum and every record above
- * are bit-identical with the switch on or off. */
+ * are bit-identical with the switch on or off.
+ *
+ * Held-out predictive scoring (logit models; ICAR and reduced rank): how well does the fit predict detection histories it has
+ * not seen, at sites it does not survey?  The held-out sites are simply absent from the handle's problem (W, y); their
+ * withheld visits are given separately.  The log predictive density of a held-out site needs the mean over the kept draws of
+ * the site's marginal likelihood of its withheld history: a handful of running sums; the draws are not needed.  A held-out
+ * entry h is a site i with visit rows r = ptr[h] .. ptr[h + 1] - 1, covariates w_r (q columns) and detections y_r.  Per
+ * iteration past the call's burn-in -- the rule of the per-site intervals above, so occ_step counts as well -- of a chain
+ * whose switch is on, one kernel launched directly behind the z update does, per entry, with a = x_i beta + eta_i (reduced
+ * rank: eta = K theta), psi = expit(a), lsig(t) = min(t, 0) - log1p(exp(-|t|)) and P = prod_r expit(-w_r alpha):
+ *   no detection in the withheld history:   D = (1 - psi) + psi P,   L = D,   l = log D
+ *   a detection:                            l = lsig(a) + sum_r lsig(+- w_r alpha)  (+ where y_r = 1, rows in row order),   L = exp(l)
+ *   pd = psi (1 - P)                        the predictive probability of at least one detection in these visits
+ *   cnt += 1;   sum L += L;   sum l += l;   sum l^2 += l l;   sum pd += pd
+ * -- the formulas of the log-likelihood sums above, taken over the withheld rows -- and it adds 1 to the chain's count of
+ * accumulated iterations.  A column belongs to one thread and additions run in iteration order: the same values whatever
+ * the path, the placement, the block size or the split into calls.  40 bytes per entry and chain.
+ *   holdout_data(2 + 2 H + 1 + R + R q)
+ *       the handle's withheld data, set and read through any valid chain index: one packed array
+ *       [H, R, site[H], ptr[H + 1], y[R], W[R q] row-major].  Validated as a whole, OCC_E_BADARG otherwise and nothing
+ *       changes: whole numbers only; 1 <= H; the sites lie in [0, n), are distinct and are NOT surveyed in this handle's
+ *       problem; ptr rises from 0 to R with at least one row per entry; y is 0 or 1; W is finite; the length is exactly
+ *       2 + 2 H + 1 + R + R q.  Settable only while no chain has holdout_stats on (OCC_E_STATE otherwise).  The first one
+ *       allocates; setting it again replaces the data and ZEROES every chain's sums and count.
+ *   holdout_stats(1)
+ *       a word of the handle per chain, 0 or 1 (any other value is OCC_E_BADARG).  It is not one of the z update's outputs
+ *       above.  Switching on ZEROES the chain's sums and count; 0 keeps everything readable.
+ *   holdout_count(1)
+ *       the chain's count of accumulated iterations.
+ *   holdout_sums(5 H)
+ *       the chain's sums, slot-major [slot][entry]: cnt, sum L, sum l, sum l^2, sum pd.
+ * holdout_count and holdout_sums are writable while the chain's switch is on (checkpoint restore): the count and every cnt
+ * are whole numbers >= 0 and every cnt of a written holdout_sums is the same, OCC_E_BADARG otherwise.  All four names answer
+ * OCC_E_STATE before the handle's first holdout_data, and a probit handle answers them with OCC_E_STATE, "held-out scoring is
+ * not available for the probit model".  Nothing is redrawn; occ_set_start and occ_set_keys do not touch them; a call that is
+ * re-run after a device-side wait gave up counts nothing twice; occ_profile and the occ_cond_* entry points never count.
+ * alpha, beta, tau, eta, z, every sum and every record above are bit-identical with the switch on or off. */
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len);
 int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double *in, int64_t len);
 

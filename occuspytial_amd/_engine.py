@@ -129,6 +129,10 @@ class Engine:
         # per-site convergence diagnostics: the batch length while switched on, 0 while off; likewise
         self._conv_batch = 0
         self._conv_last = 0   # (the batch length of the sums that stay readable after switching off)
+        # held-out predictive scoring: the withheld data as packed for the library (None: never set) and the switch; until the
+        # data are set, no call about it reaches the library
+        self._holdout = None
+        self._holdout_on = False
         _LIVE.add(self)
         return self
 
@@ -237,6 +241,12 @@ class Engine:
             out['conv_stats'] = np.full(self.n_chains, float(self._conv_batch))
             out['conv_count'] = np.array([p['count'] for p in parts], dtype=np.int64)
             out['conv_sums'] = np.stack([p['sums'] for p in parts])
+        if self._holdout_on:   # the withheld data (one row per chain, as every entry), the switch, the counts and the sums
+            parts = [self.holdout_sums(c) for c in range(self.n_chains)]
+            out['holdout_data'] = np.tile(self._holdout, (self.n_chains, 1))
+            out['holdout_stats'] = np.ones(self.n_chains)
+            out['holdout_count'] = np.array([p['count'] for p in parts], dtype=np.int64)
+            out['holdout_sums'] = np.stack([p['sums'] for p in parts])
         return out
 
     def restore(self, ckpt):
@@ -292,6 +302,41 @@ class Engine:
                 self.set('conv_sums', np.asarray(ckpt['conv_sums'], dtype=np.float64)[c].ravel(), c)
         elif self._conv_batch:
             self.conv_stats(0)
+        if 'holdout_stats' in ckpt and np.all(np.asarray(ckpt['holdout_stats']) != 0):
+            self.holdout_data(np.asarray(ckpt['holdout_data'], dtype=np.float64)[0])
+            self.holdout_stats(True)
+            for c in range(self.n_chains):
+                self.set('holdout_count', float(np.asarray(ckpt['holdout_count'])[c]), c)
+                self.set('holdout_sums', np.asarray(ckpt['holdout_sums'], dtype=np.float64)[c].ravel(), c)
+        elif self._holdout_on:
+            self.holdout_stats(False)
+
+    # ---- held-out predictive scoring (state names holdout_*, include/occ_gibbs.h) ----
+    def holdout_data(self, W, y=None):
+        """Set the handle's withheld data: ``W`` and ``y`` dicts keyed by site, as the constructor takes them, of sites this
+        engine's problem does NOT survey (or ``W`` the array :func:`occuspytial_amd.holdout.holdout_arg` packs and no
+        ``y``).  The switches of all chains go off first (the library sets the data only then); setting them zeroes every
+        chain's sums."""
+        from .holdout import holdout_arg
+        packed = holdout_arg((W, y), self.prob) if y is not None else np.ascontiguousarray(W, dtype=np.float64).ravel()
+        if self._holdout_on:
+            self.holdout_stats(False)
+        self.set('holdout_data', packed, 0)
+        self._holdout = packed.copy()
+
+    def holdout_stats(self, on):
+        """Switch the held-out sums of every chain on (which ZEROES them and their counts) or off (they stay readable).
+        While on, every iteration past a call's burn-in adds, per held-out site, the predictive density of its withheld
+        detection history under the iteration's alpha, beta and eta (:meth:`holdout_sums`)."""
+        for c in range(self.n_chains):
+            self.set('holdout_stats', 1.0 if on else 0.0, c)
+        self._holdout_on = bool(on)
+
+    def holdout_sums(self, chain=0):
+        """``{'count': iterations accumulated, 'sums': (5, H) float64}`` of one chain: per held-out entry ``cnt``, the sum of
+        the likelihood L, of l = log L, of l^2, and of pd, the predictive probability of at least one detection."""
+        sums = self.get('holdout_sums', chain)
+        return {'count': int(self.get('holdout_count', chain)[0]), 'sums': sums.reshape(5, sums.size // 5)}
 
     # ---- per-site convergence diagnostics (state names conv_*, include/occ_gibbs.h) ----
     def conv_stats(self, batch):
@@ -664,6 +709,27 @@ class EngineGroup:
     def conv_sums(self, chain=0):
         g, i = self.where[chain]
         return self.engines[g].conv_sums(i)
+
+    # held-out predictive scoring: the data and the switch on every device, the sums routed by chain
+    @property
+    def _holdout(self):
+        return getattr(self.engines[0], '_holdout', None)
+
+    @property
+    def _holdout_on(self):
+        return any(getattr(e, '_holdout_on', False) for e in self.engines)
+
+    def holdout_data(self, W, y=None):
+        for e in self.engines:
+            e.holdout_data(W, y)
+
+    def holdout_stats(self, on):
+        for e in self.engines:
+            e.holdout_stats(on)
+
+    def holdout_sums(self, chain=0):
+        g, i = self.where[chain]
+        return self.engines[g].holdout_sums(i)
 
     # (the entry points by name are Engine's own: each only names its kind)
     site_stats, site_sums, loglik_stats, loglik_sums = Engine.site_stats, Engine.site_sums, Engine.loglik_stats, Engine.loglik_sums

@@ -33,6 +33,10 @@ HIST_FIELDS = ('hist_stats', 'hist_count', 'hist_counts')
 # per-site convergence diagnostics: the chain's switch (a word of the handle: 0 off, L on with batch length L), its count of
 # accumulated iterations, its batch-means sums (11 n, slot-major: cnt, then ref, s1, s2, run, bsq of psi, then of eta)
 CONV_FIELDS = ('conv_stats', 'conv_count', 'conv_sums')
+# held-out predictive scoring: the handle's withheld data (packed: H, R, site[H], ptr[H + 1], y[R], W[R q] row-major), the
+# chain's switch (a word of the handle, 0 or 1), its count of accumulated iterations, its sums (5 H, slot-major: cnt, the sums
+# of L, of l, of l^2 and of pd)
+HOLDOUT_FIELDS = ('holdout_data', 'holdout_stats', 'holdout_count', 'holdout_sums')
 KERNEL_KINDS = ('omega_b', 'noise', 'eta_init', 'minres', 'beta_partial', 'omega_a', 'alpha_draw', 'z_ob', 'iter')
 
 

@@ -26,6 +26,7 @@
 #include "occ_spatial.hpp"
 #include "occ_hist.hpp"
 #include "occ_conv.hpp"
+#include "occ_holdout.hpp"
 #include "occ_layout.hpp"
 
 using namespace occ;
@@ -212,6 +213,22 @@ struct occ_sampler {
         ConvArgs args{};
         size_t words() const { return (size_t)CONV_SLOTS * args.Cn; }
     } conv;
+    // Held-out predictive scoring (state names holdout_data, holdout_stats, holdout_count, holdout_sums; logit models;
+    // occ_holdout.hpp).  ready: holdout_data has been set once -- the withheld rows, the sums [5][C H], the counts [C] and the
+    // switches are on the device; packed: the data as they were set (what holdout_data reads back).  The switch is a word of
+    // the handle per chain (on, on_dev), as the per-site convergence diagnostics'; any: their OR, which decides whether the
+    // kernel is launched behind the z update (baked into captured graphs with the sizes and the addresses: a change drops
+    // them).  snap: [5 C H] sums, then [C] counts, part of what a call is re-run from; snapped: taken for the running call.
+    struct Holdout {
+        bool ready = false, snapped = false;
+        uint32_t any = 0u;
+        std::vector<uint32_t> on;
+        std::vector<double> packed;
+        uint32_t *on_dev = nullptr;
+        double *snap = nullptr;
+        HoldoutArgs args{};
+        size_t words() const { return (size_t)HOLD_SLOTS * args.CH; }
+    } holdout;
     std::vector<ChainScalars> snap_sc;
     // fixed problem arrays on the device, in upload order: what a group broadcasts from its root (occ_create_group /
     // occ_create_distributed); defer_fixed: allocate only, the bytes arrive by broadcast
@@ -677,6 +694,8 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
                 hist_launch(s->hist.args, s->ctx.sc, c.C, e, st);
             if (s->conv.any)  // the per-site convergence diagnostics, likewise
                 conv_launch(s->conv.args, s->ctx.sc, c.C, e, st);
+            if (s->holdout.any)  // the held-out predictive scoring, likewise
+                holdout_launch(s->holdout.args, s->ctx.sc, c.C, e, st);
             break;
     }
     const hipError_t le = hipGetLastError();
@@ -1022,6 +1041,14 @@ int open_window(occ_sampler *s, int64_t n_iter, int64_t burnin, int64_t keep, bo
             if (!cv.snap && (rc = dev_alloc(s, &cv.snap, nw + (size_t)c.C, false))) return rc;
             HIP_TRY(hipMemcpyAsync(cv.snap, cv.args.sums, sizeof(double) * nw, hipMemcpyDeviceToDevice, s->stream));
             HIP_TRY(hipMemcpyAsync(cv.snap + nw, cv.args.count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
+        }
+        occ_sampler::Holdout &ho = s->holdout;  // ... and the sums of the held-out predictive scoring
+        ho.snapped = ho.any != 0u;
+        if (ho.snapped) {
+            const size_t nw = ho.words();
+            if (!ho.snap && (rc = dev_alloc(s, &ho.snap, nw + (size_t)c.C, false))) return rc;
+            HIP_TRY(hipMemcpyAsync(ho.snap, ho.args.sums, sizeof(double) * nw, hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(ho.snap + nw, ho.args.count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
         }
         hipLaunchKernelGGL(k_snapshot, dim3((unsigned)std::min<size_t>((Cn + 255) / 256, 2048)), dim3(256), 0, s->stream, c.eta, s->snap_eta, c.z, s->snap_z, c.Xv, s->snap_x,
                            (unsigned long long)Cn, s->rsr.m > 0 ? s->rsr.theta : nullptr, s->snap_theta, (unsigned long long)c.C * (unsigned long long)std::max(s->rsr.m, 0),
@@ -2940,6 +2967,11 @@ static int fallback_to_launch_per_step(occ_sampler *s)
         HIP_TRY(copy_on(s, s->conv.args.sums, s->conv.snap, sizeof(double) * nw, hipMemcpyDeviceToDevice));
         HIP_TRY(copy_on(s, s->conv.args.count, s->conv.snap + nw, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
     }
+    if (s->holdout.snapped) {
+        const size_t nw = s->holdout.words();
+        HIP_TRY(copy_on(s, s->holdout.args.sums, s->holdout.snap, sizeof(double) * nw, hipMemcpyDeviceToDevice));
+        HIP_TRY(copy_on(s, s->holdout.args.count, s->holdout.snap + nw, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
+    }
     for (auto &sc : s->snap_sc) sc.err = 0;
     if ((rc = write_scalars(s, s->snap_sc))) return rc;
     s->parity = s->snap_parity;
@@ -3649,6 +3681,195 @@ static int set_conv_state(occ_sampler *s, int chain, int field, const double *in
     return OCC_OK;
 }
 
+// ---- occ_get_state / occ_set_state of the held-out predictive scoring's names (logit models) ----------------------------
+// holdout_data (2 + 2 H + 1 + R + R q): the handle's withheld data, through any chain index -- [H, R, site[H], ptr[H + 1],
+// y[R], W[R q] row-major]; validated as a whole; set only while no chain's switch is on; allocates at first use; setting it
+// again replaces the data and zeroes every chain's sums.  holdout_stats (1): the chain's switch, 0 or 1; switching on zeroes
+// the chain's part.  holdout_count (1): the chain's count of accumulated iterations.  holdout_sums (5 H): the chain's slots,
+// slot-major [slot][entry].  The count and the sums are writable while the chain's switch is on (checkpoint restore).  Before
+// the first holdout_data every name answers OCC_E_STATE.  Nothing of a chain's state changes.  Whether the kernel is launched
+// behind the z update follows "is any chain on"; a change of that, of a size or of an address drops the captured graphs.
+enum : int { HOLD_NONE = -1, HOLD_DATA = 0, HOLD_SWITCH = 1, HOLD_COUNT = 2, HOLD_SUMS = 3 };
+static int holdout_field(const std::string &nm)
+{
+    return nm == "holdout_data" ? HOLD_DATA : nm == "holdout_stats" ? HOLD_SWITCH : nm == "holdout_count" ? HOLD_COUNT : nm == "holdout_sums" ? HOLD_SUMS : HOLD_NONE;
+}
+static int holdout_refused(occ_sampler *s)
+{
+    if (s->probit) return set_error(s, OCC_E_STATE, "held-out scoring is not available for the probit model");
+    return set_error(s, OCC_E_STATE, "no held-out data have been set for this handle (set holdout_data first)");
+}
+// The packed array as a whole: OCC_OK, or OCC_E_BADARG with the first rule it breaks.  On success the pieces as the device
+// takes them.
+static int holdout_parse(occ_sampler *s, const double *in, int64_t len, std::vector<int> &site, std::vector<int> &ptr, std::vector<uint8_t> &seen,
+                         std::vector<uint8_t> &y, std::vector<double> &Wt)
+{
+    const Ctx &c = s->ctx;
+    const auto whole = [](double x) { return x >= 0.0 && x < 0x1.0p31 && x == std::floor(x); };
+    if (len < 2 || !whole(in[0]) || !whole(in[1])) return set_error(s, OCC_E_BADARG, "holdout_data starts with the whole numbers H and R");
+    const size_t H = (size_t)in[0], R = (size_t)in[1], q = (size_t)c.q;
+    if (H < 1 || H > (size_t)c.n) return set_error(s, OCC_E_BADARG, "holdout_data holds 1 to n entries");
+    if (R < H) return set_error(s, OCC_E_BADARG, "holdout_data holds at least one row per entry");
+    if ((uint64_t)len != (uint64_t)2 + 2 * H + 1 + R + R * q)
+        return set_error(s, OCC_E_BADARG, "holdout_data has length 2 + 2 H + 1 + R + R q: H, R, site[H], ptr[H + 1], y[R], W[R q]");
+    const double *psite = in + 2, *pptr = psite + H, *py = pptr + H + 1, *pW = py + R;
+    std::vector<uint8_t> taken((size_t)c.n, 0);  // 1: surveyed in the handle's problem, 2: held out already
+    for (int32_t i : s->site_id)
+        if (i >= 0 && i < c.n) taken[(size_t)i] = 1;
+    site.resize(H), ptr.resize(H + 1), seen.assign(H, 0), y.resize(R), Wt.resize(R * q);
+    for (size_t h = 0; h < H; ++h) {
+        if (!whole(psite[h]) || !(psite[h] < (double)c.n)) return set_error(s, OCC_E_BADARG, "holdout_data: a site is a whole number in [0, n)");
+        const size_t i = (size_t)psite[h];
+        if (taken[i] == 1) return set_error(s, OCC_E_BADARG, ("holdout_data: site " + std::to_string(i) + " is surveyed in this handle's problem (a held-out site is left out of W and y)").c_str());
+        if (taken[i] == 2) return set_error(s, OCC_E_BADARG, ("holdout_data: site " + std::to_string(i) + " appears twice").c_str());
+        taken[i] = 2;
+        site[h] = (int)i;
+    }
+    for (size_t h = 0; h <= H; ++h) {
+        if (!whole(pptr[h]) || !(pptr[h] <= (double)R) || (h == 0 ? pptr[h] != 0.0 : !(pptr[h] > pptr[h - 1])))
+            return set_error(s, OCC_E_BADARG, "holdout_data: ptr rises from 0 to R with at least one row per entry");
+        ptr[h] = (int)pptr[h];
+    }
+    if (ptr[H] != (int)R) return set_error(s, OCC_E_BADARG, "holdout_data: ptr rises from 0 to R with at least one row per entry");
+    for (size_t r = 0; r < R; ++r) {
+        if (py[r] != 0.0 && py[r] != 1.0) return set_error(s, OCC_E_BADARG, "holdout_data: y is 0 or 1");
+        y[r] = py[r] != 0.0;
+    }
+    for (size_t h = 0; h < H; ++h)
+        for (int r = ptr[h]; r < ptr[h + 1]; ++r) seen[h] |= y[(size_t)r];
+    for (size_t r = 0; r < R; ++r)
+        for (size_t k = 0; k < q; ++k) {
+            if (!std::isfinite(pW[r * q + k])) return set_error(s, OCC_E_BADARG, "holdout_data: W is finite");
+            Wt[k * R + r] = pW[r * q + k];
+        }
+    return OCC_OK;
+}
+static int holdout_put(occ_sampler *s, const void **dst, const void *src, size_t bytes)
+{
+    uint8_t *d = nullptr;
+    const int rc = dev_alloc(s, &d, bytes, false);
+    if (rc) return rc;
+    HIP_TRY(copy_on(s, d, src, bytes, hipMemcpyHostToDevice));
+    *dst = d;
+    return OCC_OK;
+}
+// The withheld data and the sums for them: at the handle's first holdout_data, and again for every later one (every chain is
+// off then; the old arrays are freed: nothing is in flight to them, both streams have been waited for).  Every chain's sums
+// and count start at zero.
+static int holdout_alloc(occ_sampler *s, const std::vector<int> &site, const std::vector<int> &ptr, const std::vector<uint8_t> &seen,
+                         const std::vector<uint8_t> &y, const std::vector<double> &Wt)
+{
+    Ctx &c = s->ctx;
+    occ_sampler::Holdout &ho = s->holdout;
+    HoldoutArgs &a = ho.args;
+    int rc;
+    WAIT_TRY(s->stream);
+    destroy_graph(s);  // (the addresses and the sizes travel by value in the captured launches)
+    for (void *old : {(void *)a.site, (void *)a.ptr, (void *)a.seen, (void *)a.y, (void *)a.Wt, (void *)a.sums, (void *)ho.snap}) {
+        if (!old) continue;
+        s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), old), s->allocs.end());
+        HIP_TRY(hipFree(old));
+    }
+    a.site = a.ptr = nullptr, a.seen = a.y = nullptr, a.Wt = nullptr, a.sums = ho.snap = nullptr;
+    ho.snapped = false;
+    a.n = c.n, a.p = c.p, a.q = c.q, a.H = (int)site.size(), a.R = (int)y.size();
+    a.CH = (size_t)c.C * site.size();
+    a.Xt = c.Xt, a.eta = c.eta;
+    const void *d_site = nullptr, *d_ptr = nullptr, *d_seen = nullptr, *d_y = nullptr, *d_Wt = nullptr;
+    if ((rc = holdout_put(s, &d_site, site.data(), sizeof(int) * site.size())) || (rc = holdout_put(s, &d_ptr, ptr.data(), sizeof(int) * ptr.size())) ||
+        (rc = holdout_put(s, &d_seen, seen.data(), seen.size())) || (rc = holdout_put(s, &d_y, y.data(), y.size())) ||
+        (rc = holdout_put(s, &d_Wt, Wt.data(), sizeof(double) * Wt.size())))
+        return rc;
+    a.site = (const int *)d_site, a.ptr = (const int *)d_ptr, a.seen = (const uint8_t *)d_seen, a.y = (const uint8_t *)d_y, a.Wt = (const double *)d_Wt;
+    if ((rc = dev_alloc(s, &a.sums, ho.words()))) return rc;
+    if (!ho.on_dev) {
+        if ((rc = dev_alloc(s, &a.count, (size_t)c.C))) return rc;
+        if ((rc = dev_alloc(s, &ho.on_dev, (size_t)c.C))) return rc;
+        ho.on.assign((size_t)c.C, 0u);
+        a.on = ho.on_dev;
+    } else {
+        HIP_TRY(fill_on(s, a.count, 0, sizeof(double) * (size_t)c.C));
+    }
+    ho.ready = true;
+    return OCC_OK;
+}
+static int get_holdout_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
+{
+    const occ_sampler::Holdout &ho = s->holdout;
+    if (s->probit || !ho.ready) return holdout_refused(s);
+    if (field == HOLD_DATA) {
+        v = ho.packed;
+        return OCC_OK;
+    }
+    if (field == HOLD_SWITCH) {
+        v.assign(1, ho.on[(size_t)chain] ? 1.0 : 0.0);
+        return OCC_OK;
+    }
+    if (field == HOLD_COUNT) {
+        v.resize(1);
+        HIP_TRY(copy_on(s, v.data(), ho.args.count + chain, sizeof(double), hipMemcpyDeviceToHost));
+        return OCC_OK;
+    }
+    const size_t H = (size_t)ho.args.H;
+    v.resize((size_t)HOLD_SLOTS * H);
+    for (int k = 0; k < HOLD_SLOTS; ++k)  // the chain's part of every slot
+        HIP_TRY(copy_on(s, v.data() + (size_t)k * H, ho.args.sums + (size_t)k * ho.args.CH + (size_t)chain * H, sizeof(double) * H, hipMemcpyDeviceToHost));
+    return OCC_OK;
+}
+static int set_holdout_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+{
+    occ_sampler::Holdout &ho = s->holdout;
+    if (s->probit) return holdout_refused(s);
+    const auto whole = [](double x) { return x >= 0.0 && x < 0x1.0p53 && x == std::floor(x); };
+    int rc;
+    if (field == HOLD_DATA) {
+        if (ho.any) return set_error(s, OCC_E_STATE, "holdout_data cannot be set while a chain has holdout_stats on");
+        std::vector<int> site, ptr;
+        std::vector<uint8_t> seen, y;
+        std::vector<double> Wt;
+        if ((rc = holdout_parse(s, in, len, site, ptr, seen, y, Wt))) return rc;  // (all or nothing: nothing has changed yet)
+        WAIT_TRY(s->side);
+        if ((rc = holdout_alloc(s, site, ptr, seen, y, Wt))) {
+            ho.ready = false;
+            return rc;
+        }
+        ho.packed.assign(in, in + len);
+        return OCC_OK;
+    }
+    if (!ho.ready) return holdout_refused(s);
+    const size_t H = (size_t)ho.args.H;
+    if (field != HOLD_SWITCH) {
+        if (!ho.on[(size_t)chain]) return set_error(s, OCC_E_STATE, "held-out scoring is switched off for this chain (set holdout_stats first)");
+        if ((size_t)len != (field == HOLD_COUNT ? (size_t)1 : (size_t)HOLD_SLOTS * H)) return set_error(s, OCC_E_STATE, "wrong length");
+        if (field == HOLD_COUNT) {
+            if (!whole(in[0])) return set_error(s, OCC_E_BADARG, "holdout_count is a whole number >= 0");
+            HIP_TRY(copy_on(s, ho.args.count + chain, in, sizeof(double), hipMemcpyHostToDevice));
+            return OCC_OK;
+        }
+        for (size_t h = 0; h < H; ++h)  // slot 0 is cnt: the entries of a chain have counted the same iterations
+            if (!whole(in[h]) || in[h] != in[0])
+                return set_error(s, OCC_E_BADARG, "the cnt slot of holdout_sums holds one whole number >= 0 at every entry");
+        for (int k = 0; k < HOLD_SLOTS; ++k)
+            HIP_TRY(copy_on(s, ho.args.sums + (size_t)k * ho.args.CH + (size_t)chain * H, in + (size_t)k * H, sizeof(double) * H, hipMemcpyHostToDevice));
+        return OCC_OK;
+    }
+    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
+    if (in[0] != 0.0 && in[0] != 1.0) return set_error(s, OCC_E_BADARG, "holdout_stats is 0 or 1");
+    WAIT_TRY(s->side);
+    if (in[0] != 0.0) {  // switching on zeroes the chain's part, as site_stats does
+        for (int k = 0; k < HOLD_SLOTS; ++k)
+            HIP_TRY(fill_on(s, ho.args.sums + (size_t)k * ho.args.CH + (size_t)chain * H, 0, sizeof(double) * H));
+        HIP_TRY(fill_on(s, ho.args.count + chain, 0, sizeof(double)));
+    }
+    ho.on[(size_t)chain] = in[0] != 0.0 ? 1u : 0u;
+    HIP_TRY(copy_on(s, ho.on_dev, ho.on.data(), sizeof(uint32_t) * ho.on.size(), hipMemcpyHostToDevice));
+    uint32_t any = 0u;
+    for (uint32_t o : ho.on) any |= o;
+    if (any != ho.any) destroy_graph(s);
+    ho.any = any;
+    return OCC_OK;
+}
+
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len)
 {
     if (!s || !name || !len) return OCC_E_BADARG;
@@ -3679,6 +3900,10 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     if (conv_field(nm) != CONV_NONE) {
         const int crc = get_conv_state(s, chain, conv_field(nm), v);
         return crc ? crc : give_state(s, v, out, cap, len);
+    }
+    if (holdout_field(nm) != HOLD_NONE) {
+        const int orc = get_holdout_state(s, chain, holdout_field(nm), v);
+        return orc ? orc : give_state(s, v, out, cap, len);
     }
     int sums_kind = SUMS_SITE;
     const int site_q = site_field(nm, &sums_kind);
@@ -3750,6 +3975,7 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     if (moran_field(nm) != MORAN_NONE) return set_moran_state(s, chain, moran_field(nm), in, len);
     if (hist_field(nm) != HIST_NONE) return set_hist_state(s, chain, hist_field(nm), in, len);
     if (conv_field(nm) != CONV_NONE) return set_conv_state(s, chain, conv_field(nm), in, len);
+    if (holdout_field(nm) != HOLD_NONE) return set_holdout_state(s, chain, holdout_field(nm), in, len);
     int sums_kind = SUMS_SITE;
     const int sums_q = site_field(nm, &sums_kind);
     if (sums_q != SITE_NONE) return set_site_state(s, chain, sums_kind, sums_q, in, len);
@@ -3923,6 +4149,7 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
     Scoped<uint32_t> no_spatial(&s->spatial.any, 0u);
     Scoped<uint32_t> no_hist(&s->hist.any, 0u);
     Scoped<uint32_t> no_conv(&s->conv.any, 0u);
+    Scoped<uint32_t> no_holdout(&s->holdout.any, 0u);
     int rc = open_window(s, 1 << 30, 0, 0, false, false);  // no chain reaches its stop during the timing loops
     if (rc) return rc;
     // The fused iteration kernel first, IN SITU: `reps` real iterations continue the chains from where they are

@@ -14,6 +14,7 @@ from .._problem import FlatProblem, default_start
 from ..chain import Chain
 from ..convergence import diagnostics_batch
 from ..data import Data
+from ..holdout import holdout_arg
 from ..intervals import interval_bins
 from ..posterior import PosteriorParameter
 from ..ppc import ppc_flag
@@ -120,7 +121,7 @@ class GibbsBase:
         return self.chain
 
     def sample(self, size, burnin=0, start=None, chains=2, progressbar=True, site_summaries=False, waic=False, regions=None,
-               ppc=False, spatial_check=False, site_intervals=False, site_diagnostics=False):
+               ppc=False, spatial_check=False, site_intervals=False, site_diagnostics=False, holdout=None):
         """Draw ``size`` iterations per chain and return the kept ``alpha``, ``beta``, ``tau`` draws.
 
         Same contract as the reference (``base.py:243-291``): ``burnin < size`` else ``ValueError``;
@@ -159,6 +160,13 @@ class GibbsBase:
         over the kept iterations the device keeps, per site, batch-means sums of psi and of the spatial effect eta;
         ``out.site_diagnostics`` is a :class:`~occuspytial_amd.convergence.SiteDiagnostics` (R-hat across chains, effective
         sample size and Monte-Carlo standard error per site, and the worst sites; ``None`` otherwise).
+
+        ``holdout=(W_test, y_test)`` (likewise): the withheld visits of sites this sampler does NOT survey, as dicts keyed
+        by site like the constructor's ``W`` and ``y``.  Over the kept iterations the device adds, per held-out site, the
+        predictive density of its withheld detection history; ``out.holdout`` is a
+        :class:`~occuspytial_amd.holdout.HoldoutScore` (expected log predictive density with its standard error, Brier
+        score and AUC of the predicted detections; ``None`` otherwise).  :func:`occuspytial_amd.holdout.split` makes the
+        folds of a K-fold run and :func:`occuspytial_amd.holdout.combine` joins their scores.
         """
         bins = interval_bins(site_intervals)
         batch = diagnostics_batch(site_diagnostics, size - burnin)
@@ -186,6 +194,9 @@ class GibbsBase:
         if batch:
             self._refuse_site_diagnostics()
             extra['site_diagnostics'] = batch
+        if holdout is not None:
+            self._refuse_holdout()
+            extra['holdout'] = holdout_arg(holdout, self._problem)
         samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start,
                                   progressbar=progressbar, **extra)
         out = PosteriorParameter(*samples)
@@ -202,6 +213,8 @@ class GibbsBase:
             out.site_intervals = self.__dict__.pop('_site_intervals')
         if 'site_diagnostics' in extra:
             out.site_diagnostics = self.__dict__.pop('_site_diagnostics')
+        if 'holdout' in extra:
+            out.holdout = self.__dict__.pop('_holdout')
         return out
 
     def _refuse_ppc(self):
@@ -226,6 +239,12 @@ class GibbsBase:
         """The batch-means sums are kept on the device behind the engine's z update: a sampler with a Python ``step`` has none."""
         if not hasattr(self, '_run_chains'):
             raise NotImplementedError(f'{self.__class__.__name__} steps in Python: site diagnostics are accumulated by the '
+                                      'device engine only')
+
+    def _refuse_holdout(self):
+        """The held-out sums are kept on the device behind the engine's z update: a sampler with a Python ``step`` has none."""
+        if not hasattr(self, '_run_chains'):
+            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: held-out scoring is accumulated by the '
                                       'device engine only')
 
     def _refuse_regions(self):

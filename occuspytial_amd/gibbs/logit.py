@@ -5,6 +5,7 @@ from .. import _lib
 from .._engine import Engine, EngineGroup
 from ..chain import Chain
 from ..convergence import SiteDiagnostics, diagnostics_batch
+from ..holdout import HoldoutScore, holdout_arg
 from ..intervals import SiteIntervals, interval_bins
 from ..ppc import PredictiveCheck, ppc_flag
 from ..regions import region_ids
@@ -167,8 +168,14 @@ class LogitICARGibbs(GibbsBase):
         except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
             raise ValueError(f'the loaded engine library has no site diagnostics ({exc}): rebuild it') from None
 
+    def _holdout_call(self, call):
+        try:
+            return call()
+        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
+            raise ValueError(f'the loaded engine library has no held-out scoring ({exc}): rebuild it') from None
+
     def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False, regions=None, ppc=False,
-               spatial_check=False, site_intervals=False, site_diagnostics=False):
+               spatial_check=False, site_intervals=False, site_diagnostics=False, holdout=None):
         """Continue the chains of ``checkpoint`` (a dict from :meth:`checkpoint` or the path of its ``.npz``)
         for ``size`` more iterations on this sampler's problem.  Returns a ``PosteriorParameter`` of the new
         draws; every chain's ``Chain`` is the continuation (use ``Chain.expand`` / ``append`` to join them to
@@ -184,7 +191,9 @@ class LogitICARGibbs(GibbsBase):
         accumulated so far.
         ``site_diagnostics`` (as in :meth:`sample`): the per-site batch-means sums go on from those the checkpoint holds,
         with the checkpoint's batch length whatever is asked for here (from zero if it holds none: ``True`` is then
-        ``floor(sqrt(size))``); ``out.site_diagnostics`` covers every iteration accumulated so far."""
+        ``floor(sqrt(size))``); ``out.site_diagnostics`` covers every iteration accumulated so far.
+        ``holdout`` (as in :meth:`sample`): the held-out sums go on from those the checkpoint holds if it holds them for
+        the same withheld data (from zero otherwise); ``out.holdout`` covers every iteration accumulated so far."""
         from ..posterior import PosteriorParameter
         from tqdm.auto import tqdm
         bins = interval_bins(site_intervals)
@@ -207,6 +216,9 @@ class LogitICARGibbs(GibbsBase):
             self._refuse_site_intervals()
         if batch:
             self._refuse_site_diagnostics()
+        if holdout is not None:
+            self._refuse_holdout()
+            holdout = holdout_arg(holdout, self._problem)
         C = int(checkpoint['n_chains'])
         self.__dict__['_stepping'] = False
         eng = self._get_engine([int(k) for k in np.asarray(checkpoint['keys'])])
@@ -239,6 +251,11 @@ class LogitICARGibbs(GibbsBase):
                 self._conv_switch(eng, batch)
         elif getattr(eng, '_conv_batch', 0):   # (the checkpoint's switch was on: this call did not ask)
             eng.conv_stats(0)
+        if holdout is not None:
+            if not (getattr(eng, '_holdout_on', False) and np.array_equal(eng._holdout, holdout)):   # (none, or of other data: from zero)
+                self._holdout_call(lambda: (eng.holdout_data(holdout), eng.holdout_stats(True)))
+        elif getattr(eng, '_holdout_on', False):   # (the checkpoint's switch was on: this call did not ask)
+            eng.holdout_stats(False)
         alpha = np.zeros((C, size, self._problem.q))
         beta = np.zeros((C, size, self._problem.p))
         tau = np.zeros((C, size))
@@ -275,11 +292,13 @@ class LogitICARGibbs(GibbsBase):
             out.site_intervals = SiteIntervals.from_engine(eng)
         if batch:
             out.site_diagnostics = SiteDiagnostics.from_engine(eng)
+        if holdout is not None:
+            out.holdout = HoldoutScore.from_engine(eng)
         return out
 
     # ------------------------------------------------------------------ batched chains
     def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False, waic=False, regions=None,
-                    ppc=False, spatial_check=False, site_intervals=False, site_diagnostics=False):
+                    ppc=False, spatial_check=False, site_intervals=False, site_diagnostics=False, holdout=None):
         """All chains of one ``sample`` call as one device batch.
 
         Mirrors ``GibbsBase._run`` (base.py:214-241) per chain: start values from the chain's own
@@ -303,6 +322,9 @@ class LogitICARGibbs(GibbsBase):
         ``site_diagnostics`` (a batch length, or False): the per-site batch-means sums of psi and eta, switched in the same
         way; the :class:`~occuspytial_amd.convergence.SiteDiagnostics` read from the engine at the end is left for ``sample``.
         With the default no call about them reaches the engine.
+        ``holdout`` (the packed withheld data, or None): the held-out sums, switched in the same way -- the data are set with
+        every chain off before the first chunk; the :class:`~occuspytial_amd.holdout.HoldoutScore` read from the engine at
+        the end is left for ``sample``.  With the default no call about them reaches the engine.
         """
         from tqdm.auto import tqdm
 
@@ -333,6 +355,10 @@ class LogitICARGibbs(GibbsBase):
             self._hist_switch(eng, 0)
         if site_diagnostics or getattr(eng, '_conv_batch', 0):   # (likewise)
             self._conv_switch(eng, 0)
+        if holdout is not None:   # (sets the data with every chain's switch off)
+            self._holdout_call(lambda: eng.holdout_data(holdout))
+        elif getattr(eng, '_holdout_on', False):   # (a reused engine that an earlier call left on)
+            eng.holdout_stats(False)
         sums_on = False
 
         C = len(samplers)
@@ -365,6 +391,8 @@ class LogitICARGibbs(GibbsBase):
                         eng.hist_stats(site_intervals)
                     if site_diagnostics:
                         eng.conv_stats(site_diagnostics)
+                    if holdout is not None:
+                        eng.holdout_stats(True)
                     sums_on = True
                 a_, b_, t_ = eng.run(step, b)
                 m = step - b
@@ -399,6 +427,8 @@ class LogitICARGibbs(GibbsBase):
             self.__dict__['_site_intervals'] = SiteIntervals.from_engine(eng)
         if site_diagnostics:
             self.__dict__['_site_diagnostics'] = SiteDiagnostics.from_engine(eng)
+        if holdout is not None:
+            self.__dict__['_holdout'] = HoldoutScore.from_engine(eng)
         return chains
 
 

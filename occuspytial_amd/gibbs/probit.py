@@ -123,6 +123,10 @@ class ProbitRSRGibbs(GibbsBase):
         # (likewise)
         raise NotImplementedError('site diagnostics are not available for the probit model')
 
+    def _refuse_holdout(self):
+        # (likewise)
+        raise NotImplementedError('held-out scoring is not available for the probit model')
+
     step = LogitICARGibbs.step
     checkpoint = LogitICARGibbs.checkpoint
     resume = LogitICARGibbs.resume

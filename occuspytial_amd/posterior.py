@@ -43,6 +43,7 @@ class PosteriorParameter:
     waic = None    # a WAIC when sample(..., waic=True) asked for the streaming log-likelihood sums
     regions = None  # a RegionOccupancy when sample(..., regions=...) asked for the occupied sites per region and draw
     ppc = None     # a PredictiveCheck when sample(..., ppc=True) asked for the posterior predictive check
+    holdout = None  # a HoldoutScore when sample(..., holdout=(W_test, y_test)) asked for the predictive score at held-out sites
     site_diagnostics = None  # a SiteDiagnostics when sample(..., site_diagnostics=True or a batch length) asked for per-site R-hat, ESS and MCSE
     site_intervals = None  # a SiteIntervals when sample(..., site_intervals=True or a number of bins) asked for per-site histograms of psi
     spatial_check = None  # a SpatialCheck when sample(..., spatial_check=True) asked for Moran's I of the occupancy residuals
