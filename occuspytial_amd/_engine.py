@@ -231,22 +231,16 @@ class Engine:
             out['ppc_stats'] = np.ones(self.n_chains)
         if self._moran_on:   # likewise
             out['moran_stats'] = np.ones(self.n_chains)
-        if self._hist_bins:   # the switch (the number of bins), the counts of accumulated iterations and the histograms
-            parts = [self.hist_counts(c) for c in range(self.n_chains)]
-            out['hist_stats'] = np.full(self.n_chains, float(self._hist_bins))
-            out['hist_count'] = np.array([p['count'] for p in parts], dtype=np.int64)
-            out['hist_counts'] = np.stack([p['counts'] for p in parts])
-        if self._conv_batch:   # the switch (the batch length), the counts of accumulated iterations and the batch-means sums
-            parts = [self.conv_sums(c) for c in range(self.n_chains)]
-            out['conv_stats'] = np.full(self.n_chains, float(self._conv_batch))
-            out['conv_count'] = np.array([p['count'] for p in parts], dtype=np.int64)
-            out['conv_sums'] = np.stack([p['sums'] for p in parts])
-        if self._holdout_on:   # the withheld data (one row per chain, as every entry), the switch, the counts and the sums
-            parts = [self.holdout_sums(c) for c in range(self.n_chains)]
-            out['holdout_data'] = np.tile(self._holdout, (self.n_chains, 1))
-            out['holdout_stats'] = np.ones(self.n_chains)
-            out['holdout_count'] = np.array([p['count'] for p in parts], dtype=np.int64)
-            out['holdout_sums'] = np.stack([p['sums'] for p in parts])
+        for kind, k in _lib.ACCUM_KINDS.items():
+            on = getattr(self, k.on)
+            if on:   # (the handle's input, one row per chain, as every entry,) the switch's value, the counts and the data
+                switch, count, data = k.fields[-3:]
+                parts = [self._accum(kind, c) for c in range(self.n_chains)]
+                if k.input:
+                    out[k.input] = np.tile(self._holdout, (self.n_chains, 1))
+                out[switch] = np.full(self.n_chains, float(on))
+                out[count] = np.array([p[0] for p in parts], dtype=np.int64)
+                out[data] = np.stack([p[1] for p in parts])
         return out
 
     def restore(self, ckpt):
@@ -288,28 +282,23 @@ class Engine:
             self.moran_stats(True)
         elif self._moran_on:
             self.moran_stats(False)
-        if 'hist_stats' in ckpt and np.all(np.asarray(ckpt['hist_stats']) != 0):
-            self.hist_stats(int(np.asarray(ckpt['hist_stats']).ravel()[0]))
-            for c in range(self.n_chains):
-                self.set('hist_count', float(np.asarray(ckpt['hist_count'])[c]), c)
-                self.set('hist_counts', np.asarray(ckpt['hist_counts'])[c].ravel(), c)
-        elif self._hist_bins:
-            self.hist_stats(0)
-        if 'conv_stats' in ckpt and np.all(np.asarray(ckpt['conv_stats']) != 0):
-            self.conv_stats(int(np.asarray(ckpt['conv_stats']).ravel()[0]))
-            for c in range(self.n_chains):
-                self.set('conv_count', float(np.asarray(ckpt['conv_count'])[c]), c)
-                self.set('conv_sums', np.asarray(ckpt['conv_sums'], dtype=np.float64)[c].ravel(), c)
-        elif self._conv_batch:
-            self.conv_stats(0)
-        if 'holdout_stats' in ckpt and np.all(np.asarray(ckpt['holdout_stats']) != 0):
-            self.holdout_data(np.asarray(ckpt['holdout_data'], dtype=np.float64)[0])
-            self.holdout_stats(True)
-            for c in range(self.n_chains):
-                self.set('holdout_count', float(np.asarray(ckpt['holdout_count'])[c]), c)
-                self.set('holdout_sums', np.asarray(ckpt['holdout_sums'], dtype=np.float64)[c].ravel(), c)
-        elif self._holdout_on:
-            self.holdout_stats(False)
+        for k in _lib.ACCUM_KINDS.values():   # (the methods bear the names of the input and of the switch)
+            switch, count, data = k.fields[-3:]
+            if switch in ckpt and np.all(np.asarray(ckpt[switch]) != 0):
+                if k.input:
+                    getattr(self, k.input)(np.asarray(ckpt[k.input], dtype=np.float64)[0])
+                getattr(self, switch)(int(np.asarray(ckpt[switch]).ravel()[0]))
+                for c in range(self.n_chains):
+                    self.set(count, float(np.asarray(ckpt[count])[c]), c)
+                    self.set(data, np.asarray(ckpt[data], dtype=np.float64)[c].ravel(), c)
+            elif getattr(self, k.on):
+                getattr(self, switch)(0)
+
+    def _accum(self, kind, chain):
+        """``(iterations accumulated, the data in their shape and dtype)`` of one accumulator (``_lib.ACCUM_KINDS``) and chain."""
+        k = _lib.ACCUM_KINDS[kind]
+        shape = tuple(self.prob.n if d == 'n' else d for d in k.shape)
+        return int(self.get(k.fields[-2], chain)[0]), self.get(k.fields[-1], chain).reshape(shape).astype(k.dtype, copy=False)
 
     # ---- held-out predictive scoring (state names holdout_*, include/occ_gibbs.h) ----
     def holdout_data(self, W, y=None):
@@ -335,8 +324,8 @@ class Engine:
     def holdout_sums(self, chain=0):
         """``{'count': iterations accumulated, 'sums': (5, H) float64}`` of one chain: per held-out entry ``cnt``, the sum of
         the likelihood L, of l = log L, of l^2, and of pd, the predictive probability of at least one detection."""
-        sums = self.get('holdout_sums', chain)
-        return {'count': int(self.get('holdout_count', chain)[0]), 'sums': sums.reshape(5, sums.size // 5)}
+        count, sums = self._accum('holdout', chain)
+        return {'count': count, 'sums': sums}
 
     # ---- per-site convergence diagnostics (state names conv_*, include/occ_gibbs.h) ----
     def conv_stats(self, batch):
@@ -357,8 +346,8 @@ class Engine:
         ``ref, s1, s2, run, bsq`` of psi, then the same five of eta."""
         batch = self._conv_batch or self._conv_last   # (neither is set when the switch was set by name: ask the handle)
         batch = batch or int(max(self.get('conv_stats', c)[0] for c in range(self.n_chains)))
-        return {'batch': batch, 'count': int(self.get('conv_count', chain)[0]),
-                'sums': self.get('conv_sums', chain).reshape(11, self.prob.n)}
+        count, sums = self._accum('conv', chain)
+        return {'batch': batch, 'count': count, 'sums': sums}
 
     # ---- per-site intervals (state names hist_*, include/occ_gibbs.h) ----
     def hist_stats(self, bins):
@@ -375,9 +364,8 @@ class Engine:
 
     def hist_counts(self, chain=0):
         """``{'bins': B, 'count': iterations accumulated, 'counts': (B, n) uint32}`` of one chain."""
-        counts = self.get('hist_counts', chain)
-        B = counts.size // self.prob.n
-        return {'bins': B, 'count': int(self.get('hist_count', chain)[0]), 'counts': counts.reshape(B, self.prob.n).astype(np.uint32)}
+        count, counts = self._accum('hist', chain)
+        return {'bins': counts.shape[0], 'count': count, 'counts': counts}
 
     # ---- spatial residual check (state names moran_*, include/occ_gibbs.h) ----
     def moran_stats(self, on):
@@ -629,107 +617,14 @@ class EngineGroup:
     def _sums_on(self):   # (a stand-in engine of the tests need not know the sums: it has none switched on)
         return {kind: any(getattr(e, '_sums_on', {}).get(kind, False) for e in self.engines) for kind in _lib.SUMS_KINDS}
 
-    def sums_switch(self, kind, on):
-        for e in self.engines:
-            e.sums_switch(kind, on)
-
-    def sums(self, kind, chain=0):
-        g, i = self.where[chain]
-        return self.engines[g].sums(kind, i)
-
-    # occupied sites per region and draw: the map on every device, the draws routed by chain
-    @property
-    def _regions(self):
-        return getattr(self.engines[0], '_regions', None)
-
-    @property
-    def _region_on(self):
-        return any(getattr(e, '_region_on', False) for e in self.engines)
-
-    def regions(self, ids):
-        for e in self.engines:
-            e.regions(ids)
-
-    def region_stats(self, on):
-        for e in self.engines:
-            e.region_stats(on)
-
-    def region_draws(self, chain=0):
-        g, i = self.where[chain]
-        return self.engines[g].region_draws(i)
-
-    # posterior predictive check: the switch on every device, the draws routed by chain
-    @property
-    def _ppc_on(self):
-        return any(getattr(e, '_ppc_on', False) for e in self.engines)
-
-    def ppc_stats(self, on):
-        for e in self.engines:
-            e.ppc_stats(on)
-
-    def ppc_draws(self, chain=0):
-        g, i = self.where[chain]
-        return self.engines[g].ppc_draws(i)
-
-    # spatial residual check: the switch on every device, the draws routed by chain
-    @property
-    def _moran_on(self):
-        return any(getattr(e, '_moran_on', False) for e in self.engines)
-
-    def moran_stats(self, on):
-        for e in self.engines:
-            e.moran_stats(on)
-
-    def moran_draws(self, chain=0):
-        g, i = self.where[chain]
-        return self.engines[g].moran_draws(i)
-
-    # per-site intervals: the switch on every device, the histograms routed by chain
-    @property
-    def _hist_bins(self):
-        return max(getattr(e, '_hist_bins', 0) for e in self.engines)
-
-    def hist_stats(self, bins):
-        for e in self.engines:
-            e.hist_stats(bins)
-
-    def hist_counts(self, chain=0):
-        g, i = self.where[chain]
-        return self.engines[g].hist_counts(i)
-
-    # per-site convergence diagnostics: the switch on every device, the sums routed by chain
-    @property
-    def _conv_batch(self):
-        return max(getattr(e, '_conv_batch', 0) for e in self.engines)
-
-    def conv_stats(self, batch):
-        for e in self.engines:
-            e.conv_stats(batch)
-
-    def conv_sums(self, chain=0):
-        g, i = self.where[chain]
-        return self.engines[g].conv_sums(i)
-
-    # held-out predictive scoring: the data and the switch on every device, the sums routed by chain
-    @property
-    def _holdout(self):
-        return getattr(self.engines[0], '_holdout', None)
-
-    @property
-    def _holdout_on(self):
-        return any(getattr(e, '_holdout_on', False) for e in self.engines)
-
-    def holdout_data(self, W, y=None):
-        for e in self.engines:
-            e.holdout_data(W, y)
-
-    def holdout_stats(self, on):
-        for e in self.engines:
-            e.holdout_stats(on)
-
-    def holdout_sums(self, chain=0):
-        g, i = self.where[chain]
-        return self.engines[g].holdout_sums(i)
+    # What every feature of Engine needs of a group -- the sums, the regions, ppc, moran, hist, conv, holdout: its switches and
+    # inputs are set on every engine, its results are read from the engine of the chain (the last argument, 0 if left out,
+    # after `lead` others), and what Engine remembers of it is any engine's, the largest, or the first engine's.  A stand-in
+    # engine of the tests need not know a feature: it has it switched off.
+    ON_EVERY = ('sums_switch', 'regions', 'region_stats', 'ppc_stats', 'moran_stats', 'hist_stats', 'conv_stats', 'holdout_data', 'holdout_stats')
+    BY_CHAIN = {'sums': 1, 'region_draws': 0, 'ppc_draws': 0, 'moran_draws': 0, 'hist_counts': 0, 'conv_sums': 0, 'holdout_sums': 0}
+    REMEMBERED = {'_regions': None, '_region_on': any, '_ppc_on': any, '_moran_on': any, '_hist_bins': max, '_conv_batch': max,
+                  '_holdout': None, '_holdout_on': any}
 
     # (the entry points by name are Engine's own: each only names its kind)
     site_stats, site_sums, loglik_stats, loglik_sums = Engine.site_stats, Engine.site_sums, Engine.loglik_stats, Engine.loglik_sums
@@ -778,3 +673,31 @@ class EngineGroup:
             part['n_chains'] = np.int64(len(idx))
             e.restore(part)
         self.keys = [int(k) for k in np.asarray(ckpt['keys'])]
+
+
+def _on_every(name):
+    def call(self, *args, **kw):
+        for e in self.engines:
+            getattr(e, name)(*args, **kw)
+    return call
+
+
+def _by_chain(name, lead):
+    def call(self, *args, chain=0):
+        g, i = self.where[args[lead] if len(args) > lead else chain]
+        return getattr(self.engines[g], name)(*args[:lead], i)
+    return call
+
+
+def _remembered(name, rule):
+    if rule is None:
+        return property(lambda self: getattr(self.engines[0], name, None))
+    return property(lambda self: rule(getattr(e, name, 0) for e in self.engines))
+
+
+for _name in EngineGroup.ON_EVERY:
+    setattr(EngineGroup, _name, _on_every(_name))
+for _name, _lead in EngineGroup.BY_CHAIN.items():
+    setattr(EngineGroup, _name, _by_chain(_name, _lead))
+for _name, _rule in EngineGroup.REMEMBERED.items():
+    setattr(EngineGroup, _name, _remembered(_name, _rule))

@@ -60,6 +60,27 @@ SUMS_KINDS = {
 }
 
 
+class AccumKind(NamedTuple):
+    """One accumulator the engine keeps behind the z update (``ACCUM`` of csrc/occ_accum.hpp), as Python sees it.  ``Engine`` has
+    a method by the name of the switch and, where there is one, of the input."""
+    fields: tuple       # its state names: (the handle's input first, if it needs one,) switch, count, data
+    on: str             # the attribute of ``Engine`` that holds the switch's value while on (bins, batch length, True), else 0
+    slots: int          # arrays per chain on the device
+    dtype: str          # of a chain's data as Python returns and checkpoints them (the count: int64)
+    shape: tuple        # ... and their shape; 'n': the problem's sites
+
+    @property
+    def input(self):
+        return self.fields[0] if len(self.fields) == 4 else None
+
+
+ACCUM_KINDS = {
+    'hist': AccumKind(HIST_FIELDS, '_hist_bins', 1, 'uint32', (-1, 'n')),       # (B, n)
+    'conv': AccumKind(CONV_FIELDS, '_conv_batch', 11, 'float64', (11, -1)),     # (11, n)
+    'holdout': AccumKind(HOLDOUT_FIELDS, '_holdout_on', 5, 'float64', (5, -1)),  # (5, H)
+}
+
+
 class OccProblem(C.Structure):
     _fields_ = [
         ('n', C.c_int64), ('n_surveyed', C.c_int64), ('n_rows', C.c_int64),

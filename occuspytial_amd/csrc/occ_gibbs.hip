@@ -27,6 +27,7 @@
 #include "occ_hist.hpp"
 #include "occ_conv.hpp"
 #include "occ_holdout.hpp"
+#include "occ_accum.hpp"
 #include "occ_layout.hpp"
 
 using namespace occ;
@@ -99,6 +100,11 @@ const SumsKind SUMS[N_SUMS] = {
      {"site_psi", "site_occ", "site_z", "site_eta", "site_eta2"}},
     {OUT_LL, LL_NACC, &Ctx::ll_acc, &Ctx::ll_count, "log-likelihood sums", output_of(OUT_LL).sw, "ll_count", {"ll_lik", "ll_log", "ll_log2"}}};
 
+// The accumulators behind the z update have a table of their own (occ_accum.hpp: ACCUM, plain C++); it agrees with the kernels' headers.
+static_assert(ACCUM[ACC_HIST].slots == 1 && ACCUM[ACC_HIST].elem == sizeof(*HistArgs::cnt) && ACCUM[ACC_HIST].on_min == HIST_BINS_MIN && ACCUM[ACC_HIST].on_max == HIST_BINS_MAX, "ACCUM: hist");
+static_assert(ACCUM[ACC_CONV].slots == CONV_SLOTS && ACCUM[ACC_CONV].elem == sizeof(*ConvArgs::sums) && ACCUM[ACC_CONV].on_max == CONV_BATCH_MAX, "ACCUM: conv");
+static_assert(ACCUM[ACC_HOLD].slots == HOLD_SLOTS && ACCUM[ACC_HOLD].elem == sizeof(*HoldoutArgs::sums), "ACCUM: holdout");
+
 }  // namespace
 
 struct occ_sampler {
@@ -170,65 +176,49 @@ struct occ_sampler {
     struct Ppc : CallRecord<unsigned long long> {
         bool ready = false;
     } ppc;
-    // Spatial residual check (state names moran_stats, moran_draws; logit models; occ_spatial.hpp).  ready: a chain has been
-    // switched on once -- the off-diagonal CSR of Q, the residuals' buffer and the switches are on the device.  The switch is a
-    // word of the handle per chain (on, on_dev), not a bit of ChainScalars::site_on; any: their OR, which decides whether the
-    // two kernels are launched behind the z update (baked into captured graphs: a change drops them).  The record's width is
-    // the SP_NCOL signed integer sums; args: the kernels' argument block (its `rec` follows the record).
-    struct Spatial : CallRecord<long long> {
-        bool ready = false;
+    // The switches of a feature whose kernels stand behind the z update: a word of the handle per chain (on, on_dev), not a
+    // bit of ChainScalars::site_on; any: their OR, which decides whether the kernels are launched (baked into captured graphs:
+    // a change drops them).  switch_alloc / switch_set.
+    struct Switches {
         uint32_t any = 0u;
         std::vector<uint32_t> on;
         uint32_t *on_dev = nullptr;
+    };
+    // Spatial residual check (state names moran_stats, moran_draws; logit models; occ_spatial.hpp).  ready: a chain has been
+    // switched on once -- the off-diagonal CSR of Q, the residuals' buffer and the switches are on the device.  The record's
+    // width is the SP_NCOL signed integer sums; args: the kernels' argument block (its `rec` follows the record).
+    struct Spatial : CallRecord<long long>, Switches {
+        bool ready = false;
         SpArgs args{};
     } spatial;
-    // Per-site intervals (state names hist_stats, hist_count, hist_counts; logit models; occ_hist.hpp).  ready: a chain has been
-    // switched on once -- the histograms [C][B][n], the counts [C] and the switches are on the device.  B belongs to the
-    // handle.  The switch is a word of the handle per chain (on, on_dev), as the spatial residual check's; any: their OR, which
-    // decides whether the kernel is launched behind the z update (baked into captured graphs with B and the addresses: a
-    // change drops them).  bound: per chain an upper bound on every count -- the iterations past burn-in of every call since
-    // the last zeroing or write -- which keeps the 32-bit counts from wrapping.  snap: [C B n] counts, then [C] count words,
-    // part of what a call is re-run from; snapped: taken for the running call.
-    struct Hist {
+    // An accumulator behind the z update (occ_accum.hpp: ACCUM; logit models).  ready: its arrays are on the device -- data,
+    // [slots][C][unit] elements, count, [C], and the switches; unit: the per-chain, per-slot length the data were allocated for.
+    // snap: the data, then the counts, part of what a call is re-run from; snapped: taken for the running call.  The kinds
+    // add their kernel's argument block, filled from here (the addresses and B, L or the sizes travel by value in the captured
+    // launches: a change drops them).
+    struct AccumRun : Switches {
         bool ready = false, snapped = false;
-        uint32_t any = 0u;
-        std::vector<uint32_t> on;
+        uint8_t *data = nullptr, *count = nullptr, *snap = nullptr;
+        size_t unit = 0;
+    };
+    // Per-site intervals (occ_hist.hpp): ready at the first switch-on; B belongs to the handle.  bound: per chain an upper
+    // bound on every count -- the iterations past burn-in of every call since the last zeroing or write -- which keeps the
+    // 32-bit counts from wrapping.
+    struct Hist : AccumRun {
         std::vector<uint64_t> bound;
-        uint32_t *on_dev = nullptr, *snap = nullptr;
         HistArgs args{};
-        size_t words(int C) const { return (size_t)C * (size_t)args.B * (size_t)args.n; }
     } hist;
-    // Per-site convergence diagnostics (state names conv_stats, conv_count, conv_sums; logit models; occ_conv.hpp).  ready: a
-    // chain has been switched on once -- the sums [11][C n], the counts [C] and the switches are on the device.  The batch
-    // length L belongs to the handle.  The switch is a word of the handle per chain (on, on_dev), as the per-site intervals';
-    // any: their OR, which decides whether the kernel is launched behind the z update (baked into captured graphs with L and
-    // the addresses: a change drops them).  snap: [11 C n] sums, then [C] counts, part of what a call is re-run from; snapped:
-    // taken for the running call.
-    struct Conv {
-        bool ready = false, snapped = false;
-        uint32_t any = 0u;
-        std::vector<uint32_t> on;
-        uint32_t *on_dev = nullptr;
-        double *snap = nullptr;
+    // Per-site convergence diagnostics (occ_conv.hpp): ready at the first switch-on; the batch length L belongs to the handle.
+    struct Conv : AccumRun {
         ConvArgs args{};
-        size_t words() const { return (size_t)CONV_SLOTS * args.Cn; }
     } conv;
-    // Held-out predictive scoring (state names holdout_data, holdout_stats, holdout_count, holdout_sums; logit models;
-    // occ_holdout.hpp).  ready: holdout_data has been set once -- the withheld rows, the sums [5][C H], the counts [C] and the
-    // switches are on the device; packed: the data as they were set (what holdout_data reads back).  The switch is a word of
-    // the handle per chain (on, on_dev), as the per-site convergence diagnostics'; any: their OR, which decides whether the
-    // kernel is launched behind the z update (baked into captured graphs with the sizes and the addresses: a change drops
-    // them).  snap: [5 C H] sums, then [C] counts, part of what a call is re-run from; snapped: taken for the running call.
-    struct Holdout {
-        bool ready = false, snapped = false;
-        uint32_t any = 0u;
-        std::vector<uint32_t> on;
+    // Held-out predictive scoring (occ_holdout.hpp): ready once holdout_data has been set -- the withheld rows are on the device
+    // too; packed: the data as they were set (what holdout_data reads back).
+    struct Holdout : AccumRun {
         std::vector<double> packed;
-        uint32_t *on_dev = nullptr;
-        double *snap = nullptr;
         HoldoutArgs args{};
-        size_t words() const { return (size_t)HOLD_SLOTS * args.CH; }
     } holdout;
+    AccumRun &accum(int kind) { return kind == ACC_HIST ? (AccumRun &)hist : kind == ACC_CONV ? (AccumRun &)conv : (AccumRun &)holdout; }
     std::vector<ChainScalars> snap_sc;
     // fixed problem arrays on the device, in upload order: what a group broadcasts from its root (occ_create_group /
     // occ_create_distributed); defer_fixed: allocate only, the bytes arrive by broadcast
@@ -1026,29 +1016,14 @@ int open_window(occ_sampler *s, int64_t n_iter, int64_t burnin, int64_t keep, bo
             HIP_TRY(hipMemcpyAsync(r.snap, c.*SUMS[k].acc, sizeof(double) * nsum, hipMemcpyDeviceToDevice, s->stream));
             HIP_TRY(hipMemcpyAsync(r.snap + nsum, c.*SUMS[k].count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
         }
-        occ_sampler::Hist &hs = s->hist;  // ... and so are the histograms of the per-site intervals
-        hs.snapped = hs.any != 0u;
-        if (hs.snapped) {
-            const size_t nw = hs.words(c.C);
-            if (!hs.snap && (rc = dev_alloc(s, &hs.snap, nw + (size_t)c.C, false))) return rc;
-            HIP_TRY(hipMemcpyAsync(hs.snap, hs.args.cnt, sizeof(uint32_t) * nw, hipMemcpyDeviceToDevice, s->stream));
-            HIP_TRY(hipMemcpyAsync(hs.snap + nw, hs.args.count, sizeof(uint32_t) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
-        }
-        occ_sampler::Conv &cv = s->conv;  // ... and the sums of the per-site convergence diagnostics
-        cv.snapped = cv.any != 0u;
-        if (cv.snapped) {
-            const size_t nw = cv.words();
-            if (!cv.snap && (rc = dev_alloc(s, &cv.snap, nw + (size_t)c.C, false))) return rc;
-            HIP_TRY(hipMemcpyAsync(cv.snap, cv.args.sums, sizeof(double) * nw, hipMemcpyDeviceToDevice, s->stream));
-            HIP_TRY(hipMemcpyAsync(cv.snap + nw, cv.args.count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
-        }
-        occ_sampler::Holdout &ho = s->holdout;  // ... and the sums of the held-out predictive scoring
-        ho.snapped = ho.any != 0u;
-        if (ho.snapped) {
-            const size_t nw = ho.words();
-            if (!ho.snap && (rc = dev_alloc(s, &ho.snap, nw + (size_t)c.C, false))) return rc;
-            HIP_TRY(hipMemcpyAsync(ho.snap, ho.args.sums, sizeof(double) * nw, hipMemcpyDeviceToDevice, s->stream));
-            HIP_TRY(hipMemcpyAsync(ho.snap + nw, ho.args.count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
+        for (int k = 0; k < N_ACCUM; ++k) {  // ... and so are the accumulators behind the z update, in bytes: data, then counts
+            occ_sampler::AccumRun &r = s->accum(k);
+            const size_t nd = (size_t)ACCUM[k].elem * accum_words(ACCUM[k], (size_t)c.C, r.unit), nc = (size_t)ACCUM[k].elem * (size_t)c.C;
+            r.snapped = r.any != 0u;
+            if (!r.snapped) continue;
+            if (!r.snap && (rc = dev_alloc(s, &r.snap, nd + nc, false))) return rc;
+            HIP_TRY(hipMemcpyAsync(r.snap, r.data, nd, hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(hipMemcpyAsync(r.snap + nd, r.count, nc, hipMemcpyDeviceToDevice, s->stream));
         }
         hipLaunchKernelGGL(k_snapshot, dim3((unsigned)std::min<size_t>((Cn + 255) / 256, 2048)), dim3(256), 0, s->stream, c.eta, s->snap_eta, c.z, s->snap_z, c.Xv, s->snap_x,
                            (unsigned long long)Cn, s->rsr.m > 0 ? s->rsr.theta : nullptr, s->snap_theta, (unsigned long long)c.C * (unsigned long long)std::max(s->rsr.m, 0),
@@ -2957,20 +2932,12 @@ static int fallback_to_launch_per_step(occ_sampler *s)
         HIP_TRY(copy_on(s, c.*SUMS[k].acc, s->sums[k].snap, sizeof(double) * nsum, hipMemcpyDeviceToDevice));
         HIP_TRY(copy_on(s, c.*SUMS[k].count, s->sums[k].snap + nsum, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
     }
-    if (s->hist.snapped) {
-        const size_t nw = s->hist.words(c.C);
-        HIP_TRY(copy_on(s, s->hist.args.cnt, s->hist.snap, sizeof(uint32_t) * nw, hipMemcpyDeviceToDevice));
-        HIP_TRY(copy_on(s, s->hist.args.count, s->hist.snap + nw, sizeof(uint32_t) * (size_t)c.C, hipMemcpyDeviceToDevice));
-    }
-    if (s->conv.snapped) {
-        const size_t nw = s->conv.words();
-        HIP_TRY(copy_on(s, s->conv.args.sums, s->conv.snap, sizeof(double) * nw, hipMemcpyDeviceToDevice));
-        HIP_TRY(copy_on(s, s->conv.args.count, s->conv.snap + nw, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
-    }
-    if (s->holdout.snapped) {
-        const size_t nw = s->holdout.words();
-        HIP_TRY(copy_on(s, s->holdout.args.sums, s->holdout.snap, sizeof(double) * nw, hipMemcpyDeviceToDevice));
-        HIP_TRY(copy_on(s, s->holdout.args.count, s->holdout.snap + nw, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
+    for (int k = 0; k < N_ACCUM; ++k) {
+        const occ_sampler::AccumRun &r = s->accum(k);
+        const size_t nd = (size_t)ACCUM[k].elem * accum_words(ACCUM[k], (size_t)c.C, r.unit);
+        if (!r.snapped) continue;
+        HIP_TRY(copy_on(s, r.data, r.snap, nd, hipMemcpyDeviceToDevice));
+        HIP_TRY(copy_on(s, r.count, r.snap + nd, (size_t)ACCUM[k].elem * (size_t)c.C, hipMemcpyDeviceToDevice));
     }
     for (auto &sc : s->snap_sc) sc.err = 0;
     if ((rc = write_scalars(s, s->snap_sc))) return rc;
@@ -3354,6 +3321,24 @@ static int set_ppc_state(occ_sampler *s, int chain, int field, const double *in,
 // chain's state changes.  Whether the two kernels are launched behind the z update follows "is any chain on": a change
 // drops the captured graphs, as flip_output does for a change of level.
 enum : int { MORAN_NONE = -1, MORAN_SWITCH = 0, MORAN_DRAWS = 1 };
+// The switches of a feature behind the z update (occ_sampler::Switches): every chain off, on the device too ...
+static int switch_alloc(occ_sampler *s, occ_sampler::Switches &sw)
+{
+    sw.on.assign((size_t)s->ctx.C, 0u);
+    return dev_alloc(s, &sw.on_dev, sw.on.size());
+}
+// ... and one chain's switch set, after the caller has waited for the side stream: the captured graphs drop when "is any
+// chain on" changes.  The one place that writes `any`.
+static int switch_set(occ_sampler *s, occ_sampler::Switches &sw, int chain, bool on)
+{
+    sw.on[(size_t)chain] = on ? 1u : 0u;
+    HIP_TRY(copy_on(s, sw.on_dev, sw.on.data(), sizeof(uint32_t) * sw.on.size(), hipMemcpyHostToDevice));
+    uint32_t any = 0u;
+    for (uint32_t o : sw.on) any |= o;
+    if (any != sw.any) destroy_graph(s);
+    sw.any = any;
+    return OCC_OK;
+}
 static int moran_field(const std::string &nm) { return nm == "moran_stats" ? MORAN_SWITCH : nm == "moran_draws" ? MORAN_DRAWS : MORAN_NONE; }
 static int moran_refused(occ_sampler *s)
 {
@@ -3410,8 +3395,7 @@ static int moran_init(occ_sampler *s)
     HIP_TRY(copy_on(s, val_dev, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice));
     double2 *res = nullptr;
     if ((rc = dev_alloc(s, &res, (size_t)c.C * n))) return rc;
-    if ((rc = dev_alloc(s, &sp.on_dev, (size_t)c.C))) return rc;
-    sp.on.assign((size_t)c.C, 0u);
+    if ((rc = switch_alloc(s, sp))) return rc;
     sp.args.n = n, sp.args.p = c.p;
     sp.args.Xt = c.Xt, sp.args.eta = c.eta, sp.args.z = c.z;
     sp.args.ptr = ptr_dev, sp.args.col = col_dev, sp.args.val = val_dev;
@@ -3448,256 +3432,55 @@ static int set_moran_state(occ_sampler *s, int chain, int field, const double *i
     int rc;
     WAIT_TRY(s->side);
     if (!sp.ready && (rc = moran_init(s))) return rc;
-    sp.on[(size_t)chain] = on ? 1u : 0u;
-    HIP_TRY(copy_on(s, sp.on_dev, sp.on.data(), sizeof(uint32_t) * sp.on.size(), hipMemcpyHostToDevice));
-    uint32_t any = 0u;
-    for (uint32_t o : sp.on) any |= o;
-    if (any != sp.any) destroy_graph(s);
-    sp.any = any;
-    return OCC_OK;
+    return switch_set(s, sp, chain, on);
 }
 
-// ---- occ_get_state / occ_set_state of the per-site intervals' names (logit models) -------------------------------------
-// hist_stats (1): the chain's switch, a word of the handle: 0 off, B in [HIST_BINS_MIN, HIST_BINS_MAX] on with B bins; B
-// belongs to the handle.  hist_count (1): the chain's count of accumulated iterations.  hist_counts (B n): the chain's
-// histograms bin-major [bin][site] as doubles (32-bit counts: exact).  The first switch-on allocates; switching on zeroes
-// the chain's part; 0 keeps everything readable.  The count and the counts are writable while the chain's switch is on
-// (checkpoint restore).  Before the first switch-on every name answers OCC_E_STATE (switching a chain OFF before that is
-// accepted and does nothing).  Nothing of a chain's state changes.  Whether the kernel is launched behind the z update
-// follows "is any chain on"; a change of that, of B or of the histograms' address drops the captured graphs.
-enum : int { HIST_NONE = -1, HIST_SWITCH = 0, HIST_COUNT = 1, HIST_COUNTS = 2 };
-static int hist_field(const std::string &nm)
+// ---- occ_get_state / occ_set_state of the names of the accumulators behind the z update (ACCUM; logit models) ----------
+// Per kind: the chain's switch (1), a word of the handle; its count of accumulated iterations (1); its data, the chain's part
+// of every slot, slot-major (slots x unit).  Switching on zeroes the chain's part; 0 keeps everything readable.  The count
+// and the data are writable while the chain's switch is on (checkpoint restore).  Nothing of a chain's state changes.  Whether
+// the kernel is launched behind the z update follows "is any chain on"; a change of that, of a size the kernel takes by
+// value or of an address drops the captured graphs.  What differs:
+//   hist_stats     0 off, B in [HIST_BINS_MIN, HIST_BINS_MAX] on with B bins; B belongs to the handle.  hist_counts (B n): the
+//                  histograms bin-major [bin][site] as doubles (32-bit counts: exact).  The first switch-on allocates.
+//   conv_stats     0 off, L in [1, 2^30] on with batch length L; L belongs to the handle.  conv_sums (11 n).  The first
+//                  switch-on allocates.
+//   holdout_stats  0 or 1.  holdout_sums (5 H).  holdout_data (2 + 2 H + 1 + R + R q): the handle's withheld data, through
+//                  any chain index -- [H, R, site[H], ptr[H + 1], y[R], W[R q] row-major]; validated as a whole; set only
+//                  while no chain's switch is on; allocates; setting it again replaces the data and zeroes every chain's sums.
+// Before the first switch-on -- the first holdout_data -- every name of the kind answers OCC_E_STATE (switching a chain of the
+// first two OFF before that is accepted and does nothing).
+static int accum_refused(occ_sampler *s, const Accum &a)
 {
-    return nm == "hist_stats" ? HIST_SWITCH : nm == "hist_count" ? HIST_COUNT : nm == "hist_counts" ? HIST_COUNTS : HIST_NONE;
+    if (s->probit) return set_error(s, OCC_E_STATE, (std::string(a.what) + " " + a.verb + " not available for the probit model").c_str());
+    return set_error(s, OCC_E_STATE, a.not_ready);
 }
-static int hist_refused(occ_sampler *s)
+// The kind's data for per-chain, per-slot length `unit`, every chain's data and count at zero: at first use with the count
+// and the switches, later in place of the old data and snapshot (freed: nothing is in flight to them, both streams have been
+// waited for).  The caller fills its kernel's argument block from the result.
+static int accum_alloc(occ_sampler *s, int kind, size_t unit)
 {
-    if (s->probit) return set_error(s, OCC_E_STATE, "per-site intervals are not available for the probit model");
-    return set_error(s, OCC_E_STATE, "per-site intervals have not been switched on for this handle (set hist_stats first)");
-}
-// The histograms for B bins: at the handle's first switch-on, and again for another B while every chain is off (the old ones
-// are freed: nothing is in flight to them, both streams have been waited for).  Every chain's counts start at zero.
-static int hist_alloc(occ_sampler *s, int B)
-{
-    Ctx &c = s->ctx;
-    occ_sampler::Hist &hs = s->hist;
+    const size_t C = (size_t)s->ctx.C, elem = (size_t)ACCUM[kind].elem;
+    occ_sampler::AccumRun &r = s->accum(kind);
     int rc;
     WAIT_TRY(s->stream);
-    destroy_graph(s);  // (the addresses and B travel by value in the captured launches)
-    for (uint32_t **old : {&hs.args.cnt, &hs.snap}) {
+    destroy_graph(s);  // (the addresses and the sizes travel by value in the captured launches)
+    for (uint8_t **old : {&r.data, &r.snap}) {
         if (!*old) continue;
         s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), (void *)*old), s->allocs.end());
         HIP_TRY(hipFree(*old));
         *old = nullptr;
     }
-    hs.snapped = false;
-    hs.args.n = c.n, hs.args.p = c.p, hs.args.B = B;
-    hs.args.Xt = c.Xt, hs.args.eta = c.eta;
-    if ((rc = dev_alloc(s, &hs.args.cnt, hs.words(c.C)))) return rc;
-    if (!hs.ready) {
-        if ((rc = dev_alloc(s, &hs.args.count, (size_t)c.C))) return rc;
-        if ((rc = dev_alloc(s, &hs.on_dev, (size_t)c.C))) return rc;
-        hs.on.assign((size_t)c.C, 0u);
-        hs.bound.assign((size_t)c.C, 0ull);
-        hs.args.on = hs.on_dev;
+    r.snapped = false;
+    r.unit = unit;
+    if ((rc = dev_alloc(s, &r.data, elem * accum_words(ACCUM[kind], C, unit)))) return rc;
+    if (!r.on_dev) {
+        if ((rc = dev_alloc(s, &r.count, elem * C)) || (rc = switch_alloc(s, r))) return rc;
     } else {
-        HIP_TRY(fill_on(s, hs.args.count, 0, sizeof(uint32_t) * (size_t)c.C));
-        hs.bound.assign((size_t)c.C, 0ull);
+        HIP_TRY(fill_on(s, r.count, 0, elem * C));
     }
-    hs.ready = true;
+    r.ready = true;
     return OCC_OK;
-}
-static int get_hist_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
-{
-    const occ_sampler::Hist &hs = s->hist;
-    if (s->probit || !hs.ready) return hist_refused(s);
-    if (field == HIST_SWITCH) {
-        v.assign(1, hs.on[(size_t)chain] ? (double)hs.args.B : 0.0);
-        return OCC_OK;
-    }
-    const size_t per = field == HIST_COUNT ? (size_t)1 : (size_t)hs.args.B * (size_t)hs.args.n;
-    const uint32_t *src = field == HIST_COUNT ? hs.args.count + chain : hs.args.cnt + (size_t)chain * per;
-    std::vector<uint32_t> w(per);
-    HIP_TRY(copy_on(s, w.data(), src, sizeof(uint32_t) * per, hipMemcpyDeviceToHost));
-    v.assign(w.begin(), w.end());
-    return OCC_OK;
-}
-static int set_hist_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
-{
-    occ_sampler::Hist &hs = s->hist;
-    if (s->probit) return hist_refused(s);
-    if (field != HIST_SWITCH) {
-        if (!hs.ready) return hist_refused(s);
-        if (!hs.on[(size_t)chain]) return set_error(s, OCC_E_STATE, "per-site intervals are switched off for this chain (set hist_stats first)");
-        const size_t per = field == HIST_COUNT ? (size_t)1 : (size_t)hs.args.B * (size_t)hs.args.n;
-        if ((size_t)len != per) return set_error(s, OCC_E_STATE, "wrong length");
-        std::vector<uint32_t> w(per);
-        uint64_t top = 0;
-        for (size_t k = 0; k < per; ++k) {
-            if (!(in[k] >= 0.0) || !(in[k] < 0x1.0p32) || in[k] != std::floor(in[k]))
-                return set_error(s, OCC_E_BADARG, "hist_count and hist_counts are whole numbers in [0, 2^32)");
-            w[k] = (uint32_t)in[k];
-            top = std::max<uint64_t>(top, w[k]);
-        }
-        uint32_t *dst = field == HIST_COUNT ? hs.args.count + chain : hs.args.cnt + (size_t)chain * per;
-        HIP_TRY(copy_on(s, dst, w.data(), sizeof(uint32_t) * per, hipMemcpyHostToDevice));
-        hs.bound[(size_t)chain] = std::max(hs.bound[(size_t)chain], top);  // (still an upper bound on every count of the chain)
-        return OCC_OK;
-    }
-    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
-    const double b = in[0];
-    if (b != 0.0 && !(b >= (double)HIST_BINS_MIN && b <= (double)HIST_BINS_MAX && b == std::floor(b)))
-        return set_error(s, OCC_E_BADARG, "hist_stats is 0 or a number of bins from 4 to 1024");
-    const int B = (int)b;
-    if (B == 0 && !hs.ready) return OCC_OK;  // never switched on: nothing to switch off
-    int rc;
-    WAIT_TRY(s->side);
-    if (B != 0 && hs.ready && B != hs.args.B && hs.any)
-        return set_error(s, OCC_E_BADARG, ("the handle's per-site histograms have " + std::to_string(hs.args.B) +
-                                           " bins while a chain is switched on: switch every chain off before asking for another number").c_str());
-    if (B != 0 && (!hs.ready || B != hs.args.B) && (rc = hist_alloc(s, B))) return rc;
-    if (B != 0) {  // switching on zeroes the chain's part, as site_stats does
-        const size_t per = (size_t)B * (size_t)hs.args.n;
-        HIP_TRY(fill_on(s, hs.args.cnt + (size_t)chain * per, 0, sizeof(uint32_t) * per));
-        HIP_TRY(fill_on(s, hs.args.count + chain, 0, sizeof(uint32_t)));
-        hs.bound[(size_t)chain] = 0ull;
-    }
-    hs.on[(size_t)chain] = B != 0 ? 1u : 0u;
-    HIP_TRY(copy_on(s, hs.on_dev, hs.on.data(), sizeof(uint32_t) * hs.on.size(), hipMemcpyHostToDevice));
-    uint32_t any = 0u;
-    for (uint32_t o : hs.on) any |= o;
-    if (any != hs.any) destroy_graph(s);
-    hs.any = any;
-    return OCC_OK;
-}
-
-// ---- occ_get_state / occ_set_state of the per-site convergence diagnostics' names (logit models) ------------------------
-// conv_stats (1): the chain's switch, a word of the handle: 0 off, L in [1, 2^30] on with batch length L; L belongs to the
-// handle.  conv_count (1): the chain's count of accumulated iterations.  conv_sums (11 n): the chain's slots, slot-major
-// [slot][site].  The first switch-on allocates; switching on zeroes the chain's part; 0 keeps everything readable.  The count
-// and the sums are writable while the chain's switch is on (checkpoint restore).  Before the first switch-on every name
-// answers OCC_E_STATE (switching a chain OFF before that is accepted and does nothing).  Nothing of a chain's state changes.
-// Whether the kernel is launched behind the z update follows "is any chain on"; a change of that, of L or of the sums'
-// address drops the captured graphs.
-enum : int { CONV_NONE = -1, CONV_SWITCH = 0, CONV_COUNT = 1, CONV_SUMS = 2 };
-static int conv_field(const std::string &nm)
-{
-    return nm == "conv_stats" ? CONV_SWITCH : nm == "conv_count" ? CONV_COUNT : nm == "conv_sums" ? CONV_SUMS : CONV_NONE;
-}
-static int conv_refused(occ_sampler *s)
-{
-    if (s->probit) return set_error(s, OCC_E_STATE, "per-site convergence diagnostics are not available for the probit model");
-    return set_error(s, OCC_E_STATE, "per-site convergence diagnostics have not been switched on for this handle (set conv_stats first)");
-}
-// The sums, at the handle's first switch-on: their size does not depend on L, so they are allocated once.
-static int conv_alloc(occ_sampler *s)
-{
-    Ctx &c = s->ctx;
-    occ_sampler::Conv &cv = s->conv;
-    int rc;
-    WAIT_TRY(s->stream);
-    destroy_graph(s);  // (the addresses and L travel by value in the captured launches)
-    cv.args.n = c.n, cv.args.p = c.p;
-    cv.args.Cn = (size_t)c.C * (size_t)c.n;
-    cv.args.Xt = c.Xt, cv.args.eta = c.eta;
-    if ((rc = dev_alloc(s, &cv.args.sums, cv.words()))) return rc;
-    if ((rc = dev_alloc(s, &cv.args.count, (size_t)c.C))) return rc;
-    if ((rc = dev_alloc(s, &cv.on_dev, (size_t)c.C))) return rc;
-    cv.on.assign((size_t)c.C, 0u);
-    cv.args.on = cv.on_dev;
-    cv.ready = true;
-    return OCC_OK;
-}
-static int get_conv_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
-{
-    const occ_sampler::Conv &cv = s->conv;
-    if (s->probit || !cv.ready) return conv_refused(s);
-    if (field == CONV_SWITCH) {
-        v.assign(1, cv.on[(size_t)chain] ? (double)cv.args.L : 0.0);
-        return OCC_OK;
-    }
-    if (field == CONV_COUNT) {
-        v.resize(1);
-        HIP_TRY(copy_on(s, v.data(), cv.args.count + chain, sizeof(double), hipMemcpyDeviceToHost));
-        return OCC_OK;
-    }
-    const size_t n = (size_t)cv.args.n;
-    v.resize((size_t)CONV_SLOTS * n);
-    for (int k = 0; k < CONV_SLOTS; ++k)  // the chain's part of every slot
-        HIP_TRY(copy_on(s, v.data() + (size_t)k * n, cv.args.sums + (size_t)k * cv.args.Cn + (size_t)chain * n, sizeof(double) * n, hipMemcpyDeviceToHost));
-    return OCC_OK;
-}
-static int set_conv_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
-{
-    occ_sampler::Conv &cv = s->conv;
-    if (s->probit) return conv_refused(s);
-    const auto whole = [](double x) { return x >= 0.0 && x < 0x1.0p53 && x == std::floor(x); };
-    if (field != CONV_SWITCH) {
-        if (!cv.ready) return conv_refused(s);
-        if (!cv.on[(size_t)chain]) return set_error(s, OCC_E_STATE, "per-site convergence diagnostics are switched off for this chain (set conv_stats first)");
-        const size_t n = (size_t)cv.args.n;
-        if ((size_t)len != (field == CONV_COUNT ? (size_t)1 : (size_t)CONV_SLOTS * n)) return set_error(s, OCC_E_STATE, "wrong length");
-        if (field == CONV_COUNT) {
-            if (!whole(in[0])) return set_error(s, OCC_E_BADARG, "conv_count is a whole number >= 0");
-            HIP_TRY(copy_on(s, cv.args.count + chain, in, sizeof(double), hipMemcpyHostToDevice));
-            return OCC_OK;
-        }
-        for (size_t i = 0; i < n; ++i)  // slot 0 is cnt: the sites of a chain have counted the same iterations
-            if (!whole(in[i]) || in[i] != in[0])
-                return set_error(s, OCC_E_BADARG, "the cnt slot of conv_sums holds one whole number >= 0 at every site");
-        for (int k = 0; k < CONV_SLOTS; ++k)
-            HIP_TRY(copy_on(s, cv.args.sums + (size_t)k * cv.args.Cn + (size_t)chain * n, in + (size_t)k * n, sizeof(double) * n, hipMemcpyHostToDevice));
-        return OCC_OK;
-    }
-    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
-    const double b = in[0];
-    if (b != 0.0 && !(b >= 1.0 && b <= (double)CONV_BATCH_MAX && b == std::floor(b)))
-        return set_error(s, OCC_E_BADARG, "conv_stats is 0 or a batch length from 1 to 2^30");
-    const int L = (int)b;
-    if (L == 0 && !cv.ready) return OCC_OK;  // never switched on: nothing to switch off
-    int rc;
-    WAIT_TRY(s->side);
-    if (L != 0 && cv.ready && L != cv.args.L && cv.any)
-        return set_error(s, OCC_E_BADARG, ("the handle's per-site convergence diagnostics have batch length " + std::to_string(cv.args.L) +
-                                           " while a chain is switched on: switch every chain off before asking for another length").c_str());
-    if (L != 0 && !cv.ready && (rc = conv_alloc(s))) return rc;
-    if (L != 0) {  // switching on zeroes the chain's part, as site_stats does
-        if (L != cv.args.L) {
-            WAIT_TRY(s->stream);
-            destroy_graph(s);
-            cv.args.L = L;
-        }
-        const size_t n = (size_t)cv.args.n;
-        for (int k = 0; k < CONV_SLOTS; ++k)
-            HIP_TRY(fill_on(s, cv.args.sums + (size_t)k * cv.args.Cn + (size_t)chain * n, 0, sizeof(double) * n));
-        HIP_TRY(fill_on(s, cv.args.count + chain, 0, sizeof(double)));
-    }
-    cv.on[(size_t)chain] = L != 0 ? 1u : 0u;
-    HIP_TRY(copy_on(s, cv.on_dev, cv.on.data(), sizeof(uint32_t) * cv.on.size(), hipMemcpyHostToDevice));
-    uint32_t any = 0u;
-    for (uint32_t o : cv.on) any |= o;
-    if (any != cv.any) destroy_graph(s);
-    cv.any = any;
-    return OCC_OK;
-}
-
-// ---- occ_get_state / occ_set_state of the held-out predictive scoring's names (logit models) ----------------------------
-// holdout_data (2 + 2 H + 1 + R + R q): the handle's withheld data, through any chain index -- [H, R, site[H], ptr[H + 1],
-// y[R], W[R q] row-major]; validated as a whole; set only while no chain's switch is on; allocates at first use; setting it
-// again replaces the data and zeroes every chain's sums.  holdout_stats (1): the chain's switch, 0 or 1; switching on zeroes
-// the chain's part.  holdout_count (1): the chain's count of accumulated iterations.  holdout_sums (5 H): the chain's slots,
-// slot-major [slot][entry].  The count and the sums are writable while the chain's switch is on (checkpoint restore).  Before
-// the first holdout_data every name answers OCC_E_STATE.  Nothing of a chain's state changes.  Whether the kernel is launched
-// behind the z update follows "is any chain on"; a change of that, of a size or of an address drops the captured graphs.
-enum : int { HOLD_NONE = -1, HOLD_DATA = 0, HOLD_SWITCH = 1, HOLD_COUNT = 2, HOLD_SUMS = 3 };
-static int holdout_field(const std::string &nm)
-{
-    return nm == "holdout_data" ? HOLD_DATA : nm == "holdout_stats" ? HOLD_SWITCH : nm == "holdout_count" ? HOLD_COUNT : nm == "holdout_sums" ? HOLD_SUMS : HOLD_NONE;
-}
-static int holdout_refused(occ_sampler *s)
-{
-    if (s->probit) return set_error(s, OCC_E_STATE, "held-out scoring is not available for the probit model");
-    return set_error(s, OCC_E_STATE, "no held-out data have been set for this handle (set holdout_data first)");
 }
 // The packed array as a whole: OCC_OK, or OCC_E_BADARG with the first rule it breaks.  On success the pieces as the device
 // takes them.
@@ -3753,122 +3536,163 @@ static int holdout_put(occ_sampler *s, const void **dst, const void *src, size_t
     *dst = d;
     return OCC_OK;
 }
-// The withheld data and the sums for them: at the handle's first holdout_data, and again for every later one (every chain is
-// off then; the old arrays are freed: nothing is in flight to them, both streams have been waited for).  Every chain's sums
-// and count start at zero.
-static int holdout_alloc(occ_sampler *s, const std::vector<int> &site, const std::vector<int> &ptr, const std::vector<uint8_t> &seen,
-                         const std::vector<uint8_t> &y, const std::vector<double> &Wt)
+// The histograms for B bins: at the handle's first switch-on, and again for another B while every chain is off.
+static int hist_alloc(occ_sampler *s, int B)
 {
-    Ctx &c = s->ctx;
+    const Ctx &c = s->ctx;
+    occ_sampler::Hist &hs = s->hist;
+    const int rc = accum_alloc(s, ACC_HIST, (size_t)B * (size_t)c.n);
+    if (rc) return rc;
+    hs.bound.assign((size_t)c.C, 0ull);
+    hs.args.n = c.n, hs.args.p = c.p, hs.args.B = B;
+    hs.args.Xt = c.Xt, hs.args.eta = c.eta;
+    hs.args.cnt = (uint32_t *)hs.data, hs.args.count = (uint32_t *)hs.count, hs.args.on = hs.on_dev;
+    return OCC_OK;
+}
+// The batch-means sums, at the handle's first switch-on: their size does not depend on L, so they are allocated once.
+static int conv_alloc(occ_sampler *s)
+{
+    const Ctx &c = s->ctx;
+    occ_sampler::Conv &cv = s->conv;
+    const int rc = accum_alloc(s, ACC_CONV, (size_t)c.n);
+    if (rc) return rc;
+    cv.args.n = c.n, cv.args.p = c.p;
+    cv.args.Cn = (size_t)c.C * (size_t)c.n;
+    cv.args.Xt = c.Xt, cv.args.eta = c.eta;
+    cv.args.sums = (double *)cv.data, cv.args.count = (double *)cv.count, cv.args.on = cv.on_dev;
+    return OCC_OK;
+}
+// holdout_data: the withheld data and the sums for them, at the handle's first and again at every later one (every chain is
+// off then; the old arrays are freed as accum_alloc frees the sums).
+static int holdout_set_data(occ_sampler *s, const double *in, int64_t len)
+{
+    const Ctx &c = s->ctx;
     occ_sampler::Holdout &ho = s->holdout;
     HoldoutArgs &a = ho.args;
+    if (ho.any) return set_error(s, OCC_E_STATE, "holdout_data cannot be set while a chain has holdout_stats on");
+    std::vector<int> site, ptr;
+    std::vector<uint8_t> seen, y;
+    std::vector<double> Wt;
     int rc;
-    WAIT_TRY(s->stream);
-    destroy_graph(s);  // (the addresses and the sizes travel by value in the captured launches)
-    for (void *old : {(void *)a.site, (void *)a.ptr, (void *)a.seen, (void *)a.y, (void *)a.Wt, (void *)a.sums, (void *)ho.snap}) {
+    if ((rc = holdout_parse(s, in, len, site, ptr, seen, y, Wt))) return rc;  // (all or nothing: nothing has changed yet)
+    WAIT_TRY(s->side);
+    rc = accum_alloc(s, ACC_HOLD, site.size());
+    ho.ready = false;  // (until the withheld rows are on the device too; after a failure, until the next holdout_data)
+    if (rc) return rc;
+    for (void *old : {(void *)a.site, (void *)a.ptr, (void *)a.seen, (void *)a.y, (void *)a.Wt}) {
         if (!old) continue;
         s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), old), s->allocs.end());
         HIP_TRY(hipFree(old));
     }
-    a.site = a.ptr = nullptr, a.seen = a.y = nullptr, a.Wt = nullptr, a.sums = ho.snap = nullptr;
-    ho.snapped = false;
+    a.site = a.ptr = nullptr, a.seen = a.y = nullptr, a.Wt = nullptr;
     a.n = c.n, a.p = c.p, a.q = c.q, a.H = (int)site.size(), a.R = (int)y.size();
     a.CH = (size_t)c.C * site.size();
     a.Xt = c.Xt, a.eta = c.eta;
+    a.sums = (double *)ho.data, a.count = (double *)ho.count, a.on = ho.on_dev;
     const void *d_site = nullptr, *d_ptr = nullptr, *d_seen = nullptr, *d_y = nullptr, *d_Wt = nullptr;
     if ((rc = holdout_put(s, &d_site, site.data(), sizeof(int) * site.size())) || (rc = holdout_put(s, &d_ptr, ptr.data(), sizeof(int) * ptr.size())) ||
         (rc = holdout_put(s, &d_seen, seen.data(), seen.size())) || (rc = holdout_put(s, &d_y, y.data(), y.size())) ||
         (rc = holdout_put(s, &d_Wt, Wt.data(), sizeof(double) * Wt.size())))
         return rc;
     a.site = (const int *)d_site, a.ptr = (const int *)d_ptr, a.seen = (const uint8_t *)d_seen, a.y = (const uint8_t *)d_y, a.Wt = (const double *)d_Wt;
-    if ((rc = dev_alloc(s, &a.sums, ho.words()))) return rc;
-    if (!ho.on_dev) {
-        if ((rc = dev_alloc(s, &a.count, (size_t)c.C))) return rc;
-        if ((rc = dev_alloc(s, &ho.on_dev, (size_t)c.C))) return rc;
-        ho.on.assign((size_t)c.C, 0u);
-        a.on = ho.on_dev;
-    } else {
-        HIP_TRY(fill_on(s, a.count, 0, sizeof(double) * (size_t)c.C));
-    }
+    ho.packed.assign(in, in + len);
     ho.ready = true;
     return OCC_OK;
 }
-static int get_holdout_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
+// What the chains' common switch value is while on (B, L, 1) ...
+static double accum_on_value(const occ_sampler *s, int kind) { return kind == ACC_HIST ? (double)s->hist.args.B : kind == ACC_CONV ? (double)s->conv.args.L : 1.0; }
+// ... and what a switch-on with `val` asks of the kind before the chain's part is zeroed: B and L belong to the handle, so
+// another value is refused while a chain is on; the histograms depend on B in size, the sums on L not at all.
+static int accum_switch_on(occ_sampler *s, int kind, int val)
 {
-    const occ_sampler::Holdout &ho = s->holdout;
-    if (s->probit || !ho.ready) return holdout_refused(s);
-    if (field == HOLD_DATA) {
-        v = ho.packed;
+    occ_sampler::Hist &hs = s->hist;
+    occ_sampler::Conv &cv = s->conv;
+    int rc;
+    switch (kind) {
+        case ACC_HIST:
+            if (hs.ready && val != hs.args.B && hs.any)
+                return set_error(s, OCC_E_BADARG, ("the handle's per-site histograms have " + std::to_string(hs.args.B) +
+                                                   " bins while a chain is switched on: switch every chain off before asking for another number").c_str());
+            return !hs.ready || val != hs.args.B ? hist_alloc(s, val) : OCC_OK;
+        case ACC_CONV:
+            if (cv.ready && val != cv.args.L && cv.any)
+                return set_error(s, OCC_E_BADARG, ("the handle's per-site convergence diagnostics have batch length " + std::to_string(cv.args.L) +
+                                                   " while a chain is switched on: switch every chain off before asking for another length").c_str());
+            if (!cv.ready && (rc = conv_alloc(s))) return rc;
+            if (val != cv.args.L) {
+                WAIT_TRY(s->stream);
+                destroy_graph(s);
+                cv.args.L = val;
+            }
+            return OCC_OK;
+        default: return OCC_OK;  // (held-out scoring: everything came with holdout_data)
+    }
+}
+// One field of a chain: count is one element, data the chain's part of every slot; on the device at dev(slot).
+static int get_accum_state(occ_sampler *s, int chain, int kind, int field, std::vector<double> &v)
+{
+    const Accum &a = ACCUM[kind];
+    const occ_sampler::AccumRun &r = s->accum(kind);
+    if (s->probit || !r.ready) return accum_refused(s, a);
+    if (field == ACC_INPUT) {
+        v = s->holdout.packed;
         return OCC_OK;
     }
-    if (field == HOLD_SWITCH) {
-        v.assign(1, ho.on[(size_t)chain] ? 1.0 : 0.0);
+    if (field == ACC_SWITCH) {
+        v.assign(1, r.on[(size_t)chain] ? accum_on_value(s, kind) : 0.0);
         return OCC_OK;
     }
-    if (field == HOLD_COUNT) {
-        v.resize(1);
-        HIP_TRY(copy_on(s, v.data(), ho.args.count + chain, sizeof(double), hipMemcpyDeviceToHost));
-        return OCC_OK;
+    const size_t elem = (size_t)a.elem, per = field == ACC_COUNT ? (size_t)1 : r.unit, nslot = field == ACC_COUNT ? (size_t)1 : (size_t)a.slots;
+    std::vector<uint32_t> w(elem == 4 ? nslot * per : 0);  // (32-bit counts come through here, float64 sums go straight to v)
+    v.resize(nslot * per);
+    uint8_t *dst = elem == 4 ? (uint8_t *)w.data() : (uint8_t *)v.data();
+    for (size_t k = 0; k < nslot; ++k) {
+        const uint8_t *src = field == ACC_COUNT ? r.count + elem * (size_t)chain : r.data + elem * accum_offset((size_t)s->ctx.C, per, k, (size_t)chain);
+        HIP_TRY(copy_on(s, dst + elem * k * per, src, elem * per, hipMemcpyDeviceToHost));
     }
-    const size_t H = (size_t)ho.args.H;
-    v.resize((size_t)HOLD_SLOTS * H);
-    for (int k = 0; k < HOLD_SLOTS; ++k)  // the chain's part of every slot
-        HIP_TRY(copy_on(s, v.data() + (size_t)k * H, ho.args.sums + (size_t)k * ho.args.CH + (size_t)chain * H, sizeof(double) * H, hipMemcpyDeviceToHost));
+    if (elem == 4) v.assign(w.begin(), w.end());
     return OCC_OK;
 }
-static int set_holdout_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+static int set_accum_state(occ_sampler *s, int chain, int kind, int field, const double *in, int64_t len)
 {
-    occ_sampler::Holdout &ho = s->holdout;
-    if (s->probit) return holdout_refused(s);
-    const auto whole = [](double x) { return x >= 0.0 && x < 0x1.0p53 && x == std::floor(x); };
-    int rc;
-    if (field == HOLD_DATA) {
-        if (ho.any) return set_error(s, OCC_E_STATE, "holdout_data cannot be set while a chain has holdout_stats on");
-        std::vector<int> site, ptr;
-        std::vector<uint8_t> seen, y;
-        std::vector<double> Wt;
-        if ((rc = holdout_parse(s, in, len, site, ptr, seen, y, Wt))) return rc;  // (all or nothing: nothing has changed yet)
-        WAIT_TRY(s->side);
-        if ((rc = holdout_alloc(s, site, ptr, seen, y, Wt))) {
-            ho.ready = false;
-            return rc;
+    const Accum &a = ACCUM[kind];
+    occ_sampler::AccumRun &r = s->accum(kind);
+    const size_t elem = (size_t)a.elem, C = (size_t)s->ctx.C;
+    if (s->probit) return accum_refused(s, a);
+    if (field == ACC_INPUT) return holdout_set_data(s, in, len);
+    if (!r.ready && (field != ACC_SWITCH || a.name[ACC_INPUT])) return accum_refused(s, a);  // (a kind with an input is switched only after it)
+    if (field != ACC_SWITCH) {
+        if (!r.on[(size_t)chain])
+            return set_error(s, OCC_E_STATE, (std::string(a.what) + " " + a.verb + " switched off for this chain (set " + a.name[ACC_SWITCH] + " first)").c_str());
+        const size_t per = field == ACC_COUNT ? (size_t)1 : r.unit, nslot = field == ACC_COUNT ? (size_t)1 : (size_t)a.slots;
+        if ((size_t)len != nslot * per) return set_error(s, OCC_E_STATE, "wrong length");
+        if (const char *why = accum_write_refusal(a, field, in, (size_t)len, per)) return set_error(s, OCC_E_BADARG, why);
+        const std::vector<uint32_t> w(in, in + (elem == 4 ? len : 0));
+        const uint8_t *src = elem == 4 ? (const uint8_t *)w.data() : (const uint8_t *)in;
+        for (size_t k = 0; k < nslot; ++k) {
+            uint8_t *dst = field == ACC_COUNT ? r.count + elem * (size_t)chain : r.data + elem * accum_offset(C, per, k, (size_t)chain);
+            HIP_TRY(copy_on(s, dst, src + elem * k * per, elem * per, hipMemcpyHostToDevice));
         }
-        ho.packed.assign(in, in + len);
-        return OCC_OK;
-    }
-    if (!ho.ready) return holdout_refused(s);
-    const size_t H = (size_t)ho.args.H;
-    if (field != HOLD_SWITCH) {
-        if (!ho.on[(size_t)chain]) return set_error(s, OCC_E_STATE, "held-out scoring is switched off for this chain (set holdout_stats first)");
-        if ((size_t)len != (field == HOLD_COUNT ? (size_t)1 : (size_t)HOLD_SLOTS * H)) return set_error(s, OCC_E_STATE, "wrong length");
-        if (field == HOLD_COUNT) {
-            if (!whole(in[0])) return set_error(s, OCC_E_BADARG, "holdout_count is a whole number >= 0");
-            HIP_TRY(copy_on(s, ho.args.count + chain, in, sizeof(double), hipMemcpyHostToDevice));
-            return OCC_OK;
-        }
-        for (size_t h = 0; h < H; ++h)  // slot 0 is cnt: the entries of a chain have counted the same iterations
-            if (!whole(in[h]) || in[h] != in[0])
-                return set_error(s, OCC_E_BADARG, "the cnt slot of holdout_sums holds one whole number >= 0 at every entry");
-        for (int k = 0; k < HOLD_SLOTS; ++k)
-            HIP_TRY(copy_on(s, ho.args.sums + (size_t)k * ho.args.CH + (size_t)chain * H, in + (size_t)k * H, sizeof(double) * H, hipMemcpyHostToDevice));
+        if (kind == ACC_HIST)  // (still an upper bound on every count of the chain)
+            s->hist.bound[(size_t)chain] = std::max<uint64_t>(s->hist.bound[(size_t)chain], *std::max_element(w.begin(), w.end()));
         return OCC_OK;
     }
     if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
-    if (in[0] != 0.0 && in[0] != 1.0) return set_error(s, OCC_E_BADARG, "holdout_stats is 0 or 1");
+    if (!accum_switch_ok(a, in[0])) return set_error(s, OCC_E_BADARG, a.bad_switch);
+    const int val = (int)in[0];
+    if (val == 0 && !r.ready) return OCC_OK;  // never switched on: nothing to switch off
+    int rc;
     WAIT_TRY(s->side);
-    if (in[0] != 0.0) {  // switching on zeroes the chain's part, as site_stats does
-        for (int k = 0; k < HOLD_SLOTS; ++k)
-            HIP_TRY(fill_on(s, ho.args.sums + (size_t)k * ho.args.CH + (size_t)chain * H, 0, sizeof(double) * H));
-        HIP_TRY(fill_on(s, ho.args.count + chain, 0, sizeof(double)));
+    if (val != 0) {  // switching on zeroes the chain's part, as site_stats does
+        if ((rc = accum_switch_on(s, kind, val))) return rc;
+        for (size_t k = 0; k < (size_t)a.slots; ++k)
+            HIP_TRY(fill_on(s, r.data + elem * accum_offset(C, r.unit, k, (size_t)chain), 0, elem * r.unit));
+        HIP_TRY(fill_on(s, r.count + elem * (size_t)chain, 0, elem));
+        if (kind == ACC_HIST) s->hist.bound[(size_t)chain] = 0ull;
     }
-    ho.on[(size_t)chain] = in[0] != 0.0 ? 1u : 0u;
-    HIP_TRY(copy_on(s, ho.on_dev, ho.on.data(), sizeof(uint32_t) * ho.on.size(), hipMemcpyHostToDevice));
-    uint32_t any = 0u;
-    for (uint32_t o : ho.on) any |= o;
-    if (any != ho.any) destroy_graph(s);
-    ho.any = any;
-    return OCC_OK;
+    return switch_set(s, r, chain, val != 0);
 }
+
 
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len)
 {
@@ -3893,17 +3717,11 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
         const int mrc = get_moran_state(s, chain, moran_field(nm), v);
         return mrc ? mrc : give_state(s, v, out, cap, len);
     }
-    if (hist_field(nm) != HIST_NONE) {
-        const int hrc = get_hist_state(s, chain, hist_field(nm), v);
-        return hrc ? hrc : give_state(s, v, out, cap, len);
-    }
-    if (conv_field(nm) != CONV_NONE) {
-        const int crc = get_conv_state(s, chain, conv_field(nm), v);
-        return crc ? crc : give_state(s, v, out, cap, len);
-    }
-    if (holdout_field(nm) != HOLD_NONE) {
-        const int orc = get_holdout_state(s, chain, holdout_field(nm), v);
-        return orc ? orc : give_state(s, v, out, cap, len);
+    int acc_field = ACC_NONE;
+    const int acc_kind = accum_lookup(name, &acc_field);
+    if (acc_kind >= 0) {
+        const int arc = get_accum_state(s, chain, acc_kind, acc_field, v);
+        return arc ? arc : give_state(s, v, out, cap, len);
     }
     int sums_kind = SUMS_SITE;
     const int site_q = site_field(nm, &sums_kind);
@@ -3973,9 +3791,9 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     if (region_field(nm) != REGION_NONE) return set_region_state(s, chain, region_field(nm), in, len);
     if (ppc_field(nm) != PPC_NONE) return set_ppc_state(s, chain, ppc_field(nm), in, len);
     if (moran_field(nm) != MORAN_NONE) return set_moran_state(s, chain, moran_field(nm), in, len);
-    if (hist_field(nm) != HIST_NONE) return set_hist_state(s, chain, hist_field(nm), in, len);
-    if (conv_field(nm) != CONV_NONE) return set_conv_state(s, chain, conv_field(nm), in, len);
-    if (holdout_field(nm) != HOLD_NONE) return set_holdout_state(s, chain, holdout_field(nm), in, len);
+    int acc_field = ACC_NONE;
+    const int acc_kind = accum_lookup(name, &acc_field);
+    if (acc_kind >= 0) return set_accum_state(s, chain, acc_kind, acc_field, in, len);
     int sums_kind = SUMS_SITE;
     const int sums_q = site_field(nm, &sums_kind);
     if (sums_q != SITE_NONE) return set_site_state(s, chain, sums_kind, sums_q, in, len);

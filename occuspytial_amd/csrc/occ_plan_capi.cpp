@@ -1,10 +1,11 @@
-// occ_plan_capi.cpp -- the planner, the launch order and the z update's outputs (occ_plan.hpp) and the problem layout
-// (occ_layout.hpp) behind C entry points for tests/test_plan_cpu.py, tests/test_order_cpu.py, tests/test_outputs_cpu.py and
-// tests/test_layout_cpu.py (ctypes).  Test infrastructure:
+// occ_plan_capi.cpp -- the planner, the launch order and the z update's outputs (occ_plan.hpp), the accumulators behind the z
+// update (occ_accum.hpp) and the problem layout (occ_layout.hpp) behind C entry points for tests/test_plan_cpu.py,
+// tests/test_order_cpu.py, tests/test_outputs_cpu.py, tests/test_accum_cpu.py and tests/test_layout_cpu.py (ctypes).  Test infrastructure:
 // `make plan` builds it with g++ into build/; it is never linked into libocc_gibbs.so.
 #include <cstdio>
 #include <cstring>
 
+#include "occ_accum.hpp"
 #include "occ_layout.hpp"
 
 using namespace occ;
@@ -86,6 +87,28 @@ uint32_t occ_output_row(int32_t k, int32_t *level, const char **sw, int32_t *pro
     return OUTPUTS[k].bit;
 }
 int32_t occ_output_level(uint32_t on) { return output_level(on); }
+
+// The accumulators behind the z update (occ_accum.hpp: ACCUM): how many; row k's words -- what messages call it, its four
+// state names by field (null: none), its four refusals -- and numbers {elem, slots, cnt_slot}, {on_min, on_max}; then its
+// functions as they are.
+int32_t occ_accum_count(void) { return N_ACCUM; }
+void occ_accum_row(int32_t k, const char **what, const char *name[4], const char *refusal[4], int32_t num[3], double range[2])
+{
+    const Accum &a = ACCUM[k];
+    *what = a.what;
+    for (int f = 0; f < 4; ++f) name[f] = a.name[f];
+    refusal[0] = a.not_ready; refusal[1] = a.bad_switch; refusal[2] = a.bad_count; refusal[3] = a.bad_data;
+    num[0] = a.elem; num[1] = a.slots; num[2] = a.cnt_slot;
+    range[0] = a.on_min; range[1] = a.on_max;
+}
+int64_t occ_accum_words(int32_t k, int64_t C, int64_t unit) { return (int64_t)accum_words(ACCUM[k], (size_t)C, (size_t)unit); }
+int64_t occ_accum_offset(int64_t C, int64_t unit, int64_t slot, int64_t chain) { return (int64_t)accum_offset((size_t)C, (size_t)unit, (size_t)slot, (size_t)chain); }
+int32_t occ_accum_lookup(const char *name, int32_t *field) { return accum_lookup(name, field); }
+int32_t occ_accum_switch_ok(int32_t k, double v) { return accum_switch_ok(ACCUM[k], v); }
+const char *occ_accum_write_refusal(int32_t k, int32_t field, const double *in, int64_t len, int64_t unit)
+{
+    return accum_write_refusal(ACCUM[k], field, in, (size_t)len, (size_t)unit);
+}
 
 // The layout of a logit problem, by build_layout's steps in its order (occ_gibbs.hip), plus the probit model's row_t.
 // A handle for occ_layout_array / occ_layout_peer, or null with the refusal in err.

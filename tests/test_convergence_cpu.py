@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+from ._launch_text import assert_launched_only_while_on, unit_text
 from .conftest import ROOT, load_golden
 from .test_api_cpu import _inputs
 from .test_cpu_abi import cpu_abi  # noqa: F401  (the oracle's build of the C ABI, which does not know the conv_* names)
@@ -84,18 +85,14 @@ def test_every_conv_state_name_is_in_header_and_binding():
 
 def test_the_kernel_is_launched_only_while_a_switch_is_on():
     """Read off launch_kind: the one call of conv_launch stands behind `if (s->conv.any)`, next to hist_launch in the branch of
-    the z update; the word starts at 0, only set_conv_state raises it, and occ_profile clears it for its scope.  A run with
-    the switch never touched enqueues what it enqueued before.  The unit has one kernel, no atomics and no LDS."""
-    src = open(os.path.join(ROOT, 'occuspytial_amd', 'csrc', 'occ_gibbs.hip')).read()
-    assert len(re.findall(r'\bconv_launch\(', src)) == 1
-    assert re.search(r'hist_launch\(s->hist\.args[^\n]*\n\s*if \(s->conv\.any\)[^\n]*\n\s*conv_launch\(s->conv\.args, s->ctx\.sc, c\.C, e, st\);', src)
-    assert re.search(r'struct Conv \{[^}]*uint32_t any = 0u;', src)
-    assert re.findall(r'(?:cv|conv)\.any = ([^;]+);', src) == ['any']
-    assert re.search(r'Scoped<uint32_t> no_conv\(&s->conv\.any, 0u\);', src)
-    unit = open(os.path.join(ROOT, 'occuspytial_amd', 'csrc', 'occ_conv.hip')).read()
+    the z update; the word starts at 0, only switch_set raises it -- the one place that does, for every feature behind the z
+    update -- and occ_profile clears it for its scope.  A run with the switch never touched enqueues what it enqueued before.
+    The unit has one kernel, no atomics and no LDS."""
+    assert_launched_only_while_on('conv')
+    unit = unit_text('occ_conv.hip')
     assert 'atomic' not in unit.lower() and '__shared__' not in unit and len(re.findall(r'__global__', unit)) == 1
     assert re.search(r'return a\.on\[chain\] != 0u && a\.sums != nullptr && after == t \+ 1u && sc\.err == 0 && rel >= sc\.burnin;', unit)
-    hist = open(os.path.join(ROOT, 'occuspytial_amd', 'csrc', 'occ_hist.hip')).read()
+    hist = unit_text('occ_hist.hip')
     assert re.search(r'return a\.on\[chain\] != 0u && a\.cnt != nullptr && after == t \+ 1u && sc\.err == 0 && rel >= sc\.burnin;', hist)
 
 

@@ -480,6 +480,42 @@ def test_a_call_rerun_after_a_broken_handover_counts_no_iteration_twice(monkeypa
     _same(ref, alt)
 
 
+def _everything_on_rsr():
+    """The reduced-rank workload with every accumulator behind the z update and both kinds of per-site sums on, run (8, 0) then
+    (5, 1): per chain the histograms, the batch-means sums, the held-out sums and the site sums, each with its count."""
+    eng = _engine(*WORKLOADS['rsr40'](2), site=True, ll=True, bins=64, conv=4)
+    eng.run(8, 0)
+    eng.run(5, 1)
+    out = [dict(hist=eng.hist_counts(c), conv=eng.conv_sums(c), holdout=eng.holdout_sums(c), site=eng.site_sums(c), ll=eng.loglik_sums(c))
+           for c in range(eng.n_chains)], eng.stats()
+    eng.close()
+    return out
+
+
+def test_a_rerun_call_restores_every_accumulator_from_one_snapshot_loop(monkeypatch):
+    """All three accumulators and both kinds of per-site sums are on while a call is re-run after a broken hand-over: the
+    snapshot holds uint32 histograms beside float64 sums, each in a buffer of its own, and every array comes back as the
+    undisturbed run has it, bit for bit.  An element size or an address taken from the wrong kind would show here."""
+    monkeypatch.setenv('OCC_QUIET', '1')
+    ref, st = _everything_on_rsr()
+    assert st['fused_fallbacks'] == 0
+    monkeypatch.setenv('OCC_DEBUG_BREAK_HANDOVER', '1')
+    alt, st = _everything_on_rsr()
+    assert st['fused_fallbacks'] == 1
+    assert len(ref) == len(alt) == 2
+    for c, (u, v) in enumerate(zip(ref, alt)):
+        assert u['hist']['counts'].dtype == np.uint32 and u['hist']['counts'].shape == (64, 720) and u['conv']['sums'].shape == (11, 720)
+        assert u['holdout']['sums'].shape == (5, 180)
+        for kind, data in (('hist', 'counts'), ('conv', 'sums'), ('holdout', 'sums')):
+            assert u[kind]['count'] == v[kind]['count'] == 12, (c, kind)
+            assert np.array_equal(u[kind][data], v[kind][data]), (c, kind, np.count_nonzero(u[kind][data] != v[kind][data]))
+        assert np.all(u['hist']['counts'].sum(axis=0) == 12) and np.all(u['conv']['sums'][0] == 12) and np.all(u['holdout']['sums'][CNT] == 12)
+        for kind in ('site', 'll'):
+            assert u[kind]['count'] == v[kind]['count'] == 12 and sorted(u[kind]) == sorted(v[kind]), (c, kind)
+            for name in u[kind]:
+                assert np.array_equal(u[kind][name], v[kind][name]), (c, kind, name)
+
+
 # ------------------------------------------------------------------ 5: nothing else sees the switch
 @pytest.mark.parametrize('name', ['queen30x40', 'generic', 'rsr40'])
 def test_nothing_else_sees_the_switch(name):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 from scipy.special import logsumexp
 
+from ._launch_text import assert_launched_only_while_on, unit_text
 from .conftest import ROOT, load_golden
 from .test_api_cpu import _inputs
 from .test_cpu_abi import cpu_abi  # noqa: F401  (the oracle's build of the C ABI, which does not know the holdout_* names)
@@ -69,19 +70,14 @@ def test_every_holdout_state_name_is_in_header_and_binding():
 
 def test_the_kernel_is_launched_only_while_a_switch_is_on():
     """Read off launch_kind: the one call of holdout_launch stands behind `if (s->holdout.any)`, next to conv_launch in the
-    branch of the z update; the word starts at 0, only set_holdout_state raises it, and occ_profile clears it for its scope.  A
-    run with the switch never touched enqueues what it enqueued before.  The unit has one kernel, no atomics and no LDS, and
-    its guard is written as conv_counts_now writes it."""
-    src = open(os.path.join(ROOT, 'occuspytial_amd', 'csrc', 'occ_gibbs.hip')).read()
-    assert len(re.findall(r'\bholdout_launch\(', src)) == 1
-    assert re.search(r'conv_launch\(s->conv\.args[^\n]*\n\s*if \(s->holdout\.any\)[^\n]*\n\s*holdout_launch\(s->holdout\.args, s->ctx\.sc, c\.C, e, st\);', src)
-    assert re.search(r'struct Holdout \{[^}]*uint32_t any = 0u;', src)
-    assert re.findall(r'(?:ho|holdout)\.any = ([^;]+);', src) == ['any']
-    assert re.search(r'Scoped<uint32_t> no_holdout\(&s->holdout\.any, 0u\);', src)
-    unit = open(os.path.join(ROOT, 'occuspytial_amd', 'csrc', 'occ_holdout.hip')).read()
+    branch of the z update; the word starts at 0, only switch_set raises it -- the one place that does, for every feature
+    behind the z update -- and occ_profile clears it for its scope.  A run with the switch never touched enqueues what it
+    enqueued before.  The unit has one kernel, no atomics and no LDS, and its guard is written as conv_counts_now writes it."""
+    assert_launched_only_while_on('holdout')
+    unit = unit_text('occ_holdout.hip')
     assert 'atomic' not in unit.lower() and '__shared__' not in unit and len(re.findall(r'__global__', unit)) == 1
     guard = r'return a\.on\[chain\] != 0u && a\.sums != nullptr && after == t \+ 1u && sc\.err == 0 && rel >= sc\.burnin;'
-    assert re.search(guard, unit) and re.search(guard, open(os.path.join(ROOT, 'occuspytial_amd', 'csrc', 'occ_conv.hip')).read())
+    assert re.search(guard, unit) and re.search(guard, unit_text('occ_conv.hip'))
 
 
 # ---- HoldoutScore, compare, combine ---------------------------------------------------------------------------------

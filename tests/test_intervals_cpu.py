@@ -11,6 +11,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from ._launch_text import assert_launched_only_while_on, unit_text
 from .conftest import ROOT, load_golden
 from .test_api_cpu import _inputs
 from .test_cpu_abi import cpu_abi  # noqa: F401  (the oracle's build of the C ABI, which does not know the hist_* names)
@@ -42,15 +43,11 @@ def test_every_hist_state_name_is_in_header_and_binding():
 
 def test_the_kernel_is_launched_only_while_a_switch_is_on():
     """occ_get_stats counts no launches per kernel, so this is read off launch_kind: the one call of hist_launch stands behind
-    `if (s->hist.any)`, next to sp_launch in the branch of the z update; the word starts at 0, only set_hist_state raises it,
-    and occ_profile clears it for its scope.  A run with the switch never touched enqueues what it enqueued before."""
-    src = open(os.path.join(ROOT, 'occuspytial_amd', 'csrc', 'occ_gibbs.hip')).read()
-    assert len(re.findall(r'\bhist_launch\(', src)) == 1
-    assert re.search(r'sp_launch\(s->spatial\.args[^\n]*\n\s*if \(s->hist\.any\)[^\n]*\n\s*hist_launch\(s->hist\.args, s->ctx\.sc, c\.C, e, st\);', src)
-    assert re.search(r'struct Hist \{[^}]*uint32_t any = 0u;', src)
-    assert re.findall(r'(?:hs|hist)\.any = ([^;]+);', src) == ['any']
-    assert re.search(r'Scoped<uint32_t> no_hist\(&s->hist\.any, 0u\);', src)
-    unit = open(os.path.join(ROOT, 'occuspytial_amd', 'csrc', 'occ_hist.hip')).read()
+    `if (s->hist.any)`, next to sp_launch in the branch of the z update; the word starts at 0, only switch_set raises it -- the
+    one place that does, for every feature behind the z update -- and occ_profile clears it for its scope.  A run with the
+    switch never touched enqueues what it enqueued before."""
+    assert_launched_only_while_on('hist')
+    unit = unit_text('occ_hist.hip')
     assert 'atomic' not in unit.lower() and '__shared__' not in unit and len(re.findall(r'__global__', unit)) == 1
 
 
