@@ -27,7 +27,7 @@ extern "C" {
 #endif
 
 #define OCC_BASIS_VERSION 1
-#define OCC_BASIS_MAX_P 8 /* columns of X */
+#define OCC_BASIS_MAX_P 32 /* columns of X (up to 8: the projection kernels with 8 register sums; more: with 32) */
 
 enum {
     OCC_BASIS_OK = 0,

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, 'libocc_basis.so')
 
 VERSION = 1  # OCC_BASIS_VERSION of include/occ_basis.h this binding was written against
 OK, E_BADARG, E_HIP = 0, -1, -2
-MAX_P = 8
+MAX_P = 32
 
 _dp = C.c_void_p
 # every symbol include/occ_basis.h declares: (name, restype, argtypes)

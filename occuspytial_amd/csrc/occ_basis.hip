@@ -37,50 +37,54 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 
 constexpr int TS = 256;        // sites per tile of the column reductions (X'V, residual norms)
 constexpr int MAXP = OCC_BASIS_MAX_P;
+constexpr int FASTP = 8;       // columns of X the MP = 8 instantiations of the projection kernels hold; more (to MAXP): MP = MAXP
 constexpr int GRAM_WAVES = 16; // waves per workgroup of k_basis_gram
 constexpr int ROT_NJ = 4;      // 16-column tiles of the result one wave of k_basis_rotate holds
 
-// part[(tile * MAXP + a) * ld + c] = sum over the tile's sites i of X[i][a] src[i][c], sites in order
+// part[(tile * MP + a) * ld + c] = sum over the tile's sites i of X[i][a] src[i][c], sites in order.  MP: the columns of X the
+// kernel's register sums hold (FASTP, or MAXP for p > FASTP); the loops over them are unrolled, no array is indexed at run time.
+template <int MP>
 __global__ void __launch_bounds__(256) k_basis_xt(const double *__restrict__ src, const double *__restrict__ X, double *__restrict__ part, int n, int p,
                                                   int ld, int bc)
 {
     const int c = (int)blockIdx.y * 256 + (int)threadIdx.x;
     if (c >= bc) return;
     const int i0 = (int)blockIdx.x * TS, i1 = min(n, i0 + TS);
-    double acc[MAXP];
+    double acc[MP];
 #pragma unroll
-    for (int a = 0; a < MAXP; ++a) acc[a] = 0.0;
+    for (int a = 0; a < MP; ++a) acc[a] = 0.0;
     for (int i = i0; i < i1; ++i) {
         const double v = src[(size_t)i * ld + c];
 #pragma unroll
-        for (int a = 0; a < MAXP; ++a)
+        for (int a = 0; a < MP; ++a)
             if (a < p) acc[a] = fma(X[(size_t)i * p + a], v, acc[a]);
     }
 #pragma unroll
-    for (int a = 0; a < MAXP; ++a)
-        if (a < p) part[((size_t)blockIdx.x * MAXP + a) * ld + c] = acc[a];
+    for (int a = 0; a < MP; ++a)
+        if (a < p) part[((size_t)blockIdx.x * MP + a) * ld + c] = acc[a];
 }
 
 // D[a][c] = sum_a' Xi[a][a'] C[a'][c],  C[a'][c] = the tiles' partial sums in tile order
+template <int MP>
 __global__ void __launch_bounds__(256) k_basis_xt_solve(const double *__restrict__ part, const double *__restrict__ Xi, double *__restrict__ D, int ntile,
                                                         int p, int ld, int bc)
 {
     const int c = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (c >= bc) return;
-    double C[MAXP];
+    double C[MP];
 #pragma unroll
-    for (int a = 0; a < MAXP; ++a) C[a] = 0.0;
+    for (int a = 0; a < MP; ++a) C[a] = 0.0;
     for (int t = 0; t < ntile; ++t) {
 #pragma unroll
-        for (int a = 0; a < MAXP; ++a)
-            if (a < p) C[a] += part[((size_t)t * MAXP + a) * ld + c];
+        for (int a = 0; a < MP; ++a)
+            if (a < p) C[a] += part[((size_t)t * MP + a) * ld + c];
     }
 #pragma unroll
-    for (int a = 0; a < MAXP; ++a) {
+    for (int a = 0; a < MP; ++a) {
         if (a >= p) continue;
         double d = 0.0;
 #pragma unroll
-        for (int a2 = 0; a2 < MAXP; ++a2)
+        for (int a2 = 0; a2 < MP; ++a2)
             if (a2 < p) d = fma(Xi[a * p + a2], C[a2], d);
         D[(size_t)a * ld + c] = d;
     }
@@ -121,15 +125,16 @@ __global__ void __launch_bounds__(256) k_basis_spmm(const double *__restrict__ s
 }
 
 // out = alpha (in - X D) + beta y1 + gamma y0  (y1 / y0 are read only where beta / gamma is not zero; in may be out)
+template <int MP>
 __global__ void __launch_bounds__(256) k_basis_combine(const double *in, double *out, const double *__restrict__ X, const double *__restrict__ D,
                                                        const double *__restrict__ y1, const double *__restrict__ y0, double alpha, double beta,
                                                        double gamma, int n, int p, int ld, int bc)
 {
     const int c = (int)blockIdx.y * 64 + ((int)threadIdx.x & 63);
     if (c >= bc) return;
-    double d[MAXP];
+    double d[MP];
 #pragma unroll
-    for (int a = 0; a < MAXP; ++a) d[a] = a < p ? D[(size_t)a * ld + c] : 0.0;
+    for (int a = 0; a < MP; ++a) d[a] = a < p ? D[(size_t)a * ld + c] : 0.0;
     const int i0 = (int)blockIdx.x * 64 + ((int)threadIdx.x >> 6);
     for (int r = 0; r < 16; ++r) {
         const int i = i0 + 4 * r;
@@ -137,7 +142,7 @@ __global__ void __launch_bounds__(256) k_basis_combine(const double *in, double 
         const size_t at = (size_t)i * ld + c;
         double v = in[at];
 #pragma unroll
-        for (int a = 0; a < MAXP; ++a)
+        for (int a = 0; a < MP; ++a)
             if (a < p) v = fma(-X[(size_t)i * p + a], d[a], v);
         v *= alpha;
         if (beta != 0.0) v = fma(beta, y1[at], v);
@@ -362,8 +367,9 @@ static int upload(occ_basis *h, T **dst, const std::vector<T> &src)
 static int launch_xt(occ_basis *h, const double *src)
 {
     const int bc = bc_of(h->b);
-    hipLaunchKernelGGL(k_basis_xt, dim3(h->ntile, (bc + 255) / 256), dim3(256), 0, h->st, src, h->X, h->part, h->n, h->p, h->ld, bc);
-    hipLaunchKernelGGL(k_basis_xt_solve, dim3((bc + 255) / 256), dim3(256), 0, h->st, h->part, h->Xi, h->D, h->ntile, h->p, h->ld, bc);
+    const bool fast = h->p <= FASTP;  // (the two instantiations lay `part` out by their own MP: written and read by the same one)
+    hipLaunchKernelGGL(fast ? k_basis_xt<FASTP> : k_basis_xt<MAXP>, dim3(h->ntile, (bc + 255) / 256), dim3(256), 0, h->st, src, h->X, h->part, h->n, h->p, h->ld, bc);
+    hipLaunchKernelGGL(fast ? k_basis_xt_solve<FASTP> : k_basis_xt_solve<MAXP>, dim3((bc + 255) / 256), dim3(256), 0, h->st, h->part, h->Xi, h->D, h->ntile, h->p, h->ld, bc);
     return OCC_BASIS_OK;
 }
 
@@ -375,7 +381,7 @@ static int launch_apply(occ_basis *h, const double *src, double *out, double alp
     hipLaunchKernelGGL(k_basis_spmm, dim3(h->nslice, (bc + 63) / 64), dim3(256), 0, h->st, src, out, h->sell_ptr, h->sell_col, h->sell_val, h->ell_w,
                        h->AX, h->D, h->n, h->p, h->ld, bc);
     launch_xt(h, out);
-    hipLaunchKernelGGL(k_basis_combine, dim3(h->nslice, (bc + 63) / 64), dim3(256), 0, h->st, (const double *)out, out, h->X, h->D, y1, y0,
+    hipLaunchKernelGGL(h->p <= FASTP ? k_basis_combine<FASTP> : k_basis_combine<MAXP>, dim3(h->nslice, (bc + 63) / 64), dim3(256), 0, h->st, (const double *)out, out, h->X, h->D, y1, y0,
                        alpha * h->s, beta, gamma, h->n, h->p, h->ld, bc);
     BH_TRY(hipGetLastError());
     return OCC_BASIS_OK;
@@ -414,7 +420,7 @@ static int create_impl(occ_basis *h, int64_t n64, const int32_t *indptr, const i
                        const double *XtX_inv, int32_t b_max, int32_t device)
 {
     BH_ARG(n64 >= 1 && n64 < (int64_t)1 << 30, "n must lie in [1, 2^30)");
-    BH_ARG(p >= 1 && p <= MAXP, "p must lie in [1, 8]");
+    BH_ARG(p >= 1 && p <= MAXP, "p must lie in [1, 32]");
     BH_ARG(b_max >= 1 && b_max <= 16384, "b_max must lie in [1, 16384]");
     BH_ARG(indptr && indices && qdata && X && XtX_inv, "null input");
     const int n = (int)n64;
@@ -479,8 +485,9 @@ static int create_impl(occ_basis *h, int64_t n64, const int32_t *indptr, const i
         BH_TRY(hipMalloc((void **)&h->blk[k], blk_bytes));
         BH_TRY(hipMemsetAsync(h->blk[k], 0, blk_bytes, h->st));
     }
-    BH_TRY(hipMalloc((void **)&h->part, (size_t)h->ntile * MAXP * ld * sizeof(double)));
-    BH_TRY(hipMalloc((void **)&h->D, (size_t)MAXP * ld * sizeof(double)));
+    const size_t mp = p <= FASTP ? FASTP : MAXP;  // (the rows the instantiation in use lays `part` and D out by: launch_xt)
+    BH_TRY(hipMalloc((void **)&h->part, (size_t)h->ntile * mp * ld * sizeof(double)));
+    BH_TRY(hipMalloc((void **)&h->D, mp * ld * sizeof(double)));
     BH_TRY(hipMalloc((void **)&h->Y, ld * ld * sizeof(double)));
     BH_TRY(hipMalloc((void **)&h->G, ld * ld * sizeof(double)));
     BH_TRY(hipMalloc((void **)&h->lam, ld * sizeof(double)));
@@ -571,7 +578,7 @@ int occ_basis_project(occ_basis *h)
     const int bc = bc_of(h->b);
     double *v = blk(h, 0);
     launch_xt(h, v);
-    hipLaunchKernelGGL(k_basis_combine, dim3(h->nslice, (bc + 63) / 64), dim3(256), 0, h->st, (const double *)v, v, h->X, h->D, (const double *)nullptr,
+    hipLaunchKernelGGL(h->p <= FASTP ? k_basis_combine<FASTP> : k_basis_combine<MAXP>, dim3(h->nslice, (bc + 63) / 64), dim3(256), 0, h->st, (const double *)v, v, h->X, h->D, (const double *)nullptr,
                        (const double *)nullptr, 1.0, 0.0, 0.0, h->n, h->p, h->ld, bc);
     BH_TRY(hipGetLastError());
     h->w_valid = false;
