@@ -44,20 +44,10 @@ class SumsKind(NamedTuple):
     """One kind of per-site running sums the engine keeps on the device (``SUMS`` of csrc/occ_gibbs.hip), as Python sees it."""
     fields: tuple       # its state names: switch, count, sums (a sum's short name drops the kind's prefix, 'site_' / 'll_')
     what: str           # what messages call it
-    option: str         # the keyword of ``sample`` / ``resume`` that asks for it
-    result: str         # the attribute of their result that holds what is made of the sums
-    python_step: str    # why a sampler that steps in Python refuses it (after the class's name)
-    probit: str         # why the probit sampler refuses it
 
 
-SUMS_KINDS = {
-    'site': SumsKind(SITE_FIELDS, 'site summaries', 'site_summaries', 'sites',
-                     'steps in Python: site summaries are accumulated by the device engine only',
-                     'site summaries are not available for the probit model'),
-    'll': SumsKind(LOGLIK_FIELDS, 'log-likelihood sums', 'waic', 'waic',
-                   'steps in Python: the log-likelihood sums of WAIC are accumulated by the device engine only',
-                   'WAIC is not available for the probit model'),
-}
+# (what the samplers make of a kind -- keyword, result, refusals -- is its row of gibbs/options.py)
+SUMS_KINDS = {'site': SumsKind(SITE_FIELDS, 'site summaries'), 'll': SumsKind(LOGLIK_FIELDS, 'log-likelihood sums')}
 
 
 class AccumKind(NamedTuple):

@@ -9,18 +9,12 @@ chains to the HIP engine in one batch instead of forking one process per chain
 import numpy as np
 from scipy.sparse import csc_matrix, isspmatrix_csc
 
-from .. import _lib
 from .._problem import FlatProblem, default_start
 from ..chain import Chain
-from ..convergence import diagnostics_batch
 from ..data import Data
-from ..holdout import holdout_arg
-from ..intervals import interval_bins
 from ..posterior import PosteriorParameter
-from ..ppc import ppc_flag
-from ..regions import region_ids
-from ..spatial import spatial_flag
 from ..utils import get_generator
+from . import options
 from .parallel import sample_parallel
 from .state import FixedState, State
 
@@ -168,104 +162,24 @@ class GibbsBase:
         score and AUC of the predicted detections; ``None`` otherwise).  :func:`occuspytial_amd.holdout.split` makes the
         folds of a K-fold run and :func:`occuspytial_amd.holdout.combine` joins their scores.
         """
-        bins = interval_bins(site_intervals)
-        batch = diagnostics_batch(site_diagnostics, size - burnin)
+        given = dict(locals())
+        first = options.parse_first(given, self._problem, size - burnin)
         if burnin >= size:
             raise ValueError('burnin value cannot be larger than sample size')
         if chains < 1:
             raise ValueError('chains must a positive integer.')
-        kinds = self._sums_asked(site_summaries=site_summaries, waic=waic)
-        for kind in kinds:
-            self._refuse_sums(kind)
-        extra = {_lib.SUMS_KINDS[kind].option: True for kind in kinds}   # (with the defaults, no keyword about them goes on)
-        ids = region_ids(regions, self._problem.n)
-        if ids is not None:
-            self._refuse_regions()
-            extra['regions'] = ids
-        if ppc_flag(ppc):
-            self._refuse_ppc()
-            extra['ppc'] = True
-        if spatial_flag(spatial_check):
-            self._refuse_spatial_check()
-            extra['spatial_check'] = True
-        if bins:
-            self._refuse_site_intervals()
-            extra['site_intervals'] = bins
-        if batch:
-            self._refuse_site_diagnostics()
-            extra['site_diagnostics'] = batch
-        if holdout is not None:
-            self._refuse_holdout()
-            extra['holdout'] = holdout_arg(holdout, self._problem)
-        samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start,
-                                  progressbar=progressbar, **extra)
+        asked = options.ask(self, given, size - burnin, first)
+        extra = {'asked': asked} if asked else {}   # (with the defaults, no keyword about them goes on)
+        samples = sample_parallel(self, size=size, burnin=burnin, chains=chains, start=start, progressbar=progressbar, **extra)
         out = PosteriorParameter(*samples)
-        for kind in kinds:
-            result = _lib.SUMS_KINDS[kind].result
-            setattr(out, result, self.__dict__.pop('_' + result))
-        if ids is not None:
-            out.regions = self._region_result(ids, out)
-        if 'ppc' in extra:
-            out.ppc = self.__dict__.pop('_ppc')
-        if 'spatial_check' in extra:
-            out.spatial_check = self.__dict__.pop('_spatial_check')
-        if 'site_intervals' in extra:
-            out.site_intervals = self.__dict__.pop('_site_intervals')
-        if 'site_diagnostics' in extra:
-            out.site_diagnostics = self.__dict__.pop('_site_diagnostics')
-        if 'holdout' in extra:
-            out.holdout = self.__dict__.pop('_holdout')
+        for result, value in self.__dict__.pop('_outputs', {}).items():   # (what _run_chains made of the options asked)
+            setattr(out, result, value)
         return out
 
-    def _refuse_ppc(self):
-        """The detections are replicated by the engine's z update: a sampler with a Python ``step`` has none."""
-        if not hasattr(self, '_run_chains'):
-            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: posterior predictive checks are formed by '
-                                      'the device engine only')
-
-    def _refuse_spatial_check(self):
-        """The residuals' sums are formed on the device behind the engine's z update: a sampler with a Python ``step`` has none."""
-        if not hasattr(self, '_run_chains'):
-            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: the spatial residual check is formed by '
-                                      'the device engine only')
-
-    def _refuse_site_intervals(self):
-        """The histograms are kept on the device behind the engine's z update: a sampler with a Python ``step`` has none."""
-        if not hasattr(self, '_run_chains'):
-            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: site intervals are accumulated by the '
-                                      'device engine only')
-
-    def _refuse_site_diagnostics(self):
-        """The batch-means sums are kept on the device behind the engine's z update: a sampler with a Python ``step`` has none."""
-        if not hasattr(self, '_run_chains'):
-            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: site diagnostics are accumulated by the '
-                                      'device engine only')
-
-    def _refuse_holdout(self):
-        """The held-out sums are kept on the device behind the engine's z update: a sampler with a Python ``step`` has none."""
-        if not hasattr(self, '_run_chains'):
-            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: held-out scoring is accumulated by the '
-                                      'device engine only')
-
-    def _refuse_regions(self):
-        """The occupied sites per region are counted by the engine's z update: a sampler with a Python ``step`` has none."""
-        if not hasattr(self, '_run_chains'):
-            raise NotImplementedError(f'{self.__class__.__name__} steps in Python: the occupied sites per region are counted by '
-                                      'the device engine only')
-
-    def _region_result(self, ids, post):
-        from ..regions import RegionOccupancy
-        return RegionOccupancy(ids, self._problem.obs, post['occupied'])
-
-    @staticmethod
-    def _sums_asked(**options):
-        """The kinds of per-site sums (``_lib.SUMS_KINDS``) whose keyword is set."""
-        return [kind for kind, k in _lib.SUMS_KINDS.items() if options[k.option]]
-
-    def _refuse_sums(self, kind):
-        """Per-site sums of either kind are accumulated by the engine's z update: a sampler with a Python ``step`` has none."""
-        if not hasattr(self, '_run_chains'):
-            raise NotImplementedError(f'{self.__class__.__name__} {_lib.SUMS_KINDS[kind].python_step}')
+    def _refusal(self, option):
+        """Why this sampler refuses an optional output (a row of ``options.OPTIONS``), or None.  Every one of them is formed on
+        the device behind the engine's z update: a sampler with a Python ``step`` has none."""
+        return None if hasattr(self, '_run_chains') else f'{self.__class__.__name__} {option.python_step}'
 
     def copy(self):
         """A shallow copy with its own generator spawned from this one's seed sequence

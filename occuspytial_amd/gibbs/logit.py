@@ -1,20 +1,11 @@
 """``LogitICARGibbs`` on the MI355X engine (API of reference ``occuspytial/gibbs/logit.py:102-266``)."""
 import numpy as np
 
-from .. import _lib
 from .._engine import Engine, EngineGroup
 from ..chain import Chain
-from ..convergence import SiteDiagnostics, diagnostics_batch
-from ..holdout import HoldoutScore, holdout_arg
-from ..intervals import SiteIntervals, interval_bins
-from ..ppc import PredictiveCheck, ppc_flag
-from ..regions import region_ids
-from ..sites import SiteSummary
-from ..spatial import SpatialCheck, spatial_flag
-from ..waic import WAIC
+from . import options
 from .base import GibbsBase
-
-SUMS_RESULT = {'site': SiteSummary, 'll': WAIC}   # kind of per-site sums (_lib.SUMS_KINDS) -> what a result holds of them
+from .options import OPTIONS
 
 
 def _philox_key(rng):
@@ -132,48 +123,6 @@ class LogitICARGibbs(GibbsBase):
             np.savez(path, **ckpt)
         return ckpt
 
-    def _sums_switch(self, eng, kind, on):
-        try:
-            eng.sums_switch(kind, on)
-        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
-            raise ValueError(f'the loaded engine library has no {_lib.SUMS_KINDS[kind].what} ({exc}): rebuild it') from None
-
-    def _regions_call(self, call):
-        try:
-            return call()
-        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
-            raise ValueError(f'the loaded engine library does not count the occupied sites per region ({exc}): rebuild it') from None
-
-    def _ppc_switch(self, eng, on):
-        try:
-            eng.ppc_stats(on)
-        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
-            raise ValueError(f'the loaded engine library has no posterior predictive check ({exc}): rebuild it') from None
-
-    def _moran_switch(self, eng, on):
-        try:
-            eng.moran_stats(on)
-        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
-            raise ValueError(f'the loaded engine library has no spatial residual check ({exc}): rebuild it') from None
-
-    def _hist_switch(self, eng, bins):
-        try:
-            eng.hist_stats(bins)
-        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
-            raise ValueError(f'the loaded engine library has no site intervals ({exc}): rebuild it') from None
-
-    def _conv_switch(self, eng, batch):
-        try:
-            eng.conv_stats(batch)
-        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
-            raise ValueError(f'the loaded engine library has no site diagnostics ({exc}): rebuild it') from None
-
-    def _holdout_call(self, call):
-        try:
-            return call()
-        except ValueError as exc:   # a stale build, or a stand-in library that does not know the state names
-            raise ValueError(f'the loaded engine library has no held-out scoring ({exc}): rebuild it') from None
-
     def resume(self, checkpoint, size, progressbar=True, site_summaries=False, waic=False, regions=None, ppc=False,
                spatial_check=False, site_intervals=False, site_diagnostics=False, holdout=None):
         """Continue the chains of ``checkpoint`` (a dict from :meth:`checkpoint` or the path of its ``.npz``)
@@ -194,68 +143,23 @@ class LogitICARGibbs(GibbsBase):
         ``floor(sqrt(size))``); ``out.site_diagnostics`` covers every iteration accumulated so far.
         ``holdout`` (as in :meth:`sample`): the held-out sums go on from those the checkpoint holds if it holds them for
         the same withheld data (from zero otherwise); ``out.holdout`` covers every iteration accumulated so far."""
+        given = dict(locals())
         from ..posterior import PosteriorParameter
         from tqdm.auto import tqdm
-        bins = interval_bins(site_intervals)
-        batch = diagnostics_batch(site_diagnostics, size)
+        first = options.parse_first(given, self._problem, size)
         if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, '__fspath__'):
             with np.load(checkpoint) as f:
                 checkpoint = {k: f[k] for k in f.files}
         if size < 1:
             raise ValueError('size must be a positive integer')
-        ids = region_ids(regions, self._problem.n)
-        if ids is not None:
-            self._refuse_regions()
-        ppc = ppc_flag(ppc)
-        if ppc:
-            self._refuse_ppc()
-        spatial_check = spatial_flag(spatial_check)
-        if spatial_check:
-            self._refuse_spatial_check()
-        if bins:
-            self._refuse_site_intervals()
-        if batch:
-            self._refuse_site_diagnostics()
-        if holdout is not None:
-            self._refuse_holdout()
-            holdout = holdout_arg(holdout, self._problem)
+        asked = options.ask(self, given, size, first)
         C = int(checkpoint['n_chains'])
         self.__dict__['_stepping'] = False
         eng = self._get_engine([int(k) for k in np.asarray(checkpoint['keys'])])
         eng.restore(checkpoint)
-        kinds = self._sums_asked(site_summaries=site_summaries, waic=waic)
-        for kind in kinds:
-            self._refuse_sums(kind)
-            if _lib.SUMS_KINDS[kind].fields[0] not in checkpoint:
-                self._sums_switch(eng, kind, True)
-        if ids is not None:
-            self._regions_call(lambda: (eng.regions(ids), eng.region_stats(True)))
-            occupied = np.zeros((C, size, max(int(ids.max()) + 1, 1)))
-        if ppc:
-            self._ppc_switch(eng, True)
-            ppc_rows = np.zeros((C, size, 4))
-        elif getattr(eng, '_ppc_on', False):   # (the checkpoint's switch was on: this call did not ask)
-            eng.ppc_stats(False)
-        if spatial_check:
-            self._moran_switch(eng, True)
-            moran_rows = np.zeros((C, size, 8))
-        elif getattr(eng, '_moran_on', False):   # (the checkpoint's switch was on: this call did not ask)
-            eng.moran_stats(False)
-        if bins:
-            if getattr(eng, '_hist_bins', 0) != bins:   # (the checkpoint holds none, or of another number of bins: from zero)
-                self._hist_switch(eng, bins)
-        elif getattr(eng, '_hist_bins', 0):   # (the checkpoint's switch was on: this call did not ask)
-            eng.hist_stats(0)
-        if batch:
-            if not getattr(eng, '_conv_batch', 0):   # (the checkpoint holds none: from zero; otherwise its batch length stays)
-                self._conv_switch(eng, batch)
-        elif getattr(eng, '_conv_batch', 0):   # (the checkpoint's switch was on: this call did not ask)
-            eng.conv_stats(0)
-        if holdout is not None:
-            if not (getattr(eng, '_holdout_on', False) and np.array_equal(eng._holdout, holdout)):   # (none, or of other data: from zero)
-                self._holdout_call(lambda: (eng.holdout_data(holdout), eng.holdout_stats(True)))
-        elif getattr(eng, '_holdout_on', False):   # (the checkpoint's switch was on: this call did not ask)
-            eng.holdout_stats(False)
+        for o in OPTIONS:   # (each by its own rule: on from the checkpoint's state or from zero, left as restored or switched off)
+            o.resume(eng, asked.get(o.keyword), checkpoint)
+        mine = [(o, asked[o.keyword], o.rows(C, size, asked[o.keyword])) for o in OPTIONS if o.keyword in asked]
         alpha = np.zeros((C, size, self._problem.q))
         beta = np.zeros((C, size, self._problem.p))
         tau = np.zeros((C, size))
@@ -265,66 +169,33 @@ class LogitICARGibbs(GibbsBase):
         while done < size:
             step = min(chunk, size - done)
             alpha[:, done:done + step], beta[:, done:done + step], tau[:, done:done + step] = eng.run(step, 0)
-            if ids is not None:
-                occupied[:, done:done + step] = [eng.region_draws(c) for c in range(C)]
-            if ppc:
-                ppc_rows[:, done:done + step] = [eng.ppc_draws(c) for c in range(C)]
-            if spatial_check:
-                moran_rows[:, done:done + step] = [eng.moran_draws(c) for c in range(C)]
+            for o, _, rows in mine:
+                o.read(eng, rows, done, done + step)
             done += step
             bar.update(step)
         bar.close()
-        extra = {'occupied': occupied} if ids is not None else {}
+        extra = {o.vector: rows for o, _, rows in mine if o.vector}
         chains = [Chain._from_arrays({'alpha': alpha[c], 'beta': beta[c], 'tau': tau[c], **{k: v[c] for k, v in extra.items()}},
                                      vectors=tuple(extra)) for c in range(C)]
         self.chain = chains[0]
         self._pull_state(eng, 0)
         out = PosteriorParameter(*chains)
-        for kind in kinds:
-            setattr(out, _lib.SUMS_KINDS[kind].result, SUMS_RESULT[kind].from_engine(eng))
-        if ids is not None:
-            out.regions = self._region_result(ids, out)
-        if ppc:
-            out.ppc = PredictiveCheck.from_problem(self._problem, ppc_rows)
-        if spatial_check:
-            out.spatial_check = SpatialCheck.from_problem(self._problem, moran_rows)
-        if bins:
-            out.site_intervals = SiteIntervals.from_engine(eng)
-        if batch:
-            out.site_diagnostics = SiteDiagnostics.from_engine(eng)
-        if holdout is not None:
-            out.holdout = HoldoutScore.from_engine(eng)
+        for o, want, rows in mine:
+            setattr(out, o.result, o.finish(eng, self._problem, want, rows))
         return out
 
     # ------------------------------------------------------------------ batched chains
-    def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, site_summaries=False, waic=False, regions=None,
-                    ppc=False, spatial_check=False, site_intervals=False, site_diagnostics=False, holdout=None):
+    def _run_chains(self, samplers, size, burnin=0, start=None, progressbar=True, asked=None):
         """All chains of one ``sample`` call as one device batch.
 
         Mirrors ``GibbsBase._run`` (base.py:214-241) per chain: start values from the chain's own
         generator (or the ``start`` dict), then ``size`` iterations keeping those ``>= burnin``.
-        ``site_summaries``: burn-in chunks run with the engine's per-site sums switched off; the switch goes on (which
-        zeroes them) right before the first chunk that keeps a draw, and inside that chunk the engine itself counts
-        only the iterations past the chunk's burn-in.  With the default no call about them reaches the engine.
-        ``waic``: the log-likelihood sums, switched in exactly the same way.
-        ``regions`` (an array of region ids, or None): the count of occupied sites per region, switched in the same way; every
-        chunk's rows are appended to the chains' ``occupied``.  With the default no call about it reaches the engine.
-        ``ppc``: the posterior predictive check, switched in the same way; every chunk's rows are appended and the
-        :class:`~occuspytial_amd.ppc.PredictiveCheck` made of them is left for ``sample``.  With the default no call about
-        it reaches the engine.
-        ``spatial_check``: the spatial residual check, switched in the same way; every chunk's rows are appended and the
-        :class:`~occuspytial_amd.spatial.SpatialCheck` made of them is left for ``sample``.  With the default no call about
-        it reaches the engine.
-        ``site_intervals`` (a number of bins, or False): the per-site histograms of psi, switched as the site sums are -- off
-        during burn-in chunks, on (which zeroes them) before the first chunk that keeps a draw; they accumulate on the
-        device and the :class:`~occuspytial_amd.intervals.SiteIntervals` read from the engine at the end is left for
-        ``sample``.  With the default no call about them reaches the engine.
-        ``site_diagnostics`` (a batch length, or False): the per-site batch-means sums of psi and eta, switched in the same
-        way; the :class:`~occuspytial_amd.convergence.SiteDiagnostics` read from the engine at the end is left for ``sample``.
-        With the default no call about them reaches the engine.
-        ``holdout`` (the packed withheld data, or None): the held-out sums, switched in the same way -- the data are set with
-        every chain off before the first chunk; the :class:`~occuspytial_amd.holdout.HoldoutScore` read from the engine at
-        the end is left for ``sample``.  With the default no call about them reaches the engine.
+        ``asked`` maps the keyword of every optional output asked for to what the engine is asked for (``options.ask``).
+        Each of them goes through its row's four phases: burn-in chunks run with it off -- so does an option that is not
+        asked but was left on by an earlier call on this engine; it goes on (which zeroes what accumulates) right before the
+        first chunk that keeps a draw, and inside that chunk the engine itself counts only the iterations past the chunk's
+        burn-in; the rows of its draws, if it has them, are read after every chunk that keeps one; its result is made at the end
+        and left for ``sample``.  With the defaults no call about any option reaches the engine.
         """
         from tqdm.auto import tqdm
 
@@ -339,33 +210,14 @@ class LogitICARGibbs(GibbsBase):
         for c, s in enumerate(samplers):
             self._push_start(eng, c, s.state)
             eng.set('z', z0, c)
-        kinds = self._sums_asked(site_summaries=site_summaries, waic=waic)
-        for kind in _lib.SUMS_KINDS:
-            if kind in kinds or getattr(eng, '_sums_on', {}).get(kind):   # (a reused engine that an earlier call left switched on)
-                self._sums_switch(eng, kind, False)   # (also the early answer of a library that does not know the kind)
-        if regions is not None:   # (sets the map with every chain's switch off)
-            self._regions_call(lambda: eng.regions(regions))
-        elif getattr(eng, '_region_on', False):   # (a reused engine that an earlier call left counting)
-            eng.region_stats(False)
-        if ppc or getattr(eng, '_ppc_on', False):   # (off during burn-in; a reused engine that an earlier call left on)
-            self._ppc_switch(eng, False)
-        if spatial_check or getattr(eng, '_moran_on', False):   # (likewise)
-            self._moran_switch(eng, False)
-        if site_intervals or getattr(eng, '_hist_bins', 0):   # (likewise)
-            self._hist_switch(eng, 0)
-        if site_diagnostics or getattr(eng, '_conv_batch', 0):   # (likewise)
-            self._conv_switch(eng, 0)
-        if holdout is not None:   # (sets the data with every chain's switch off)
-            self._holdout_call(lambda: eng.holdout_data(holdout))
-        elif getattr(eng, '_holdout_on', False):   # (a reused engine that an earlier call left on)
-            eng.holdout_stats(False)
-        sums_on = False
+        asked = asked or {}
+        for o in OPTIONS:
+            o.before(eng, asked.get(o.keyword))
+        switched_on = False
 
         C = len(samplers)
         keep = size - burnin
-        extra = {'occupied': np.zeros((C, keep, max(int(regions.max()) + 1, 1)))} if regions is not None else {}
-        ppc_rows = np.zeros((C, keep, 4)) if ppc else None
-        moran_rows = np.zeros((C, keep, 8)) if spatial_check else None
+        mine = [(o, asked[o.keyword], o.rows(C, keep, asked[o.keyword])) for o in OPTIONS if o.keyword in asked]
         alpha = np.zeros((C, keep, self._problem.q))
         beta = np.zeros((C, keep, self._problem.p))
         tau = np.zeros((C, keep))
@@ -378,31 +230,15 @@ class LogitICARGibbs(GibbsBase):
             if b == step:  # the whole chunk is burn-in: run it, keep only its last draw, drop it
                 eng.run(step, step - 1)
             else:
-                if not sums_on:
-                    for kind in kinds:
-                        self._sums_switch(eng, kind, True)
-                    if regions is not None:
-                        eng.region_stats(True)
-                    if ppc:
-                        eng.ppc_stats(True)
-                    if spatial_check:
-                        eng.moran_stats(True)
-                    if site_intervals:
-                        eng.hist_stats(site_intervals)
-                    if site_diagnostics:
-                        eng.conv_stats(site_diagnostics)
-                    if holdout is not None:
-                        eng.holdout_stats(True)
-                    sums_on = True
+                if not switched_on:
+                    for o, want, _ in mine:
+                        o.on(eng, want)
+                    switched_on = True
                 a_, b_, t_ = eng.run(step, b)
                 m = step - b
                 alpha[:, kept:kept + m], beta[:, kept:kept + m], tau[:, kept:kept + m] = a_, b_, t_
-                if regions is not None:
-                    extra['occupied'][:, kept:kept + m] = [eng.region_draws(c) for c in range(C)]
-                if ppc:
-                    ppc_rows[:, kept:kept + m] = [eng.ppc_draws(c) for c in range(C)]
-                if spatial_check:
-                    moran_rows[:, kept:kept + m] = [eng.moran_draws(c) for c in range(C)]
+                for o, _, rows in mine:
+                    o.read(eng, rows, kept, kept + m)
                 kept += m
             done += step
             for bar in bars:
@@ -410,6 +246,7 @@ class LogitICARGibbs(GibbsBase):
         for bar in bars:
             bar.close()
 
+        extra = {o.vector: rows for o, _, rows in mine if o.vector}
         chains = []
         for c, s in enumerate(samplers):
             ch = Chain._from_arrays({'alpha': alpha[c], 'beta': beta[c], 'tau': tau[c], **{k: v[c] for k, v in extra.items()}},
@@ -417,18 +254,7 @@ class LogitICARGibbs(GibbsBase):
             s.chain = ch
             chains.append(ch)
         self._pull_state(eng, 0)
-        for kind in kinds:
-            self.__dict__['_' + _lib.SUMS_KINDS[kind].result] = SUMS_RESULT[kind].from_engine(eng)
-        if ppc:
-            self.__dict__['_ppc'] = PredictiveCheck.from_problem(self._problem, ppc_rows)
-        if spatial_check:
-            self.__dict__['_spatial_check'] = SpatialCheck.from_problem(self._problem, moran_rows)
-        if site_intervals:
-            self.__dict__['_site_intervals'] = SiteIntervals.from_engine(eng)
-        if site_diagnostics:
-            self.__dict__['_site_diagnostics'] = SiteDiagnostics.from_engine(eng)
-        if holdout is not None:
-            self.__dict__['_holdout'] = HoldoutScore.from_engine(eng)
+        self.__dict__['_outputs'] = {o.result: o.finish(eng, self._problem, want, rows) for o, want, rows in mine}
         return chains
 
 

@@ -7,7 +7,6 @@ the same model with both fixed (DESIGN.md "ProbitRSRGibbs").
 """
 import numpy as np
 
-from .. import _lib
 from .._engine import Engine
 from .logit import LogitICARGibbs
 from .base import GibbsBase
@@ -102,34 +101,10 @@ class ProbitRSRGibbs(GibbsBase):
         st = self.state
         st.eps = eng.get('eps', chain)
 
-    def _refuse_sums(self, kind):
-        # (its z update conditions on the auxiliary eps: what "psi" should mean there is a modelling decision not yet made,
-        # and the site's marginal likelihood is not what it forms)
-        raise NotImplementedError(_lib.SUMS_KINDS[kind].probit)
-
-    def _refuse_ppc(self):
-        # (its detection part is a probit regression on the auxiliary scale: a check of it is out of scope so far)
-        raise NotImplementedError('posterior predictive checks are not available for the probit model')
-
-    def _refuse_spatial_check(self):
-        # (its psi is the modelling decision DESIGN 11 leaves open)
-        raise NotImplementedError('the spatial residual check is not available for the probit model')
-
-    def _refuse_site_intervals(self):
-        # (its psi is the modelling decision DESIGN 11 leaves open)
-        raise NotImplementedError('site intervals are not available for the probit model')
-
-    def _refuse_site_diagnostics(self):
-        # (likewise)
-        raise NotImplementedError('site diagnostics are not available for the probit model')
-
-    def _refuse_holdout(self):
-        # (likewise)
-        raise NotImplementedError('held-out scoring is not available for the probit model')
+    def _refusal(self, option):
+        return option.probit   # (None where this model allows the option: the rows of gibbs/options.py say which and why)
 
     step = LogitICARGibbs.step
     checkpoint = LogitICARGibbs.checkpoint
     resume = LogitICARGibbs.resume
     _run_chains = LogitICARGibbs._run_chains
-    _regions_call = LogitICARGibbs._regions_call   # (the occupied sites per region ARE counted here: its z is drawn as the reference draws it)
-
