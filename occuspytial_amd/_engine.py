@@ -116,13 +116,11 @@ class Engine:
         self.keys = [int(v) & (2 ** 64 - 1) for v in keys]
         # kind of per-site sums (_lib.SUMS_KINDS) -> switched on (sums_switch); off: no call about them reaches the library
         self._sums_on = dict.fromkeys(_lib.SUMS_KINDS, False)
-        # occupied sites per region and draw: the map (None: never set) and the switch; until set, no call about them reaches the library
+        # the draws of a call (_lib.DRAWS_KINDS): each kind's switch, and the regions' map (None: never set); until a switch or
+        # the map is first set, no call about the kind reaches the library
         self._regions = None
-        self._region_on = False
-        # posterior predictive check: the switch; until it is first set, no call about it reaches the library
-        self._ppc_on = False
-        # spatial residual check: the switch; until it is first set, no call about it reaches the library
-        self._moran_on = False
+        for k in _lib.DRAWS_KINDS.values():
+            setattr(self, k.on, False)
         # per-site intervals: the number of bins while switched on, 0 while off; until it is first set, no call about them
         # reaches the library
         self._hist_bins = 0
@@ -224,13 +222,12 @@ class Engine:
                 out[switch] = np.ones(self.n_chains)
                 for name in rest:
                     out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
-        if self._regions is not None:   # the map (one row per chain, as every entry) and the switch; the draws belong to a call
-            out['region_id'] = np.tile(self._regions, (self.n_chains, 1))
-            out['region_stats'] = np.full(self.n_chains, float(self._region_on))
-        if self._ppc_on:   # the switch; the draws belong to a call
-            out['ppc_stats'] = np.ones(self.n_chains)
-        if self._moran_on:   # likewise
-            out['moran_stats'] = np.ones(self.n_chains)
+        for k in _lib.DRAWS_KINDS.values():   # (the handle's input, one row per chain, as every entry,) and the switch; the draws belong to a call
+            on = getattr(self, k.on)
+            if k.input and self._regions is not None:
+                out[k.input] = np.tile(self._regions, (self.n_chains, 1))
+            if k.input in out or (on and not k.input):
+                out[k.fields[-2]] = np.full(self.n_chains, float(on))
         for kind, k in _lib.ACCUM_KINDS.items():
             on = getattr(self, k.on)
             if on:   # (the handle's input, one row per chain, as every entry,) the switch's value, the counts and the data
@@ -269,19 +266,13 @@ class Engine:
                         self.set(name, ckpt[name][c], c)
             elif self._sums_on[kind]:
                 self.sums_switch(kind, False)
-        if 'region_id' in ckpt:
-            self.regions(np.asarray(ckpt['region_id'])[0])
-            self.region_stats(bool(np.all(np.asarray(ckpt['region_stats']) != 0)))
-        elif self._region_on:
-            self.region_stats(False)
-        if 'ppc_stats' in ckpt and np.all(np.asarray(ckpt['ppc_stats']) != 0):
-            self.ppc_stats(True)
-        elif self._ppc_on:
-            self.ppc_stats(False)
-        if 'moran_stats' in ckpt and np.all(np.asarray(ckpt['moran_stats']) != 0):
-            self.moran_stats(True)
-        elif self._moran_on:
-            self.moran_stats(False)
+        for k in _lib.DRAWS_KINDS.values():   # (the methods bear the names of the switches)
+            switch = k.fields[-2]
+            on = switch in ckpt and bool(np.all(np.asarray(ckpt[switch]) != 0))
+            if k.input in ckpt:   # (a kind with an input is switched as the checkpoint says, off too)
+                self.regions(np.asarray(ckpt[k.input])[0])
+            if k.input in ckpt or on or getattr(self, k.on):
+                getattr(self, switch)(on)
         for k in _lib.ACCUM_KINDS.values():   # (the methods bear the names of the input and of the switch)
             switch, count, data = k.fields[-3:]
             if switch in ckpt and np.all(np.asarray(ckpt[switch]) != 0):
@@ -367,34 +358,39 @@ class Engine:
         count, counts = self._accum('hist', chain)
         return {'bins': counts.shape[0], 'count': count, 'counts': counts}
 
-    # ---- spatial residual check (state names moran_*, include/occ_gibbs.h) ----
+    # ---- the draws of a call (state names moran_*, ppc_* and region_*, include/occ_gibbs.h), by kind (_lib.DRAWS_KINDS) ----
+    def _draws_switch(self, kind, on):
+        k = _lib.DRAWS_KINDS[kind]
+        for c in range(self.n_chains):
+            self.set(k.fields[-2], 1.0 if on else 0.0, c)
+        setattr(self, k.on, bool(on))
+
+    def _draws_rows(self, kind, chain):
+        k = _lib.DRAWS_KINDS[kind]
+        width = k.width or (max(int(self._regions.max()) + 1, 1) if self._regions is not None else 1)
+        return self.get(k.fields[-1], chain).reshape(-1, width)
+
     def moran_stats(self, on):
         """Switch the spatial residual check of every chain.  While on, every kept draw of ``run`` records the sums of
         Moran's I of the occupancy residuals z - psi and of one replicate of them (:meth:`moran_draws`)."""
-        for c in range(self.n_chains):
-            self.set('moran_stats', 1.0 if on else 0.0, c)
-        self._moran_on = bool(on)
+        self._draws_switch('moran', on)
 
     def moran_draws(self, chain=0):
         """``(keep, 8)`` rows of one chain from the last ``run`` -- A, B, C, D of the residuals, then of their replicate
         (``occuspytial_amd.spatial``) -- ``(0, 8)`` if its switch was off during that call."""
-        return self.get('moran_draws', chain).reshape(-1, 8)
+        return self._draws_rows('moran', chain)
 
-    # ---- posterior predictive check (state names ppc_*, include/occ_gibbs.h) ----
     def ppc_stats(self, on):
         """Switch the posterior predictive check of every chain.  While on, every kept draw of ``run`` replicates the
         detections of every surveyed site from the draw's z and alpha and records four sums (:meth:`ppc_draws`)."""
-        for c in range(self.n_chains):
-            self.set('ppc_stats', 1.0 if on else 0.0, c)
-        self._ppc_on = bool(on)
+        self._draws_switch('ppc', on)
 
     def ppc_draws(self, chain=0):
         """``(keep, 4)`` rows of one chain from the last ``run`` -- the Freeman-Tukey discrepancy of the observed and of the
         replicated detections, the replicated detections, the replicated sites with a detection -- ``(0, 4)`` if its
         switch was off during that call."""
-        return self.get('ppc_draws', chain).reshape(-1, 4)
+        return self._draws_rows('ppc', chain)
 
-    # ---- occupied sites per region and draw (state names region_*, include/occ_gibbs.h) ----
     def regions(self, ids):
         """Set the handle's map: the region of every site, whole numbers in [-1, 256), -1 for none.  The switches of all
         chains go off first (the library sets a map only then)."""
@@ -407,14 +403,11 @@ class Engine:
     def region_stats(self, on):
         """Switch the count of occupied sites per region of every chain.  While on, every kept draw of ``run`` records, per
         region, the number of its sites with z = 1 (:meth:`region_draws`)."""
-        for c in range(self.n_chains):
-            self.set('region_stats', 1.0 if on else 0.0, c)
-        self._region_on = bool(on)
+        self._draws_switch('region', on)
 
     def region_draws(self, chain=0):
         """``(keep, G)`` counts of one chain from the last ``run``; ``(0, G)`` if its switch was off during that call."""
-        G = max(int(self._regions.max()) + 1, 1) if self._regions is not None else 1
-        return self.get('region_draws', chain).reshape(-1, G)
+        return self._draws_rows('region', chain)
 
     # ---- per-site sums accumulated on the device (state names site_* and ll_*, include/occ_gibbs.h), by kind ----
     def sums_switch(self, kind, on):
@@ -621,10 +614,10 @@ class EngineGroup:
     # inputs are set on every engine, its results are read from the engine of the chain (the last argument, 0 if left out,
     # after `lead` others), and what Engine remembers of it is any engine's, the largest, or the first engine's.  A stand-in
     # engine of the tests need not know a feature: it has it switched off.
-    ON_EVERY = ('sums_switch', 'regions', 'region_stats', 'ppc_stats', 'moran_stats', 'hist_stats', 'conv_stats', 'holdout_data', 'holdout_stats')
-    BY_CHAIN = {'sums': 1, 'region_draws': 0, 'ppc_draws': 0, 'moran_draws': 0, 'hist_counts': 0, 'conv_sums': 0, 'holdout_sums': 0}
-    REMEMBERED = {'_regions': None, '_region_on': any, '_ppc_on': any, '_moran_on': any, '_hist_bins': max, '_conv_batch': max,
-                  '_holdout': None, '_holdout_on': any}
+    _DRAWS = tuple(_lib.DRAWS_KINDS.values())   # (their methods bear the names of the switch and of the rows)
+    ON_EVERY = ('sums_switch', 'regions') + tuple(k.fields[-2] for k in _DRAWS) + ('hist_stats', 'conv_stats', 'holdout_data', 'holdout_stats')
+    BY_CHAIN = {'sums': 1, **{k.fields[-1]: 0 for k in _DRAWS}, 'hist_counts': 0, 'conv_sums': 0, 'holdout_sums': 0}
+    REMEMBERED = {'_regions': None, **{k.on: any for k in _DRAWS}, '_hist_bins': max, '_conv_batch': max, '_holdout': None, '_holdout_on': any}
 
     # (the entry points by name are Engine's own: each only names its kind)
     site_stats, site_sums, loglik_stats, loglik_sums = Engine.site_stats, Engine.site_sums, Engine.loglik_stats, Engine.loglik_sums

@@ -19,14 +19,6 @@ N_KERNEL_KINDS = 9
 SITE_FIELDS = ('site_stats', 'site_count', 'site_psi', 'site_occ', 'site_z', 'site_eta', 'site_eta2')
 # likewise the per-site log-likelihood sums of streaming WAIC: switch, count, and the three sums of length n
 LOGLIK_FIELDS = ('ll_stats', 'll_count', 'll_lik', 'll_log', 'll_log2')
-# the occupied sites per region and draw: the handle's map (n), the chain's switch, the chain's counts of the last occ_run (keep G)
-REGION_FIELDS = ('region_id', 'region_stats', 'region_draws')
-# the posterior predictive check: the chain's switch, the chain's rows of the last occ_run (keep 4: T_obs, T_rep, replicated
-# detections, replicated sites with a detection)
-PPC_FIELDS = ('ppc_stats', 'ppc_draws')
-# the spatial residual check: the chain's switch (a word of the handle), the chain's rows of the last occ_run (keep 8: the sums
-# A, B, C, D of Moran's I of z - psi, then those of its replicate)
-MORAN_FIELDS = ('moran_stats', 'moran_draws')
 # per-site intervals: the chain's switch (a word of the handle: 0 off, B on with B bins), its count of accumulated iterations,
 # its histograms of psi (B n, bin-major)
 HIST_FIELDS = ('hist_stats', 'hist_count', 'hist_counts')
@@ -69,6 +61,29 @@ ACCUM_KINDS = {
     'conv': AccumKind(CONV_FIELDS, '_conv_batch', 11, 'float64', (11, -1)),     # (11, n)
     'holdout': AccumKind(HOLDOUT_FIELDS, '_holdout_on', 5, 'float64', (5, -1)),  # (5, H)
 }
+
+
+class DrawsKind(NamedTuple):
+    """One kind of draws of a call (``DRAWS`` of csrc/occ_draws.hpp), as Python sees it.  ``Engine`` has a method by the name of
+    the switch and of the rows."""
+    fields: tuple       # its state names: (the handle's input first, if it needs one,) switch, rows
+    on: str             # the attribute of ``Engine`` that holds the switch
+    width: int          # numbers per row; None: set by the input
+
+    @property
+    def input(self):
+        return self.fields[0] if len(self.fields) == 3 else None
+
+
+DRAWS_KINDS = {
+    # the occupied sites per region and draw: the handle's map (n), the chain's switch, its counts of the last occ_run (keep G)
+    'region': DrawsKind(('region_id', 'region_stats', 'region_draws'), '_region_on', None),
+    # the posterior predictive check: T_obs, T_rep, the replicated detections, the replicated sites with a detection
+    'ppc': DrawsKind(('ppc_stats', 'ppc_draws'), '_ppc_on', 4),
+    # the spatial residual check: the sums A, B, C, D of Moran's I of z - psi, then those of its replicate
+    'moran': DrawsKind(('moran_stats', 'moran_draws'), '_moran_on', 8),
+}
+REGION_FIELDS, PPC_FIELDS, MORAN_FIELDS = (k.fields for k in DRAWS_KINDS.values())   # (the names the tests know them by)
 
 
 class OccProblem(C.Structure):

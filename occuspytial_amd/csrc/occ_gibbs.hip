@@ -28,6 +28,7 @@
 #include "occ_conv.hpp"
 #include "occ_holdout.hpp"
 #include "occ_accum.hpp"
+#include "occ_draws.hpp"
 #include "occ_layout.hpp"
 
 using namespace occ;
@@ -105,6 +106,11 @@ static_assert(ACCUM[ACC_HIST].slots == 1 && ACCUM[ACC_HIST].elem == sizeof(*Hist
 static_assert(ACCUM[ACC_CONV].slots == CONV_SLOTS && ACCUM[ACC_CONV].elem == sizeof(*ConvArgs::sums) && ACCUM[ACC_CONV].on_max == CONV_BATCH_MAX, "ACCUM: conv");
 static_assert(ACCUM[ACC_HOLD].slots == HOLD_SLOTS && ACCUM[ACC_HOLD].elem == sizeof(*HoldoutArgs::sums), "ACCUM: holdout");
 
+// So have the draws of a call (occ_draws.hpp: DRAWS): the widths and the element types are the kernels'.
+static_assert(DRAWS[DRW_REGION].width == 0 && DRAWS[DRW_REGION].elem == sizeof(*Ctx::occ_rec) && DRAWS[DRW_REGION].elem == sizeof(**PbRegions::rec), "DRAWS: regions");
+static_assert(DRAWS[DRW_PPC].width == PPC_NCOL && DRAWS[DRW_PPC].elem == sizeof(*Ctx::ppc_rec), "DRAWS: ppc");
+static_assert(DRAWS[DRW_MORAN].width == SP_NCOL && DRAWS[DRW_MORAN].scaled == SP_NCOL && DRAWS[DRW_MORAN].elem == sizeof(*SpArgs::rec), "DRAWS: moran");
+
 }  // namespace
 
 struct occ_sampler {
@@ -149,33 +155,27 @@ struct occ_sampler {
         bool snapped = false;
         double *snap = nullptr;
     } sums[N_SUMS];
-    // The record of one occ_run, [C][keep][width] elements: `rec` on the device, sized like rec_buf and grown between calls,
-    // zeroed on the stream when the call's window opens and copied out (pin) behind its last batch; last: that of the last
-    // completed occ_run on the host, for the chains whose switch was on during it (last_on).  open / copy_out / close: below.
-    template <class T>
+    // The record of one occ_run of one kind of draws (occ_draws.hpp: DRAWS), [C][keep][width] elements of the kind's size, in
+    // bytes: `rec` on the device, sized like rec_buf and grown between calls, zeroed on the stream when the call's window
+    // opens and copied out (pin) behind its last batch; last: that of the last completed occ_run on the host, for the chains
+    // whose switch was on during it (last_on).  ready: the kind's names answer.  open / copy_out / close / publish: below.
     struct CallRecord {
-        T *rec = nullptr, *pin = nullptr;
-        size_t rec_cap = 0, pin_cap = 0, run_need = 0;
-        std::vector<T> last;
-        std::vector<uint8_t> last_on;
+        bool ready = false;
+        uint8_t *rec = nullptr, *pin = nullptr;
+        size_t rec_cap = 0, pin_cap = 0, run_need = 0, width = 0;
+        std::vector<uint8_t> last, last_on;
         int64_t last_keep = 0;
-    };
-    // Occupied sites per region and kept draw (state names region_id, region_stats, region_draws).  G = 0: no map yet.
-    // The record's width is G counts (last_G: of the last completed call).
-    struct Regions : CallRecord<uint32_t> {
-        int G = 0, last_G = 0;
+    } draws[N_DRAWS];
+    // Occupied sites per region and kept draw: the handle's map, G = max + 1 regions (the record's width; 0: no map yet).
+    struct Regions {
+        int G = 0;
         std::vector<int16_t> id;
         int16_t *id_dev = nullptr;
-        // probit handle: the chains' switches (its PbChain has no word for them) and the address of `rec`, in device memory
+        // probit handle: the chains' switches (its PbChain has no word for them) and the address of the record, in device memory
         std::vector<uint32_t> pb_on;
         uint32_t *pb_on_dev = nullptr;
         uint32_t **pb_rec = nullptr;
     } regions;
-    // Posterior predictive check (state names ppc_stats, ppc_draws; logit models).  ready: a chain has been switched on once.
-    // The record's width is the PPC_NCOL integer sums.
-    struct Ppc : CallRecord<unsigned long long> {
-        bool ready = false;
-    } ppc;
     // The switches of a feature whose kernels stand behind the z update: a word of the handle per chain (on, on_dev), not a
     // bit of ChainScalars::site_on; any: their OR, which decides whether the kernels are launched (baked into captured graphs:
     // a change drops them).  switch_alloc / switch_set.
@@ -184,11 +184,10 @@ struct occ_sampler {
         std::vector<uint32_t> on;
         uint32_t *on_dev = nullptr;
     };
-    // Spatial residual check (state names moran_stats, moran_draws; logit models; occ_spatial.hpp).  ready: a chain has been
-    // switched on once -- the off-diagonal CSR of Q, the residuals' buffer and the switches are on the device.  The record's
-    // width is the SP_NCOL signed integer sums; args: the kernels' argument block (its `rec` follows the record).
-    struct Spatial : CallRecord<long long>, Switches {
-        bool ready = false;
+    // Spatial residual check (logit models; occ_spatial.hpp).  Ready once a chain has been switched on: the off-diagonal CSR
+    // of Q, the residuals' buffer and the switches are on the device.  args: the kernels' argument block (its `rec` follows
+    // the record).
+    struct Spatial : Switches {
         SpArgs args{};
     } spatial;
     // An accumulator behind the z update (occ_accum.hpp: ACCUM; logit models).  ready: its arrays are on the device -- data,
@@ -1329,59 +1328,86 @@ int residency_probe(occ_sampler *s, bool *ok)
 
 }  // namespace
 
-// ---- the record of one occ_run (occ_sampler::CallRecord: the regions' counts, both models; the predictive check's sums) ----
+// ---- the records of one occ_run (occ_sampler::CallRecord, one per kind of DRAWS; the regions' for both models) -------------
 namespace {
 
-// Head of an occ_run with `keep` recorded rows of `width` elements per chain (0: no chain has the output on).  The device
+// The chains' switches of a kind as the handle holds them: a bit of site_on in the scalars `h` the caller has read, or words
+// of the handle (the spatial check's; the probit handle's regions, where `h` is not used).
+std::vector<uint8_t> draws_on(const occ_sampler *s, int kind, const std::vector<ChainScalars> &h)
+{
+    const uint32_t bit = DRAWS[kind].bit;
+    const std::vector<uint32_t> &words = bit ? s->regions.pb_on : s->spatial.on;
+    std::vector<uint8_t> on((size_t)s->ctx.C, 0);
+    for (size_t c = 0; c < on.size(); ++c) on[c] = bit && !s->probit ? (h[c].site_on & bit) != 0u : c < words.size() && words[c] != 0u;
+    return on;
+}
+// Heads of an occ_run with `keep` recorded rows per chain, kind by kind; a kind no chain has on records nothing.  The device
 // record is grown between calls (nothing is in flight to the old one) and zeroed on the stream in front of the call's
 // kernels -- also when a call is re-run after a run-time fallback, so a re-run counts nothing twice.  What the last call
-// left on the host is dropped: the *_draws names speak of the last COMPLETED call.  The descriptors that hold the record's
-// address are the caller's.
-template <class T>
-int record_open(occ_sampler *s, occ_sampler::CallRecord<T> &r, int C, int64_t keep, size_t width)
+// left on the host is dropped: the rows names speak of the last COMPLETED call.
+int records_open(occ_sampler *s, int C, int64_t keep)
 {
-    r.last.clear();
-    r.last_on.assign((size_t)C, 0);
-    r.last_keep = 0;
-    r.run_need = (size_t)C * (size_t)keep * width;
-    if (!r.run_need) return OCC_OK;
-    int rc;
-    if ((rc = grow_device(s, &r.rec, &r.rec_cap, r.run_need))) return rc;
-    if ((rc = grow_pinned(s, &r.pin, &r.pin_cap, r.run_need))) return rc;
-    HIP_TRY(hipMemsetAsync(r.rec, 0, sizeof(T) * r.run_need, s->stream));
+    for (int k = 0; k < N_DRAWS; ++k) {
+        occ_sampler::CallRecord &r = s->draws[k];
+        const bool any = DRAWS[k].bit ? (s->outputs_on & DRAWS[k].bit) != 0u : s->spatial.any != 0u;
+        r.last.clear();
+        r.last_on.assign((size_t)C, 0);
+        r.last_keep = 0;
+        r.width = !any ? 0 : DRAWS[k].width ? (size_t)DRAWS[k].width : (size_t)s->regions.G;
+        r.run_need = (size_t)DRAWS[k].elem * (size_t)C * (size_t)keep * r.width;
+        if (!r.run_need) continue;
+        int rc;
+        if ((rc = grow_device(s, &r.rec, &r.rec_cap, r.run_need))) return rc;
+        if ((rc = grow_pinned(s, &r.pin, &r.pin_cap, r.run_need))) return rc;
+        HIP_TRY(hipMemsetAsync(r.rec, 0, r.run_need, s->stream));
+    }
     return OCC_OK;
 }
-// Behind the call's last batch, with the recorded rows: the copy to the page-locked staging buffer
-template <class T>
-int record_copy_out(occ_sampler *s, const occ_sampler::CallRecord<T> &r)
+// A record may have moved: its address goes to whoever holds it -- the device descriptor (with rec_buf's), the spatial
+// kernels' argument block, which travels by value in the captured launches (they drop), or the probit handle's word, which
+// holds it for the length of an occ_run only (occ_step and occ_profile never count: outside it the kernel finds no record).
+int records_publish(occ_sampler *s, bool in_run = true)
 {
-    if (r.run_need) HIP_TRY(hipMemcpyAsync(r.pin, r.rec, sizeof(T) * r.run_need, hipMemcpyDeviceToHost, s->stream));
+    Ctx &c = s->ctx;
+    uint32_t *occ = (uint32_t *)s->draws[DRW_REGION].rec;
+    unsigned long long *ppc = (unsigned long long *)s->draws[DRW_PPC].rec;
+    long long *moran = (long long *)s->draws[DRW_MORAN].rec;
+    if (s->probit) {
+        if (!in_run) occ = nullptr;
+        if (s->draws[DRW_REGION].run_need) HIP_TRY(copy_on(s, s->regions.pb_rec, &occ, sizeof(uint32_t *), hipMemcpyHostToDevice));
+        return OCC_OK;
+    }
+    if (s->spatial.args.rec != moran) {
+        WAIT_TRY(s->stream);
+        WAIT_TRY(s->side);
+        destroy_graph(s);
+        s->spatial.args.rec = moran;
+    }
+    if (c.rec != s->rec_buf || c.occ_rec != occ || c.ppc_rec != ppc) {
+        c.rec = s->rec_buf;
+        c.occ_rec = occ;
+        c.ppc_rec = ppc;
+        HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
+    }
     return OCC_OK;
 }
-// Clean end of the call (the stream has been waited for): what the *_draws name answers from now on.  on[c]: chain c's switch
-template <class T>
-void record_close(occ_sampler::CallRecord<T> &r, int64_t keep, const std::vector<uint8_t> &on)
+// Behind the call's last batch, with the recorded rows: the copies to the page-locked staging buffers
+int records_copy_out(occ_sampler *s)
 {
-    if (!r.run_need) return;
-    r.last.assign(r.pin, r.pin + r.run_need);
-    r.last_on = on;
-    r.last_keep = keep;
+    for (const occ_sampler::CallRecord &r : s->draws)
+        if (r.run_need) HIP_TRY(hipMemcpyAsync(r.pin, r.rec, r.run_need, hipMemcpyDeviceToHost, s->stream));
+    return OCC_OK;
 }
-int regions_open(occ_sampler *s, int C, int64_t keep)
+// Clean end of the call (the stream has been waited for): what the rows names answer from now on.  h: the scalars it ended with
+void records_close(occ_sampler *s, int64_t keep, const std::vector<ChainScalars> &h)
 {
-    return record_open(s, s->regions, C, keep, (s->outputs_on & OUT_REGION) ? (size_t)s->regions.G : 0);
-}
-void regions_close(occ_sampler *s, int64_t keep, const std::vector<uint8_t> &on)
-{
-    record_close(s->regions, keep, on);
-    s->regions.last_G = s->regions.G;
-}
-// the chains whose `bit` of site_on is set
-std::vector<uint8_t> chains_on(const std::vector<ChainScalars> &h, uint32_t bit)
-{
-    std::vector<uint8_t> on(h.size());
-    for (size_t c = 0; c < h.size(); ++c) on[c] = (h[c].site_on & bit) != 0u;
-    return on;
+    for (int k = 0; k < N_DRAWS; ++k) {
+        occ_sampler::CallRecord &r = s->draws[k];
+        if (!r.run_need) continue;
+        r.last.assign(r.pin, r.pin + r.run_need);
+        r.last_on = draws_on(s, k, h);
+        r.last_keep = keep;
+    }
 }
 
 }  // namespace
@@ -1611,8 +1637,7 @@ int pb_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, do
     for (PbChain &c : h) { c.rec_first = c.it + (uint32_t)burnin; c.rec_keep = (uint32_t)keep; }
     if ((rc = pb_write_chains(s, h))) return rc;
     HIP_TRY(copy_on(s, A.rec, &s->rec_buf, sizeof(double *), hipMemcpyHostToDevice));
-    if ((rc = regions_open(s, A.C, keep))) return rc;
-    if (s->regions.run_need) HIP_TRY(copy_on(s, s->regions.pb_rec, &s->regions.rec, sizeof(uint32_t *), hipMemcpyHostToDevice));
+    if ((rc = records_open(s, A.C, keep)) || (rc = records_publish(s))) return rc;
     if (!s->pb_exec) {  // one linear graph of PB_GRAPH_SEQ iterations, captured once (the kernels take nothing that changes)
         HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
         for (int k = 0; k < PB_GRAPH_SEQ && rc == OCC_OK; ++k) rc = pb_launch_iteration(s, s->stream);
@@ -1635,24 +1660,21 @@ int pb_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, do
         ++s->eager_iterations;
     }
     HIP_TRY(hipEventRecord(s->ev1, s->stream));
-    if ((rc = record_copy_out(s, s->regions))) return rc;
+    if ((rc = records_copy_out(s))) return rc;
     WAIT_TRY(s->stream);
     float ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     s->last_run_ms = ms;
     double *none = nullptr;
     HIP_TRY(copy_on(s, A.rec, &none, sizeof(double *), hipMemcpyHostToDevice));
-    if (s->regions.run_need) {  // (occ_step and occ_profile never count: outside occ_run the kernel finds no record)
-        uint32_t *no_rec = nullptr;
-        HIP_TRY(copy_on(s, s->regions.pb_rec, &no_rec, sizeof(uint32_t *), hipMemcpyHostToDevice));
-    }
+    if ((rc = records_publish(s, false))) return rc;
     std::vector<double> rec(need);
     if (need) HIP_TRY(copy_on(s, rec.data(), s->rec_buf, sizeof(double) * need, hipMemcpyDeviceToHost));
     split_rows(rec.data(), A.C, keep, A.q, A.p, out_alpha, out_beta, out_tau);
     if ((rc = pb_read_chains(s, h))) return rc;
     s->iterations = h[0].it;
     if ((rc = pb_check(s, h))) return rc;
-    regions_close(s, keep, std::vector<uint8_t>(s->regions.pb_on.begin(), s->regions.pb_on.end()));
+    records_close(s, keep, {});
     return OCC_OK;
 }
 
@@ -1860,12 +1882,10 @@ int occ_destroy(occ_sampler *s)
             if (s->pb_graph) (void)hipGraphDestroy(s->pb_graph);
             for (void *p : s->allocs) (void)hipFree(p);
             if (s->rec_buf) (void)hipFree(s->rec_buf);
-            if (s->regions.rec) (void)hipFree(s->regions.rec);
-            if (s->regions.pin) (void)hipHostFree(s->regions.pin);
-            if (s->ppc.rec) (void)hipFree(s->ppc.rec);
-            if (s->ppc.pin) (void)hipHostFree(s->ppc.pin);
-            if (s->spatial.rec) (void)hipFree(s->spatial.rec);
-            if (s->spatial.pin) (void)hipHostFree(s->spatial.pin);
+            for (const occ_sampler::CallRecord &r : s->draws) {
+                if (r.rec) (void)hipFree(r.rec);
+                if (r.pin) (void)hipHostFree(r.pin);
+            }
             if (s->pin_sc) (void)hipHostFree(s->pin_sc);
             if (s->pin_rec) (void)hipHostFree(s->pin_rec);
             for (hipEvent_t ev : {s->ev0, s->ev1, s->ev_z[0], s->ev_z[1], s->ev_side[0], s->ev_side[1]})
@@ -2708,12 +2728,8 @@ static int finish_marks(occ_sampler *s, bool last, size_t n_rec)
     const int grc = grow_pinned(s, &s->pin_rec, &s->pin_rec_cap, n_rec);
     if (grc) return grc;
     if (n_rec) HIP_TRY(hipMemcpyAsync(s->pin_rec, s->rec_buf, sizeof(double) * n_rec, hipMemcpyDeviceToHost, s->stream));
-    const int rrc = record_copy_out(s, s->regions);
+    const int rrc = records_copy_out(s);
     if (rrc) return rrc;
-    const int prc = record_copy_out(s, s->ppc);
-    if (prc) return prc;
-    const int src = record_copy_out(s, s->spatial);
-    if (src) return src;
     s->marks_done = true;
     return OCC_OK;
 }
@@ -2727,21 +2743,8 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     const size_t need = (size_t)C * keep * rw;
     int rc = grow_device(s, &s->rec_buf, &s->rec_cap, need);  // (its address lives in the device descriptor)
     if (rc) return rc;
-    if ((rc = regions_open(s, C, keep))) return rc;  // (zeroed here, in front of the window: also when the call is re-run)
-    if ((rc = record_open(s, s->ppc, C, keep, (s->outputs_on & OUT_PPC) ? (size_t)PPC_NCOL : 0))) return rc;
-    if ((rc = record_open(s, s->spatial, C, keep, s->spatial.any ? (size_t)SP_NCOL : 0))) return rc;
-    if (s->spatial.args.rec != s->spatial.rec) {  // (the record grew: its address travels by value in the captured launches)
-        WAIT_TRY(s->stream);
-        WAIT_TRY(s->side);
-        destroy_graph(s);
-        s->spatial.args.rec = s->spatial.rec;
-    }
-    if (c.rec != s->rec_buf || c.occ_rec != s->regions.rec || c.ppc_rec != s->ppc.rec) {
-        c.rec = s->rec_buf;
-        c.occ_rec = s->regions.rec;
-        c.ppc_rec = s->ppc.rec;
-        HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
-    }
+    if ((rc = records_open(s, C, keep))) return rc;  // (zeroed here, in front of the window: also when the call is re-run)
+    if ((rc = records_publish(s))) return rc;
     if ((rc = open_window(s, n_iter, burnin, keep, snapshot, true))) return rc;
     std::vector<ChainScalars> h;
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
@@ -2875,9 +2878,7 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     s->clean_exit = true;
 
     split_rows(s->pin_rec, C, keep, q, p, out_alpha, out_beta, out_tau);
-    regions_close(s, keep, chains_on(h, OUT_REGION));
-    record_close(s->ppc, keep, chains_on(h, OUT_PPC));
-    record_close(s->spatial, keep, std::vector<uint8_t>(s->spatial.on.begin(), s->spatial.on.end()));
+    records_close(s, keep, h);
     return OCC_OK;
 }
 
@@ -3166,161 +3167,56 @@ static int set_site_state(occ_sampler *s, int chain, int kind, int field, const 
     return flip_output(s, h, chain, k.bit, on);
 }
 
-// ---- occ_get_state / occ_set_state of the region names (both models) --------------------------------------------------
-// region_id (n): the handle's map, through any chain index -- whole numbers in [-1, REGION_MAX), -1: no region, G = max + 1
-// (at least 1); set only while no chain counts; allocates at first use.  region_stats (1): the chain's switch, 0 or 1.
-// region_draws (keep G, read-only): the chain's counts of the last completed occ_run, row-major [t][g]; length 0 if its
-// switch was off during that call.  Before the first region_id every name answers OCC_E_STATE.  Nothing of a chain's state
-// changes: nothing is redrawn.  Which z kernel is launched follows "is any chain on" (flip_output): a change
-// drops the captured graphs.
-enum : int { REGION_NONE = -1, REGION_ID = 0, REGION_SWITCH = 1, REGION_DRAWS = 2 };
-static int region_field(const std::string &nm)
-{
-    return nm == "region_id" ? REGION_ID : nm == output_of(OUT_REGION).sw ? REGION_SWITCH : nm == "region_draws" ? REGION_DRAWS : REGION_NONE;
-}
-static int regions_unset(occ_sampler *s)
-{
-    return set_error(s, OCC_E_STATE, "no regions have been set for this handle (set region_id first)");
-}
-// the chains' switches as the handle holds them now
-static int region_switches(occ_sampler *s, std::vector<uint8_t> &on, std::vector<ChainScalars> *scalars = nullptr)
-{
-    on.assign((size_t)s->ctx.C, 0);
-    if (s->probit) {
-        for (size_t c = 0; c < on.size() && c < s->regions.pb_on.size(); ++c) on[c] = s->regions.pb_on[c] != 0u;
-        return OCC_OK;
-    }
-    std::vector<ChainScalars> h;
-    const int rc = read_scalars(s, h);
-    if (rc) return rc;
-    on = chains_on(h, OUT_REGION);
-    if (scalars) scalars->swap(h);
-    return OCC_OK;
-}
-static int get_region_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
-{
-    const occ_sampler::Regions &rg = s->regions;
-    if (rg.G == 0) return regions_unset(s);
-    if (field == REGION_ID) {
-        v.assign(rg.id.begin(), rg.id.end());
-    } else if (field == REGION_SWITCH) {
-        std::vector<uint8_t> on;
-        const int rc = region_switches(s, on);
-        if (rc) return rc;
-        v.assign(1, on[(size_t)chain] ? 1.0 : 0.0);
-    } else {
-        v.clear();
-        if ((size_t)chain < rg.last_on.size() && rg.last_on[(size_t)chain]) {
-            const size_t per = (size_t)rg.last_keep * (size_t)rg.last_G;
-            v.assign(rg.last.begin() + (size_t)chain * per, rg.last.begin() + (size_t)(chain + 1) * per);
-        }
-    }
-    return OCC_OK;
-}
-static int set_region_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+// ---- occ_get_state / occ_set_state of the names of the draws of a call (DRAWS; the regions: both models) -----------------
+// Per kind: the chain's switch (1), 0 or 1; its rows (keep x width, read-only) of the last completed occ_run, row-major, as
+// draws_value returns them; length 0 if its switch was off during that call.  Until the kind is ready every name answers
+// OCC_E_STATE.  Nothing of a chain's state changes: nothing is redrawn.  What differs:
+//   region_id    (n) the handle's map, through any chain index -- whole numbers in [-1, REGION_MAX), -1: no region, G = max + 1
+//                (at least 1); set only while no chain counts; allocates at first use; makes the kind ready.
+//   ppc_stats    ready with the first valid write.  Like the regions' switch a bit of site_on: which z kernel is launched
+//                follows "is any chain on" (flip_output), a change drops the captured graphs.
+//   moran_stats  a word of the handle: whether the two kernels are launched behind the z update follows "is any chain on"
+//                (switch_set), a change drops the captured graphs.  Ready with the first switch-ON (moran_init); switching
+//                a chain OFF before that is accepted and does nothing.
+static int set_region_id(occ_sampler *s, const double *in, int64_t len)
 {
     occ_sampler::Regions &rg = s->regions;
     Ctx &c = s->ctx;
     const size_t n = (size_t)c.n;
     int rc;
-    if (field == REGION_DRAWS) return set_error(s, OCC_E_STATE, rg.G == 0 ? "no regions have been set for this handle (set region_id first)" : "region_draws is read-only");
-    if (field == REGION_SWITCH && rg.G == 0) return regions_unset(s);
-    std::vector<uint8_t> on;
     std::vector<ChainScalars> h;
-    if ((rc = region_switches(s, on, &h))) return rc;
-    if (field == REGION_ID) {
-        for (uint8_t o : on)
-            if (o) return set_error(s, OCC_E_STATE, "region_id cannot be set while a chain has region_stats on");
-        if ((size_t)len != n) return set_error(s, OCC_E_STATE, "wrong length");
-        std::vector<int16_t> id(n);
-        int top = 0;
-        for (size_t i = 0; i < n; ++i) {
-            if (!(in[i] >= -1.0 && in[i] < (double)REGION_MAX) || in[i] != std::floor(in[i]))
-                return set_error(s, OCC_E_BADARG, "region_id holds whole numbers from -1 (no region) to 255");
-            id[i] = (int16_t)in[i];
-            top = std::max(top, (int)id[i]);
-        }
-        WAIT_TRY(s->side);
-        if (!rg.id_dev) {
-            if ((rc = dev_alloc(s, &rg.id_dev, n))) return rc;
-            if (s->probit) {
-                if ((rc = dev_alloc(s, &rg.pb_on_dev, (size_t)c.C))) return rc;
-                if ((rc = dev_alloc(s, &rg.pb_rec, 1))) return rc;
-                rg.pb_on.assign((size_t)c.C, 0u);
-            }
-        }
-        HIP_TRY(copy_on(s, rg.id_dev, id.data(), sizeof(int16_t) * n, hipMemcpyHostToDevice));
-        rg.id.swap(id);
-        rg.G = top + 1;
-        if (!s->probit) {
-            c.region_id = rg.id_dev;
-            c.region_G = rg.G;
-            HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
-        }
-        return OCC_OK;
+    if (!s->probit && (rc = read_scalars(s, h))) return rc;
+    for (uint8_t o : draws_on(s, DRW_REGION, h))
+        if (o) return set_error(s, OCC_E_STATE, DRAWS[DRW_REGION].input_locked);
+    if ((size_t)len != draws_length(DRW_INPUT, n, 0, 0)) return set_error(s, OCC_E_STATE, "wrong length");
+    std::vector<int16_t> id(n);
+    int top = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!(in[i] >= -1.0 && in[i] < (double)REGION_MAX) || in[i] != std::floor(in[i]))
+            return set_error(s, OCC_E_BADARG, "region_id holds whole numbers from -1 (no region) to 255");
+        id[i] = (int16_t)in[i];
+        top = std::max(top, (int)id[i]);
     }
-    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
-    if (in[0] != 0.0 && in[0] != 1.0) return set_error(s, OCC_E_BADARG, "region_stats is 0 or 1");
     WAIT_TRY(s->side);
-    return flip_output(s, h, chain, OUT_REGION, in[0] != 0.0);
-}
-
-// ---- occ_get_state / occ_set_state of the predictive check's names (logit models) -------------------------------------
-// ppc_stats (1): the chain's switch, 0 or 1; the record of a call is allocated at first use.  ppc_draws (keep 4, read-only):
-// the chain's rows of the last completed occ_run as doubles, columns 0 and 1 times 2^-32 (exact below 2^53 quanta,
-// otherwise rounded to nearest); length 0 if its switch was off during that call.  Before the first switch-on both names
-// answer OCC_E_STATE.  Nothing of a chain's state changes: nothing is redrawn.  Which z kernel is launched follows "is any
-// chain on" (flip_output): a change drops the captured graphs.
-enum : int { PPC_NONE = -1, PPC_SWITCH = 0, PPC_DRAWS = 1 };
-static int ppc_field(const std::string &nm) { return nm == output_of(OUT_PPC).sw ? PPC_SWITCH : nm == "ppc_draws" ? PPC_DRAWS : PPC_NONE; }
-static int ppc_refused(occ_sampler *s)
-{
-    if (s->probit) return set_error(s, OCC_E_STATE, "posterior predictive checks are not available for the probit model");
-    return set_error(s, OCC_E_STATE, "the posterior predictive check has not been switched on for this handle (set ppc_stats first)");
-}
-static int get_ppc_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
-{
-    const occ_sampler::Ppc &pc = s->ppc;
-    if (s->probit || !pc.ready) return ppc_refused(s);
-    if (field == PPC_SWITCH) {
-        std::vector<ChainScalars> h;
-        const int rc = read_scalars(s, h);
-        if (rc) return rc;
-        v.assign(1, (h[chain].site_on & OUT_PPC) ? 1.0 : 0.0);
-        return OCC_OK;
+    if (!rg.id_dev) {
+        if ((rc = dev_alloc(s, &rg.id_dev, n))) return rc;
+        if (s->probit) {
+            if ((rc = dev_alloc(s, &rg.pb_on_dev, (size_t)c.C))) return rc;
+            if ((rc = dev_alloc(s, &rg.pb_rec, 1))) return rc;
+            rg.pb_on.assign((size_t)c.C, 0u);
+        }
     }
-    v.clear();
-    if ((size_t)chain < pc.last_on.size() && pc.last_on[(size_t)chain]) {
-        const size_t per = (size_t)pc.last_keep * (size_t)PPC_NCOL;
-        v.resize(per);
-        const unsigned long long *row = pc.last.data() + (size_t)chain * per;
-        for (size_t k = 0; k < per; ++k) v[k] = (k % PPC_NCOL) < 2 ? (double)row[k] * 0x1.0p-32 : (double)row[k];
+    HIP_TRY(copy_on(s, rg.id_dev, id.data(), sizeof(int16_t) * n, hipMemcpyHostToDevice));
+    rg.id.swap(id);
+    rg.G = top + 1;
+    s->draws[DRW_REGION].ready = true;
+    if (!s->probit) {
+        c.region_id = rg.id_dev;
+        c.region_G = rg.G;
+        HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
     }
     return OCC_OK;
 }
-static int set_ppc_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
-{
-    occ_sampler::Ppc &pc = s->ppc;
-    if (s->probit) return ppc_refused(s);
-    if (field == PPC_DRAWS) return pc.ready ? set_error(s, OCC_E_STATE, "ppc_draws is read-only") : ppc_refused(s);
-    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
-    if (in[0] != 0.0 && in[0] != 1.0) return set_error(s, OCC_E_BADARG, "ppc_stats is 0 or 1");
-    std::vector<ChainScalars> h;
-    int rc;
-    if ((rc = read_scalars(s, h))) return rc;
-    WAIT_TRY(s->side);
-    if ((rc = flip_output(s, h, chain, OUT_PPC, in[0] != 0.0))) return rc;
-    pc.ready = true;
-    return OCC_OK;
-}
-
-// ---- occ_get_state / occ_set_state of the spatial residual check's names (logit models) --------------------------------
-// moran_stats (1): the chain's switch, 0 or 1, a word of the handle.  moran_draws (keep 8, read-only): the chain's rows of the
-// last completed occ_run as doubles times 2^-32; length 0 if its switch was off during that call.  Before the first
-// switch-on both names answer OCC_E_STATE (switching a chain OFF before that is accepted and does nothing).  Nothing of a
-// chain's state changes.  Whether the two kernels are launched behind the z update follows "is any chain on": a change
-// drops the captured graphs, as flip_output does for a change of level.
-enum : int { MORAN_NONE = -1, MORAN_SWITCH = 0, MORAN_DRAWS = 1 };
 // The switches of a feature behind the z update (occ_sampler::Switches): every chain off, on the device too ...
 static int switch_alloc(occ_sampler *s, occ_sampler::Switches &sw)
 {
@@ -3338,12 +3234,6 @@ static int switch_set(occ_sampler *s, occ_sampler::Switches &sw, int chain, bool
     if (any != sw.any) destroy_graph(s);
     sw.any = any;
     return OCC_OK;
-}
-static int moran_field(const std::string &nm) { return nm == "moran_stats" ? MORAN_SWITCH : nm == "moran_draws" ? MORAN_DRAWS : MORAN_NONE; }
-static int moran_refused(occ_sampler *s)
-{
-    if (s->probit) return set_error(s, OCC_E_STATE, "the spatial residual check is not available for the probit model");
-    return set_error(s, OCC_E_STATE, "the spatial residual check has not been switched on for this handle (set moran_stats first)");
 }
 // First switch-on: the weights w_ij = -Q_ij as an off-diagonal CSR, from the handle's copy of Q -- its SELL-64 arrays on the
 // device, which hold the off-diagonals of every row in column order (occ_layout.hpp; a slot of value 0 is padding, or a
@@ -3399,40 +3289,58 @@ static int moran_init(occ_sampler *s)
     sp.args.n = n, sp.args.p = c.p;
     sp.args.Xt = c.Xt, sp.args.eta = c.eta, sp.args.z = c.z;
     sp.args.ptr = ptr_dev, sp.args.col = col_dev, sp.args.val = val_dev;
-    sp.args.res = res, sp.args.rec = sp.rec, sp.args.on = sp.on_dev;
-    sp.ready = true;
+    sp.args.res = res, sp.args.rec = (long long *)s->draws[DRW_MORAN].rec, sp.args.on = sp.on_dev;
+    s->draws[DRW_MORAN].ready = true;
     return OCC_OK;
 }
-static int get_moran_state(occ_sampler *s, int chain, int field, std::vector<double> &v)
-{
-    const occ_sampler::Spatial &sp = s->spatial;
-    if (s->probit || !sp.ready) return moran_refused(s);
-    if (field == MORAN_SWITCH) {
-        v.assign(1, sp.on[(size_t)chain] ? 1.0 : 0.0);
-        return OCC_OK;
-    }
-    v.clear();
-    if ((size_t)chain < sp.last_on.size() && sp.last_on[(size_t)chain]) {
-        const size_t per = (size_t)sp.last_keep * (size_t)SP_NCOL;
-        v.resize(per);
-        const long long *row = sp.last.data() + (size_t)chain * per;
-        for (size_t k = 0; k < per; ++k) v[k] = (double)row[k] * 0x1.0p-32;
-    }
-    return OCC_OK;
-}
-static int set_moran_state(occ_sampler *s, int chain, int field, const double *in, int64_t len)
+static int moran_switch(occ_sampler *s, int chain, bool on)
 {
     occ_sampler::Spatial &sp = s->spatial;
-    if (s->probit) return moran_refused(s);
-    if (field == MORAN_DRAWS) return sp.ready ? set_error(s, OCC_E_STATE, "moran_draws is read-only") : moran_refused(s);
-    if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
-    if (in[0] != 0.0 && in[0] != 1.0) return set_error(s, OCC_E_BADARG, "moran_stats is 0 or 1");
-    const bool on = in[0] != 0.0;
-    if (!on && !sp.ready) return OCC_OK;  // never switched on: nothing to switch off
+    const bool ready = s->draws[DRW_MORAN].ready;
+    if (!on && !ready) return OCC_OK;  // never switched on: nothing to switch off
     int rc;
     WAIT_TRY(s->side);
-    if (!sp.ready && (rc = moran_init(s))) return rc;
+    if (!ready && (rc = moran_init(s))) return rc;
     return switch_set(s, sp, chain, on);
+}
+static int get_draws_state(occ_sampler *s, int chain, int kind, int field, std::vector<double> &v)
+{
+    const Draws &d = DRAWS[kind];
+    const occ_sampler::CallRecord &r = s->draws[kind];
+    if ((s->probit && !d.probit) || !r.ready) return set_error(s, OCC_E_STATE, s->probit && !d.probit ? d.no_probit : d.not_ready);
+    if (field == DRW_INPUT) {
+        v.assign(s->regions.id.begin(), s->regions.id.end());
+    } else if (field == DRW_SWITCH) {
+        std::vector<ChainScalars> h;
+        int rc;
+        if (d.bit && !s->probit && (rc = read_scalars(s, h))) return rc;
+        v.assign(1, draws_on(s, kind, h)[(size_t)chain] ? 1.0 : 0.0);
+    } else {
+        const bool has = (size_t)chain < r.last_on.size() && r.last_on[(size_t)chain];
+        v.resize(has ? draws_length(DRW_ROWS, 0, (size_t)r.last_keep, r.width) : 0);
+        const uint8_t *row = r.last.data() + (size_t)d.elem * (size_t)chain * v.size();
+        for (size_t k = 0; k < v.size(); ++k) v[k] = draws_value(d, row + (size_t)d.elem * k, k % r.width);
+    }
+    return OCC_OK;
+}
+static int set_draws_state(occ_sampler *s, int chain, int kind, int field, const double *in, int64_t len)
+{
+    const Draws &d = DRAWS[kind];
+    occ_sampler::CallRecord &r = s->draws[kind];
+    if (s->probit && !d.probit) return set_error(s, OCC_E_STATE, d.no_probit);
+    if (field == DRW_INPUT) return set_region_id(s, in, len);
+    if (!r.ready && (field == DRW_ROWS || d.name[DRW_INPUT])) return set_error(s, OCC_E_STATE, d.not_ready);  // (a kind with an input is switched only after it)
+    if (field == DRW_ROWS) return set_error(s, OCC_E_STATE, d.read_only);
+    if ((size_t)len != draws_length(DRW_SWITCH, 0, 0, 0)) return set_error(s, OCC_E_STATE, "wrong length");
+    if (in[0] != 0.0 && in[0] != 1.0) return set_error(s, OCC_E_BADARG, d.bad_switch);
+    if (!d.bit) return moran_switch(s, chain, in[0] != 0.0);
+    std::vector<ChainScalars> h;
+    int rc;
+    if (!s->probit && (rc = read_scalars(s, h))) return rc;
+    WAIT_TRY(s->side);
+    if ((rc = flip_output(s, h, chain, d.bit, in[0] != 0.0))) return rc;
+    r.ready = true;
+    return OCC_OK;
 }
 
 // ---- occ_get_state / occ_set_state of the names of the accumulators behind the z update (ACCUM; logit models) ----------
@@ -3705,17 +3613,11 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     const std::string nm(name);
     const size_t n = (size_t)c.n, R = (size_t)c.R;
     std::vector<double> v;
-    if (region_field(nm) != REGION_NONE) {
-        const int rrc = get_region_state(s, chain, region_field(nm), v);
-        return rrc ? rrc : give_state(s, v, out, cap, len);
-    }
-    if (ppc_field(nm) != PPC_NONE) {
-        const int prc = get_ppc_state(s, chain, ppc_field(nm), v);
-        return prc ? prc : give_state(s, v, out, cap, len);
-    }
-    if (moran_field(nm) != MORAN_NONE) {
-        const int mrc = get_moran_state(s, chain, moran_field(nm), v);
-        return mrc ? mrc : give_state(s, v, out, cap, len);
+    int drw_field = DRW_NONE;
+    const int drw_kind = draws_lookup(name, &drw_field);
+    if (drw_kind >= 0) {
+        const int drc = get_draws_state(s, chain, drw_kind, drw_field, v);
+        return drc ? drc : give_state(s, v, out, cap, len);
     }
     int acc_field = ACC_NONE;
     const int acc_kind = accum_lookup(name, &acc_field);
@@ -3788,9 +3690,9 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     HIP_TRY(hipSetDevice(s->device));
     WAIT_TRY(s->stream);
     const std::string nm(name);
-    if (region_field(nm) != REGION_NONE) return set_region_state(s, chain, region_field(nm), in, len);
-    if (ppc_field(nm) != PPC_NONE) return set_ppc_state(s, chain, ppc_field(nm), in, len);
-    if (moran_field(nm) != MORAN_NONE) return set_moran_state(s, chain, moran_field(nm), in, len);
+    int drw_field = DRW_NONE;
+    const int drw_kind = draws_lookup(name, &drw_field);
+    if (drw_kind >= 0) return set_draws_state(s, chain, drw_kind, drw_field, in, len);
     int acc_field = ACC_NONE;
     const int acc_kind = accum_lookup(name, &acc_field);
     if (acc_kind >= 0) return set_accum_state(s, chain, acc_kind, acc_field, in, len);

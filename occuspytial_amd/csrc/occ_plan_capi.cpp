@@ -1,11 +1,13 @@
 // occ_plan_capi.cpp -- the planner, the launch order and the z update's outputs (occ_plan.hpp), the accumulators behind the z
-// update (occ_accum.hpp) and the problem layout (occ_layout.hpp) behind C entry points for tests/test_plan_cpu.py,
-// tests/test_order_cpu.py, tests/test_outputs_cpu.py, tests/test_accum_cpu.py and tests/test_layout_cpu.py (ctypes).  Test infrastructure:
-// `make plan` builds it with g++ into build/; it is never linked into libocc_gibbs.so.
+// update (occ_accum.hpp), the draws of a call (occ_draws.hpp) and the problem layout (occ_layout.hpp) behind C entry points for
+// tests/test_plan_cpu.py, tests/test_order_cpu.py, tests/test_outputs_cpu.py, tests/test_accum_cpu.py, tests/test_draws_cpu.py
+// and tests/test_layout_cpu.py (ctypes).  Test infrastructure: `make plan` builds it with g++ into build/; it is never linked
+// into libocc_gibbs.so.
 #include <cstdio>
 #include <cstring>
 
 #include "occ_accum.hpp"
+#include "occ_draws.hpp"
 #include "occ_layout.hpp"
 
 using namespace occ;
@@ -109,6 +111,20 @@ const char *occ_accum_write_refusal(int32_t k, int32_t field, const double *in, 
 {
     return accum_write_refusal(ACCUM[k], field, in, (size_t)len, (size_t)unit);
 }
+
+// The draws of a call (occ_draws.hpp: DRAWS): how many; row k's three state names by field (null: none), its five refusals
+// and numbers {elem, is_signed, width, scaled, bit, probit}; then its functions as they are (a raw element as its 64 bits).
+int32_t occ_draws_count(void) { return N_DRAWS; }
+void occ_draws_row(int32_t k, const char *name[3], const char *refusal[5], int32_t num[6])
+{
+    const Draws &d = DRAWS[k];
+    for (int f = 0; f < 3; ++f) name[f] = d.name[f];
+    refusal[0] = d.not_ready; refusal[1] = d.no_probit; refusal[2] = d.bad_switch; refusal[3] = d.read_only; refusal[4] = d.input_locked;
+    num[0] = d.elem; num[1] = d.is_signed; num[2] = d.width; num[3] = d.scaled; num[4] = (int32_t)d.bit; num[5] = d.probit;
+}
+int32_t occ_draws_lookup(const char *name, int32_t *field) { return draws_lookup(name, field); }
+double occ_draws_value(int32_t k, uint64_t raw, int64_t col) { return draws_value(DRAWS[k], &raw, (size_t)col); }
+int64_t occ_draws_length(int32_t field, int64_t n, int64_t keep, int64_t width) { return (int64_t)draws_length(field, (size_t)n, (size_t)keep, (size_t)width); }
 
 // The layout of a logit problem, by build_layout's steps in its order (occ_gibbs.hip), plus the probit model's row_t.
 // A handle for occ_layout_array / occ_layout_peer, or null with the refusal in err.

@@ -7,8 +7,8 @@ the first chunk, ``on`` before the first chunk that keeps a draw, ``read`` after
 rule for ``resume``.  The samplers loop over the rows (``GibbsBase.sample``, ``LogitICARGibbs._run_chains`` and ``resume``).
 
 The rows come in the three families of the native side: the per-site running sums (``_lib.SUMS_KINDS``), the draws of a call
-(rows read after every chunk; nothing of them is carried over a checkpoint) and the accumulators behind the z update
-(``_lib.ACCUM_KINDS``).  A ninth option is a row here, a keyword with its paragraph in ``sample`` and ``resume``, an attribute
+(``_lib.DRAWS_KINDS``: rows read after every chunk; nothing of them is carried over a checkpoint) and the accumulators behind
+the z update (``_lib.ACCUM_KINDS``).  A ninth option is a row here, a keyword with its paragraph in ``sample`` and ``resume``, an attribute
 of ``PosteriorParameter`` and the ``Engine`` methods the row names.
 """
 import numpy as np
@@ -169,13 +169,13 @@ OPTIONS = (
     Draws('ppc', 'ppc', lambda value, problem, kept: ppc_flag(value) or None,
           python_step='posterior predictive checks are formed by the device engine only',
           probit='posterior predictive checks are not available for the probit model', rebuild='has no posterior predictive check',
-          switch='ppc_stats', left_on='_ppc_on', draws='ppc_draws', width=lambda on: 4,
+          switch='ppc_stats', left_on='_ppc_on', draws='ppc_draws', width=lambda on: _lib.DRAWS_KINDS['ppc'].width,
           make=lambda problem, on, rows: PredictiveCheck.from_problem(problem, rows)),
     # (the probit psi is the modelling decision DESIGN 11 leaves open: this one and the three below)
     Draws('spatial_check', 'spatial_check', lambda value, problem, kept: spatial_flag(value) or None,
           python_step='the spatial residual check is formed by the device engine only',
           probit='the spatial residual check is not available for the probit model', rebuild='has no spatial residual check',
-          switch='moran_stats', left_on='_moran_on', draws='moran_draws', width=lambda on: 8,
+          switch='moran_stats', left_on='_moran_on', draws='moran_draws', width=lambda on: _lib.DRAWS_KINDS['moran'].width,
           make=lambda problem, on, rows: SpatialCheck.from_problem(problem, rows)),
     Accum('site_intervals', 'site_intervals', lambda value, problem, kept: interval_bins(value) or None, parsed=FIRST,
           python_step='site intervals are accumulated by the device engine only',

@@ -31,14 +31,14 @@ def assert_launched_only_while_on(feature):
     assert len(re.findall(r'uint32_t any = 0u;', src)) == 2        # Switches::any and switch_set's local
     assert re.search(r'struct Switches \{\s*uint32_t any = 0u;', src)
     assert re.search(r'struct AccumRun : Switches \{', src) and re.search(struct, src)
-    assert re.search(r'struct Spatial : CallRecord<long long>, Switches \{', src)
+    assert re.search(r'struct Spatial : Switches \{', src)
     # one assignment to a member `any` in the whole file, in switch_set ...
     assert re.findall(r'(?:\.|->)any = ([^;]+);', src) == ['any']
     body = re.search(r'static int switch_set\(occ_sampler \*s, occ_sampler::Switches &sw, int chain, bool on\)\n\{(.*?)\n\}\n', src, re.S).group(1)
     assert 'if (any != sw.any) destroy_graph(s);\n    sw.any = any;' in body
     # ... which all four features reach: the spatial check by itself, the accumulators through set_accum_state and accum()
     assert len(re.findall(r'\bswitch_set\(', src)) == 3
-    assert re.search(r'static int set_moran_state\(.*?\n    return switch_set\(s, sp, chain, on\);\n\}', src, re.S)
+    assert re.search(r'static int moran_switch\(.*?\n    return switch_set\(s, sp, chain, on\);\n\}', src, re.S)
     assert re.search(r'static int set_accum_state\(.*?occ_sampler::AccumRun &r = s->accum\(kind\);.*?\n    return switch_set\(s, r, chain, val != 0\);\n\}', src, re.S)
     assert re.search(r'AccumRun &accum\(int kind\) \{ return kind == ACC_HIST \? \(AccumRun &\)hist : kind == ACC_CONV \? \(AccumRun &\)conv : '
                      r'\(AccumRun &\)holdout; \}', src)

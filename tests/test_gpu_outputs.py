@@ -129,6 +129,70 @@ def test_outputs_switched_on_and_off_beside_each_other(workload):
         eng.close()
 
 
+def test_the_three_kinds_of_draws_beside_each_other():
+    """The draws of a call from one description (occ_draws.hpp): `all` has the regions, the predictive check and the spatial
+    check on for chain 0 and the regions alone for chain 1; only[x] has kind x alone, switched the same way.  run(7, 3), then
+    run(2, 1): the draws and alpha, beta, tau, z, eta of the four engines are bit-equal, `all` answers for every kind and
+    chain what only[x] answers, and the rows are the LAST call's.  A checkpoint holds the engine's switches (what the
+    methods set for every chain, not one chain's later change) and no rows: draws belong to a call."""
+    from occuspytial_amd import _lib
+    from occuspytial_amd._engine import Engine
+    prob, keys, starts = _icar()
+    ids = _ids(prob.n, 7)
+    kinds = tuple(_lib.DRAWS_KINDS)
+    assert kinds == ('region', 'ppc', 'moran')
+    off_for_chain_1 = ('ppc', 'moran')
+
+    def engine(on):
+        eng = Engine(prob, keys)
+        for c, st in enumerate(starts):
+            eng.set_start(c, **st)
+        for kind in on:
+            k = _lib.DRAWS_KINDS[kind]
+            if k.input:
+                eng.regions(ids)
+            getattr(eng, k.fields[-2])(True)
+            if kind in off_for_chain_1:
+                eng.set(k.fields[-2], 0.0, 1)
+        return eng
+    every, only = engine(kinds), {x: engine((x,)) for x in kinds}
+    width = {'region': 7, 'ppc': 4, 'moran': 8}
+    for n_iter, burnin in ((7, 3), (2, 1)):
+        keep = n_iter - burnin
+        draws = every.run(n_iter, burnin)
+        for x, other in only.items():
+            for u, v in zip(draws, other.run(n_iter, burnin)):
+                assert np.array_equal(u, v), (x, 'recorded draws')
+            for c in range(2):
+                for nm in STATE:
+                    assert np.array_equal(every.get(nm, c), other.get(nm, c)), (x, nm, c)
+        for x in kinds:
+            rows_name = _lib.DRAWS_KINDS[x].fields[-1]
+            for c in range(2):
+                got, want = getattr(every, rows_name)(c), getattr(only[x], rows_name)(c)
+                on = c == 0 or x not in off_for_chain_1
+                assert got.shape == ((keep if on else 0), width[x]), (n_iter, x, c, got.shape)
+                assert got.shape == want.shape and np.array_equal(got, want), (n_iter, x, c)
+                assert every.get(rows_name, c).size == (keep * width[x] if on else 0)
+                assert every.get(_lib.DRAWS_KINDS[x].fields[-2], c)[0] == float(on)
+        assert np.any(every.region_draws(0)) and np.any(every.ppc_draws(0)) and np.any(every.moran_draws(0))
+    ckpt = every.checkpoint()
+    assert np.array_equal(ckpt['region_id'], np.tile(ids, (2, 1)))
+    for x in kinds:
+        assert np.array_equal(ckpt[_lib.DRAWS_KINDS[x].fields[-2]], np.ones(2)) and _lib.DRAWS_KINDS[x].fields[-1] not in ckpt
+    fresh = Engine(prob, keys)
+    fresh.restore(ckpt)
+    for x in kinds:
+        k = _lib.DRAWS_KINDS[x]
+        assert getattr(fresh, k.on) is True
+        for c in range(2):
+            assert fresh.get(k.fields[-2], c)[0] == 1.0
+            assert getattr(fresh, k.fields[-1])(c).shape == (0, width[x]), (x, c)
+    assert np.array_equal(fresh.get('region_id'), ids)
+    for eng in [every, fresh] + list(only.values()):
+        eng.close()
+
+
 def test_probit_region_switch_on_and_off():
     """The probit handle's one output, five run(10, 0) calls (its captured graph holds eight iterations, so every call
     replays it once and steps twice): off, both chains on, chain 0 off while chain 1 stays on, both off, both on.  Draws
