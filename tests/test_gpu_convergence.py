@@ -12,13 +12,12 @@ d d + s2 alone (4 N 2^-53 relative covers one rounding per addition); psi is hel
 Workloads: those of tests/test_gpu_intervals.py.  Every test runs under its own time limit.
 """
 import ctypes
-import signal
 
 import numpy as np
 import pytest
 
+from ._outputs_gpu import engine_with, time_limit as _time_limit, two_calls  # noqa: F401 (autouse in this module)
 from .test_gpu_intervals import WORKLOADS, _psi, _sampler
-from .test_gpu_intervals import _engine as _other_engine
 from .test_gpu_parity import KEY, _problem_from_golden, _random_start
 from .test_gpu_ppc import SCHED_KEYS
 from .test_gpu_site_summaries import _rsr_problem, _workload_a
@@ -29,24 +28,9 @@ CNT, PSI, ETA = 0, 1, 6
 REF, S1, S2, RUN, BSQ = range(5)
 
 
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """300 s per test (each takes seconds)."""
-    def late(signum, frame):
-        raise TimeoutError('a test of test_gpu_convergence.py ran past its time limit')
-    old = signal.signal(signal.SIGALRM, late)
-    signal.alarm(300)
-    yield
-    signal.alarm(0)
-    signal.signal(signal.SIGALRM, old)
-
-
 # ------------------------------------------------------------------ helpers
 def _engine(prob, keys, starts, L=5, **kw):
-    eng = _other_engine(prob, keys, starts, bins=kw.pop('bins', 0), **kw)
-    if L:
-        eng.conv_stats(L)
-    return eng
+    return engine_with(prob, keys, starts, conv=L, **kw)
 
 
 def _sums(eng):
@@ -55,12 +39,7 @@ def _sums(eng):
 
 def _two_calls(prob, keys, starts, split=((33, 4), (10, 0)), **kw):
     """run(33, 4) then run(10, 0) -> per chain the sums of the 39 iterations past the calls' burn-in."""
-    eng = _engine(prob, keys, starts, **kw)
-    for n_iter, burnin in split:
-        eng.run(n_iter, burnin)
-    out = _sums(eng)
-    eng.close()
-    return out
+    return two_calls(lambda: _engine(prob, keys, starts, **kw), _sums, split)
 
 
 def _same(a, b):

@@ -10,31 +10,19 @@ surveyed in the engine's problem: every workload here takes sites out of a gener
 leaves unsurveyed) and gives them withheld visits of ragged lengths.  Every test runs under its own time limit.
 """
 import ctypes
-import signal
 
 import numpy as np
 import pytest
 from scipy import sparse
 from scipy.special import expit
 
+from ._outputs_gpu import engine_with, time_limit as _time_limit, two_calls  # noqa: F401 (autouse in this module)
 from .conftest import load_golden
 from .test_gpu_parity import KEY, _random_start
 from .test_gpu_ppc import SCHED_KEYS
 
 pytestmark = pytest.mark.gpu
 CNT, LIK, LOG, LOG2, PD = range(5)
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """300 s per test (each takes seconds)."""
-    def late(signum, frame):
-        raise TimeoutError('a test of test_gpu_holdout.py ran past its time limit')
-    old = signal.signal(signal.SIGALRM, late)
-    signal.alarm(300)
-    yield
-    signal.alarm(0)
-    signal.signal(signal.SIGALRM, old)
 
 
 # ------------------------------------------------------------------ workloads
@@ -114,30 +102,8 @@ def _workload_a(chains=2):
 
 
 # ------------------------------------------------------------------ helpers
-def _engine(prob, keys, starts, Wt, yt, on=True, site=False, ll=False, ids=None, ppc=False, moran=False, bins=0, conv=0):
-    from occuspytial_amd._engine import Engine
-    eng = Engine(prob, keys)
-    for c, st in enumerate(starts):
-        eng.set_start(c, **st)
-    if site:
-        eng.site_stats(True)
-    if ll:
-        eng.loglik_stats(True)
-    if ids is not None:
-        eng.regions(ids)
-        eng.region_stats(True)
-    if ppc:
-        eng.ppc_stats(True)
-    if moran:
-        eng.moran_stats(True)
-    if bins:
-        eng.hist_stats(bins)
-    if conv:
-        eng.conv_stats(conv)
-    if on:
-        eng.holdout_data(Wt, yt)
-        eng.holdout_stats(True)
-    return eng
+def _engine(prob, keys, starts, Wt, yt, on=True, **kw):
+    return engine_with(prob, keys, starts, holdout=(Wt, yt) if on else None, **kw)
 
 
 def _sums(eng):
@@ -146,12 +112,7 @@ def _sums(eng):
 
 def _two_calls(work, split=((33, 4), (10, 0)), **kw):
     """run(33, 4) then run(10, 0) -> per chain the sums of the 39 iterations past the calls' burn-in."""
-    eng = _engine(*work, **kw)
-    for n_iter, burnin in split:
-        eng.run(n_iter, burnin)
-    out = _sums(eng)
-    eng.close()
-    return out
+    return two_calls(lambda: _engine(*work, **kw), _sums, split)
 
 
 def _same(a, b):

@@ -13,12 +13,12 @@ each kind (the generic kernels), the reduced-rank model at 40 columns.  Every te
 """
 import ctypes
 import itertools
-import signal
 
 import numpy as np
 import pytest
 from scipy.special import expit
 
+from ._outputs_gpu import engine_with, time_limit as _time_limit, two_calls  # noqa: F401 (autouse in this module)
 from .test_gpu_parity import KEY, _problem_from_golden, _random_start
 from .test_gpu_ppc import SCHED_KEYS
 from .test_gpu_site_summaries import _rsr_problem, _workload_a, _workload_g
@@ -27,38 +27,9 @@ pytestmark = pytest.mark.gpu
 EDGE = 1e-11
 
 
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """300 s per test (each takes seconds)."""
-    def late(signum, frame):
-        raise TimeoutError('a test of test_gpu_intervals.py ran past its time limit')
-    old = signal.signal(signal.SIGALRM, late)
-    signal.alarm(300)
-    yield
-    signal.alarm(0)
-    signal.signal(signal.SIGALRM, old)
-
-
 # ------------------------------------------------------------------ helpers
-def _engine(prob, keys, starts, bins=64, site=False, ll=False, ids=None, ppc=False, moran=False):
-    from occuspytial_amd._engine import Engine
-    eng = Engine(prob, keys)
-    for c, st in enumerate(starts):
-        eng.set_start(c, **st)
-    if site:
-        eng.site_stats(True)
-    if ll:
-        eng.loglik_stats(True)
-    if ids is not None:
-        eng.regions(ids)
-        eng.region_stats(True)
-    if ppc:
-        eng.ppc_stats(True)
-    if moran:
-        eng.moran_stats(True)
-    if bins:
-        eng.hist_stats(bins)
-    return eng
+def _engine(prob, keys, starts, bins=64, **kw):
+    return engine_with(prob, keys, starts, bins=bins, **kw)
 
 
 def _hists(eng):
@@ -67,12 +38,7 @@ def _hists(eng):
 
 def _two_calls(prob, keys, starts, split=((33, 4), (10, 0)), **kw):
     """run(33, 4) then run(10, 0) -> per chain the histograms of the 39 iterations past the calls' burn-in."""
-    eng = _engine(prob, keys, starts, **kw)
-    for n_iter, burnin in split:
-        eng.run(n_iter, burnin)
-    out = _hists(eng)
-    eng.close()
-    return out
+    return two_calls(lambda: _engine(prob, keys, starts, **kw), _hists, split)
 
 
 def _same(a, b):

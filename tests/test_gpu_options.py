@@ -2,11 +2,11 @@
 those of a plain call, every output is the one of a call that asks for it alone, and ``resume`` ends where an uninterrupted run
 ends.  ``LogitICARGibbs`` on the 30x40 lattice with every fourth site withheld, 3 chains, 7 regions.  Nothing here is
 statistical: every comparison is equality."""
-import signal
 
 import numpy as np
 import pytest
 
+from ._outputs_gpu import time_limit as _time_limit  # noqa: F401 (autouse in this module)
 from .test_gpu_holdout import _sampler
 from .test_gpu_regions import _ids
 
@@ -15,18 +15,6 @@ pytestmark = pytest.mark.gpu
 RESULT = dict(site_summaries='sites', waic='waic', regions='regions', ppc='ppc', spatial_check='spatial_check',
               site_intervals='site_intervals', site_diagnostics='site_diagnostics', holdout='holdout')
 PER_CALL = ('regions', 'ppc', 'spatial_check')      # rows of the draws a call keeps; the other five accumulate across resume
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """300 s per test (each takes seconds)."""
-    def late(signum, frame):
-        raise TimeoutError('a test of test_gpu_options.py ran past its time limit')
-    old = signal.signal(signal.SIGALRM, late)
-    signal.alarm(300)
-    yield
-    signal.alarm(0)
-    signal.signal(signal.SIGALRM, old)
 
 
 def _asked(held, diagnostics=True):

@@ -12,8 +12,9 @@ import signal
 import numpy as np
 import pytest
 
+from ._outputs_gpu import engine_with
 from .test_gpu_parity import KEY, _random_start
-from .test_gpu_regions import _engine as _probit_engine, _ids, _probit_problem
+from .test_gpu_regions import _ids, _probit_problem
 from .test_gpu_site_summaries import _workload_g
 
 pytestmark = pytest.mark.gpu
@@ -31,6 +32,10 @@ def _time_limit():
     yield
     signal.alarm(0)
     signal.signal(signal.SIGALRM, old)
+
+
+def _probit_engine(prob, keys, starts, ids=None, on=True):
+    return engine_with(prob, keys, starts, ids=ids, region_on=on)
 
 
 def _icar():

@@ -8,12 +8,12 @@ the two discrepancies, within one quantum per surveyed site with z = 1.  Workloa
 and the ragged queen fixtures; G, 17x19 with nine covariates of each kind (the generic kernels); the reduced-rank model on
 both solve paths.  Every test runs under its own time limit (``_time_limit``).
 """
-import signal
 
 import numpy as np
 import pytest
 from scipy.special import expit
 
+from ._outputs_gpu import engine_with, time_limit as _time_limit, two_calls  # noqa: F401 (autouse in this module)
 from .test_gpu_parity import KEY, _problem_from_golden, _random_start
 from .test_gpu_site_summaries import _rsr_problem, _workload_a, _workload_g
 
@@ -21,34 +21,9 @@ pytestmark = pytest.mark.gpu
 STREAM_PPC = 13
 
 
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """300 s per test (the longest, the 450-iteration run, the fallbacks and the decision, take seconds)."""
-    def late(signum, frame):
-        raise TimeoutError('a test of test_gpu_ppc.py ran past its time limit')
-    old = signal.signal(signal.SIGALRM, late)
-    signal.alarm(300)
-    yield
-    signal.alarm(0)
-    signal.signal(signal.SIGALRM, old)
-
-
 # ------------------------------------------------------------------ helpers
-def _engine(prob, keys, starts, on=True, site=False, ll=False, ids=None):
-    from occuspytial_amd._engine import Engine
-    eng = Engine(prob, keys)
-    for c, st in enumerate(starts):
-        eng.set_start(c, **st)
-    if site:
-        eng.site_stats(True)
-    if ll:
-        eng.loglik_stats(True)
-    if ids is not None:
-        eng.regions(ids)
-        eng.region_stats(True)
-    if on:
-        eng.ppc_stats(True)
-    return eng
+def _engine(prob, keys, starts, on=True, **kw):
+    return engine_with(prob, keys, starts, ppc=on, **kw)
 
 
 def _rows(eng):
@@ -57,13 +32,7 @@ def _rows(eng):
 
 def _two_calls(prob, keys, starts, split=((33, 4), (10, 0)), **kw):
     """run(33, 4) then run(10, 0) -> per chain the 39 recorded rows, (39, 4)."""
-    eng = _engine(prob, keys, starts, **kw)
-    parts = []
-    for n_iter, burnin in split:
-        eng.run(n_iter, burnin)
-        parts.append(_rows(eng))
-    eng.close()
-    return [np.concatenate([p[c] for p in parts]) for c in range(len(keys))]
+    return two_calls(lambda: _engine(prob, keys, starts, **kw), _rows, split, per_call=True)
 
 
 def _same(a, b):

@@ -6,27 +6,15 @@ sums of z that were merged before (``site_z``).  Workloads: A, the 30x40 lattice
 nine covariates of each kind (the generic kernels); the reduced-rank model on both solve paths (40 and 160 basis columns);
 ``ProbitRSRGibbs``.  Every test runs under its own time limit (``_time_limit``), and the engine's own host waits have theirs.
 """
-import signal
 
 import numpy as np
 import pytest
 
+from ._outputs_gpu import engine_with, time_limit as _time_limit, two_calls  # noqa: F401 (autouse in this module)
 from .test_gpu_parity import KEY, _problem_from_golden, _random_start
 from .test_gpu_site_summaries import _rsr_problem, _workload_a, _workload_g
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def _time_limit():
-    """300 s per test (the longest, the 450-iteration run and the fallbacks, take seconds)."""
-    def late(signum, frame):
-        raise TimeoutError('a test of test_gpu_regions.py ran past its time limit')
-    old = signal.signal(signal.SIGALRM, late)
-    signal.alarm(300)
-    yield
-    signal.alarm(0)
-    signal.signal(signal.SIGALRM, old)
 
 
 # ------------------------------------------------------------------ helpers
@@ -54,24 +42,8 @@ def _detected(prob):
     return seen
 
 
-def _engine(prob, keys, starts, ids=None, on=True, site=False, ll=False):
-    from occuspytial_amd._engine import Engine
-    eng = Engine(prob, keys)
-    for c, st in enumerate(starts):
-        st = dict(st)
-        eps = st.pop('eps', None)
-        eng.set_start(c, **st)
-        if eps is not None:
-            eng.set('eps', eps, c)
-    if site:
-        eng.site_stats(True)
-    if ll:
-        eng.loglik_stats(True)
-    if ids is not None:
-        eng.regions(ids)
-        if on:
-            eng.region_stats(True)
-    return eng
+def _engine(prob, keys, starts, ids=None, on=True, **kw):
+    return engine_with(prob, keys, starts, ids=ids, region_on=on, **kw)
 
 
 def _probit_problem(chains=2, q=12):
@@ -93,13 +65,7 @@ def _rows(eng):
 
 def _two_calls(prob, keys, starts, ids, **kw):
     """run(33, 4) then run(10, 0) -> per chain the 39 recorded rows, (39, G)."""
-    eng = _engine(prob, keys, starts, ids, **kw)
-    eng.run(33, 4)
-    first = _rows(eng)
-    eng.run(10, 0)
-    out = [np.concatenate([a, b]) for a, b in zip(first, _rows(eng))]
-    eng.close()
-    return out
+    return two_calls(lambda: _engine(prob, keys, starts, ids, **kw), _rows, per_call=True)
 
 
 def _same(a, b):

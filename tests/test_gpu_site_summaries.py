@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 from scipy.special import expit
 
+from ._outputs_gpu import engine_with, two_calls
 from .test_gpu_parity import KEY, _problem_from_golden, _random_start
 
 pytestmark = pytest.mark.gpu
@@ -68,13 +69,7 @@ def _rsr_problem(q):
 
 
 def _engine(prob, keys, starts, on=True):
-    from occuspytial_amd._engine import Engine
-    eng = Engine(prob, keys)
-    for c, st in enumerate(starts):
-        eng.set_start(c, **st)
-    if on:
-        eng.site_stats(True)
-    return eng
+    return engine_with(prob, keys, starts, site=on)
 
 
 # ------------------------------------------------------------------ 1 / 7: against an independent restatement
@@ -218,12 +213,7 @@ def test_reduced_rank_large_basis_graph_replay_equals_eager_stepping_bitwise():
 
 # ------------------------------------------------------------------ 4: every scheduling mode
 def _two_calls(prob, keys, starts):
-    eng = _engine(prob, keys, starts)
-    eng.run(33, 4)
-    eng.run(10, 0)
-    out = _read_all(eng)
-    eng.close()
-    return out
+    return two_calls(lambda: _engine(prob, keys, starts), _read_all)
 
 
 SCHED_KEYS = ('OCC_EVENT_SYNC', 'OCC_STREAM_EVENTS', 'OCC_CU_SPLIT', 'OCC_NO_SIDE_STREAM', 'OCC_EAGER_ONLY', 'OCC_NO_PERSISTENT',

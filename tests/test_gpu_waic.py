@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 from scipy.special import expit
 
+from ._outputs_gpu import engine_with, two_calls
 from .test_gpu_parity import KEY, _problem_from_golden, _random_start
 from .test_gpu_site_summaries import SUMS as SITE_SUMS
 from .test_gpu_site_summaries import _read_all as _read_all_site
@@ -38,15 +39,7 @@ def _same(a, b):
 
 
 def _engine(prob, keys, starts, ll=True, site=False):
-    from occuspytial_amd._engine import Engine
-    eng = Engine(prob, keys)
-    for c, st in enumerate(starts):
-        eng.set_start(c, **st)
-    if site:
-        eng.site_stats(True)
-    if ll:
-        eng.loglik_stats(True)
-    return eng
+    return engine_with(prob, keys, starts, site=site, ll=ll)
 
 
 def _masks(prob):
@@ -226,12 +219,7 @@ def test_reduced_rank_graph_replay_equals_eager_stepping_bitwise():
 
 
 def _two_calls(prob, keys, starts, site=False):
-    eng = _engine(prob, keys, starts, site=site)
-    eng.run(33, 4)
-    eng.run(10, 0)
-    out = _read_all(eng), (_read_all_site(eng) if site else None)
-    eng.close()
-    return out
+    return two_calls(lambda: _engine(prob, keys, starts, site=site), lambda eng: (_read_all(eng), _read_all_site(eng) if site else None))
 
 
 SCHED_KEYS = ('OCC_EVENT_SYNC', 'OCC_STREAM_EVENTS', 'OCC_CU_SPLIT', 'OCC_NO_SIDE_STREAM', 'OCC_EAGER_ONLY', 'OCC_NO_PERSISTENT',
