@@ -186,6 +186,22 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  * twice; occ_step, occ_profile and the occ_cond_* entry points never count.  alpha, beta, tau, eta, z and the site_* and
  * ll_* sums are bit-identical with the switch on or off.
  *
+ * Sum-to-zero per connected component (ICAR model): on a graph of k > 1 connected components the null space of Q has dimension
+ * k, and the ICAR model centres eta on every component, not once over all sites.
+ *   component_id(n)       the HANDLE's components, set and read through any valid chain index: whole numbers in [0, n), equal
+ *                         numbers = one component.  Validated as a whole: another value is OCC_E_BADARG and nothing changes.
+ *                         Settable only before the handle's first iteration (OCC_E_STATE afterwards); reading it before it was
+ *                         set: OCC_E_STATE.  A probit or reduced-rank handle answers OCC_E_STATE: its eta = K theta carries no
+ *                         constraint.
+ * With more than one component a correction pass follows every solve (occ_run, occ_step, occ_cond_eta, and the real iterations
+ * occ_profile runs on a fused handle -- whose kernel-by-kernel replays afterwards leave every chain mid-solve, as under the
+ * global constraint: eta after occ_profile is no draw of either model, re-start the chains): from the solve's
+ * x = Lambda^-1 y and z = Lambda^-1 1, eta_i = x_i + a_c z_i with a_c = -(sum of x over i's component) / (sum of z over it),
+ * exactly 0.0 at a component of one site, and beta's partial sums are formed again from that eta.  The sums are added in an
+ * order fixed by the labels alone: the same bits on every path and after a resume.  With one component nothing changes: no
+ * launch, no allocation, the same bits as without the name.  occ_cond_beta is unchanged; tau_shape is the caller's
+ * (0.5 + 0.5 (n - k) for this model).
+ *
  * Posterior predictive check of the detection histories (logit models; ICAR and reduced rank), conditional on z: per KEPT draw
  * of occ_run -- row t as above -- of a chain whose switch is on, the z update replicates the detections of every surveyed
  * site i, visit rows r0 <= r < r1, from alpha of the iteration and the NEW z_i:

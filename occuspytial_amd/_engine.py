@@ -52,18 +52,26 @@ class ProblemMeta:
     arrays themselves arrive on its device by broadcast (start values, output shapes)."""
 
     FIELDS = ('n', 'p', 'q', 'S', 'R', 'tau_rate', 'tau_shape', 'a_mu', 'a_prec', 'b_mu', 'b_prec')
+    OPTIONAL = ('constraint', 'n_components', 'component_labels')   # absent: the global constraint
     rsr = None
+    constraint, n_components, component_labels = 'global', 1, None
 
     def __init__(self, **kw):
         for f in self.FIELDS:
             setattr(self, f, kw[f])
+        for f in self.OPTIONAL:
+            if f in kw:
+                setattr(self, f, kw[f])
 
     @classmethod
     def of(cls, prob):
-        return cls(**{f: getattr(prob, f) for f in cls.FIELDS})
+        return cls(**{f: getattr(prob, f) for f in cls.FIELDS + cls.OPTIONAL if hasattr(prob, f)})
 
     def to_dict(self):
-        return {f: getattr(self, f) for f in self.FIELDS}
+        d = {f: getattr(self, f) for f in self.FIELDS}
+        if self.constraint != 'global':
+            d.update({f: getattr(self, f) for f in self.OPTIONAL})
+        return d
 
 
 _LIVE = weakref.WeakSet()   # engines not yet closed: closed at interpreter exit, before the library's own exit hook runs
@@ -132,6 +140,17 @@ class Engine:
         self._holdout = None
         self._holdout_on = False
         _LIVE.add(self)
+        # constraint='component' on a graph of more than one connected component: the handle gets the labels before its first
+        # iteration (with one component, or under 'global', no call about them reaches the library)
+        if getattr(prob, 'constraint', 'global') == 'component' and getattr(prob, 'n_components', 1) > 1:
+            try:
+                self.set('component_id', np.asarray(prob.component_labels, dtype=np.float64), 0)
+            except Exception as exc:
+                self.close()   # (whatever the refusal: no half-made engine is left open)
+                if isinstance(exc, ValueError) and 'unknown state name' in str(exc):
+                    # a stale build, or a stand-in library that does not know the state name
+                    raise ValueError(f"the loaded engine library has no constraint='component' ({exc}): rebuild it") from None
+                raise   # (a library that knows the name and refuses: its own words, e.g. for a reduced-rank problem)
         return self
 
     @classmethod
@@ -151,7 +170,17 @@ class Engine:
         code = lib.occ_create_group(C.byref(pb), G, dev, cnt, karr, hs)
         _lib.raise_for(code, None)
         del keep
-        return [cls.__new__(cls)._adopt(lib, C.c_void_p(hs[g]), prob, keys_per_device[g], devices[g]) for g in range(G)]
+        engines = []
+        try:
+            for g in range(G):
+                engines.append(cls.__new__(cls)._adopt(lib, C.c_void_p(hs[g]), prob, keys_per_device[g], devices[g]))
+        except Exception:   # (a handle refused the problem's mode: none of the group's handles stays open)
+            for e in engines:
+                e.close()
+            for g in range(len(engines) + 1, G):
+                lib.occ_destroy(C.c_void_p(hs[g]))
+            raise
+        return engines
 
     @classmethod
     def distributed(cls, prob, comm, keys, root=0):

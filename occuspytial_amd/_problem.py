@@ -11,6 +11,8 @@ import numpy as np
 from scipy import sparse
 from scipy.linalg import solve_triangular
 
+from .graph import CONSTRAINTS, centre, components
+
 MAX_COVARIATES = 32  # limit of the engine (up to 8: register-resident accumulators; beyond: its generic kernels)
 DENSE_PRIOR_MAX_SITES = 16384  # the reference-form prior draw keeps an n x (n - 1) factor: 2 GB at this size
 
@@ -23,7 +25,9 @@ class FlatProblem:
     ``not_surveyed``.
     """
 
-    def __init__(self, Q, W, X, y, hparams=None, check_singular=True, prior_draw='auto'):
+    def __init__(self, Q, W, X, y, hparams=None, check_singular=True, prior_draw='auto', constraint='global'):
+        if constraint not in CONSTRAINTS:
+            raise ValueError("constraint must be 'global' or 'component'")
         X = np.ascontiguousarray(X, dtype=np.float64)
         if X.ndim != 2:
             raise ValueError('X must be a 2-D array')
@@ -55,6 +59,11 @@ class FlatProblem:
         if prior_draw == 'dense':
             self.prior_factor = dense_prior_factor(Qc)
         self.Q = Qc
+        # 'global': the reference's one constraint 1'eta = 0 (gibbs/logit.py:97).  'component': one per connected component of
+        # Q's graph -- with k of them the null space of Q has dimension k ("Sum-to-zero per connected component");
+        # n_components and component_labels are set for it alone, and with k = 1 everything below takes the global path.
+        self.constraint = constraint
+        self.n_components, self.component_labels = components(Qc) if constraint == 'component' else (1, None)
 
         if list(W.keys()) != list(y.keys()):
             if set(W.keys()) != set(y.keys()):
@@ -170,6 +179,8 @@ class FlatProblem:
         d['Q_indices'] = np.ascontiguousarray(self.Q.indices, dtype=np.int64)
         d['Q_data'] = np.ascontiguousarray(self.Q.data, dtype=np.float64)
         d['scalars'] = np.array([self.tau_rate, self.tau_shape], dtype=np.float64)
+        if self.constraint == 'component':   # (optional key: a dict without it is the global constraint)
+            d['component_labels'] = np.ascontiguousarray(self.component_labels, dtype=np.int32)
         if self.rsr is not None:
             d['rsr_K'], d['rsr_Q'], d['rsr_E'] = self.rsr['K'], self.rsr['Q'], self.rsr['E']
         if self.prior_factor is not None:
@@ -188,6 +199,11 @@ class FlatProblem:
         self.R = int(self.site_ptr[-1])
         self.Q = sparse.csr_matrix((d['Q_data'], d['Q_indices'], d['Q_indptr']), shape=(self.n, self.n))
         self.tau_rate, self.tau_shape = (float(v) for v in d['scalars'])
+        self.constraint, self.n_components, self.component_labels = 'global', 1, None
+        if 'component_labels' in d:
+            self.constraint = 'component'
+            self.component_labels = np.ascontiguousarray(d['component_labels'], dtype=np.int32)
+            self.n_components = int(self.component_labels.max()) + 1
         self.surveyed = self.site_id.tolist()
         flag = self.obs_site.astype(bool)
         self.obs = self.site_id[flag].tolist()
@@ -208,7 +224,7 @@ class FlatProblem:
         # defaults: gibbs/base.py:177-186
         hp = {
             'tau_rate': 0.005,
-            'tau_shape': 0.5 + 0.5 * (self.n - 1),
+            'tau_shape': 0.5 + 0.5 * (self.n - self.n_components),   # the rank of Q (one component: base.py:179)
             'a_mu': np.zeros(self.q),
             'a_prec': np.eye(self.q) / 10,
             'b_mu': np.zeros(self.p),
@@ -288,12 +304,16 @@ def dense_prior_factor(Q):
 
 def default_start(rng, prob):
     """Default starting values of one chain, drawn from ``rng`` in the reference's order
-    (``gibbs/base.py:199-212``): tau ~ Gamma(0.5, scale 1/tau_rate); eta ~ N(0, I) centred; alpha and
+    (``gibbs/base.py:199-212``): tau ~ Gamma(0.5, scale 1/tau_rate); eta ~ N(0, I) centred (under
+    ``constraint='component'`` on every connected component); alpha and
     beta from ``multivariate_normal(mu, 100 * prec, method='cholesky')`` (``100 * prec`` is used as
     a covariance there)."""
     tau = rng.gamma(0.5, 1 / prob.tau_rate)
     eta = rng.standard_normal(prob.n)
-    eta = eta - eta.mean()
+    if getattr(prob, 'n_components', 1) > 1:   # the same variates, centred on every component
+        eta = centre(eta, prob.component_labels)
+    else:
+        eta = eta - eta.mean()
     alpha = rng.multivariate_normal(prob.a_mu, 100 * prob.a_prec, method='cholesky')
     beta = rng.multivariate_normal(prob.b_mu, 100 * prob.b_prec, method='cholesky')
     return dict(alpha=alpha, beta=beta, tau=tau, eta=eta)

@@ -21,6 +21,7 @@
 
 #include "occ_comm.hpp"
 #include "occ_tiles.hpp"
+#include "occ_comp.hpp"
 #include "occ_rsr.hpp"
 #include "occ_probit.hpp"
 #include "occ_spatial.hpp"
@@ -176,6 +177,16 @@ struct occ_sampler {
         uint32_t *pb_on_dev = nullptr;
         uint32_t **pb_rec = nullptr;
     } regions;
+    // Sum-to-zero per connected component (state name component_id; ICAR model): the labels as they were set and the tables
+    // built from them (occ_comp_plan.hpp) on the device; args: the kernels' argument block with their device copies (occ_comp.hpp).  More than
+    // one component: the correction pass stands behind the solve of every sequence (comp_on; the block travels by value in the
+    // captured launches: setting the labels drops them).
+    struct Components {
+        std::vector<int32_t> id;
+        CompArgs args{};
+        std::vector<void *> dev;  // the device arrays behind args: freed when the labels are set again
+    } comp;
+    bool comp_on() const { return comp.args.k > 1; }
     // The switches of a feature whose kernels stand behind the z update: a word of the handle per chain (on, on_dev), not a
     // bit of ChainScalars::site_on; any: their OR, which decides whether the kernels are launched (baked into captured graphs:
     // a change drops them).  switch_alloc / switch_set.
@@ -565,7 +576,7 @@ KernelEI pick_omega_a(int q)
 static const char *kind_name(int kind)
 {
     static const char *names[] = {"k_omega_b", "k_noise", "k_eta_init", "k_minres", "k_beta_partial", "k_omega_a", "k_alpha_draw",
-                                  "k_z_ob", "k_iter", "k_gate", "k_rsr_gram", "k_rsr_solve", "k_rsr_eta_beta"};
+                                  "k_z_ob", "k_iter", "k_gate", "k_rsr_gram", "k_rsr_solve", "k_rsr_eta_beta", "k_comp_part", "k_comp_coef", "k_comp_eta", "k_beta_sums"};
     return (kind >= 0 && kind < (int)(sizeof(names) / sizeof(names[0]))) ? names[kind] : "kernel";
 }
 
@@ -634,6 +645,12 @@ int launch_kind(occ_sampler *s, hipStream_t st, int kind, int e, int extra = 0)
             }
             break;
         case K_RSR_ETA_BETA: hipLaunchKernelGGL(pick_rsr_eta_beta(c.p), gs, blk, 0, st, s->rsr, OCC_ARGS); break;
+        // the per-component correction behind the solve (occ_comp.hpp): chunks, components, eta; then beta's partial sums from
+        // that eta, by the kernel and in the geometry of occ_cond_beta (= k_beta_partial's)
+        case K_COMP_PART: comp_launch(s->comp.args, s->ctx.sc, COMP_PART, 0, c.C, e, st); break;
+        case K_COMP_COEF: comp_launch(s->comp.args, s->ctx.sc, COMP_COEF, 0, c.C, e, st); break;
+        case K_COMP_ETA: comp_launch(s->comp.args, s->ctx.sc, COMP_ETA, 0, c.C, e, st); break;
+        case K_COMP_BETA: hipLaunchKernelGGL(OCC_PICK_P(k_beta_sums, tp), gs, blk, lds_p, st, OCC_ARGS); break;
         case K_ITER: {
             // k_tiles: eight bands of B + 1 workgroups per chain (the surplus one of a band returns at once); one XCD per
             // chain: eight chains (one per XCD) per launch, more chains: the next eight right behind; any placement
@@ -791,7 +808,7 @@ int walk(occ_sampler *s, hipStream_t st, const SeqParts &parts, SeqSolve sv, int
         seq_launches(parts.part[i], sv, e, cap, gate, [&](const SeqLaunch &l) {
             if (rc == OCC_OK && l.extra != EXTRA_HOST_WATCHED) LAUNCH(s, st, l.kind, l.e, l.extra == EXTRA_K_LAST ? k_last : l.extra);
             else if (rc == OCC_OK && (rc = eager_krylov(s, 1, &k_last)) == OCC_OK) s->calib_max = std::max(s->calib_max, k_last - 3);
-        });
+        }, s->comp_on());
     return rc;
 }
 
@@ -3217,6 +3234,70 @@ static int set_region_id(occ_sampler *s, const double *in, int64_t len)
     }
     return OCC_OK;
 }
+// ---- occ_get_state / occ_set_state of component_id (n): the HANDLE's connected components, through any chain index ---------
+// Whole numbers in [0, n), equal numbers = one component; validated as a whole (OCC_E_BADARG).  Settable only before the
+// handle's first iteration (OCC_E_STATE afterwards): the constraint is part of the model a chain samples.  More than one
+// component: the correction pass (occ_comp.hpp) stands behind every solve from now on; one: nothing changes.  A probit or
+// reduced-rank handle answers OCC_E_STATE: its eta = K theta carries no constraint.
+static const char *component_refusal(const occ_sampler *s)
+{
+    return s->probit || s->rsr.m > 0 ? "component_id belongs to the ICAR model: the reduced-rank and probit models' eta = K theta carries no sum-to-zero constraint" : nullptr;
+}
+static int set_component_id(occ_sampler *s, const double *in, int64_t len)
+{
+    if (const char *why = component_refusal(s)) return set_error(s, OCC_E_STATE, why);
+    const Ctx &c = s->ctx;
+    const size_t n = (size_t)c.n;
+    if (s->graph_launches != 0 || s->eager_iterations != 0)
+        return set_error(s, OCC_E_STATE, "component_id is set before the handle's first iteration");
+    if ((size_t)len != n) return set_error(s, OCC_E_STATE, "wrong length");
+    std::vector<int32_t> id(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!(in[i] >= 0.0 && in[i] < (double)n) || in[i] != std::floor(in[i]))
+            return set_error(s, OCC_E_BADARG, "component_id holds whole numbers from 0 to n - 1");
+        id[i] = (int32_t)in[i];
+    }
+    CompTables T;
+    std::string why;
+    if (!comp_tables_build(id, &T, &why)) return set_error(s, OCC_E_BADARG, why.c_str());
+    WAIT_TRY(s->stream);
+    WAIT_TRY(s->side);
+    destroy_graph(s);  // (the pass is part of what a graph holds)
+    for (void *p : s->comp.dev) {  // the tables of an earlier call (both streams are idle)
+        s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), p), s->allocs.end());
+        (void)hipFree(p);
+    }
+    s->comp.dev.clear();
+    s->comp.args = CompArgs{};
+    s->comp.id.clear();
+    int rc;
+    CompArgs a{};
+    a.n = c.n; a.k = T.k; a.nchunk = T.nchunk(); a.nheavy = (int)T.heavy.size();
+    a.Xv = c.Xv; a.eta = c.eta;
+    auto put = [&](const auto &v, auto **dev) -> int {
+        using E = std::remove_cv_t<std::remove_pointer_t<std::remove_pointer_t<decltype(dev)>>>;
+        E *d = nullptr;
+        if (int r = dev_alloc(s, &d, std::max<size_t>(v.size(), 1))) return r;
+        s->comp.dev.push_back(d);
+        if (!v.empty()) HIP_TRY(copy_on(s, d, v.data(), sizeof(E) * v.size(), hipMemcpyHostToDevice));
+        *dev = d;
+        return OCC_OK;
+    };
+    if (T.k > 1) {
+        if ((rc = put(T.list, &a.list)) || (rc = put(T.chunk_start, &a.chunk_start)) || (rc = put(T.comp_chunk, &a.comp_chunk)) ||
+            (rc = put(T.heavy, &a.heavy)) || (rc = put(T.site_lab, &a.site_lab)))
+            return rc;
+        if ((rc = dev_alloc(s, &a.part, 2 * (size_t)c.C * (size_t)a.nchunk))) return rc;
+        s->comp.dev.push_back(a.part);
+        if ((rc = dev_alloc(s, &a.coef, (size_t)c.C * (size_t)a.k))) return rc;
+        s->comp.dev.push_back(a.coef);
+    } else {
+        a = CompArgs{};  // one component: the global constraint's path, nothing allocated
+    }
+    s->comp.args = a;
+    s->comp.id.swap(id);
+    return OCC_OK;
+}
 // The switches of a feature behind the z update (occ_sampler::Switches): every chain off, on the device too ...
 static int switch_alloc(occ_sampler *s, occ_sampler::Switches &sw)
 {
@@ -3613,6 +3694,12 @@ int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, 
     const std::string nm(name);
     const size_t n = (size_t)c.n, R = (size_t)c.R;
     std::vector<double> v;
+    if (nm == "component_id") {  // the handle's labels as they were set
+        if (const char *why = component_refusal(s)) return set_error(s, OCC_E_STATE, why);
+        if (s->comp.id.empty()) return set_error(s, OCC_E_STATE, "component_id has not been set for this handle");
+        v.assign(s->comp.id.begin(), s->comp.id.end());
+        return give_state(s, v, out, cap, len);
+    }
     int drw_field = DRW_NONE;
     const int drw_kind = draws_lookup(name, &drw_field);
     if (drw_kind >= 0) {
@@ -3690,6 +3777,7 @@ int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double 
     HIP_TRY(hipSetDevice(s->device));
     WAIT_TRY(s->stream);
     const std::string nm(name);
+    if (nm == "component_id") return set_component_id(s, in, len);
     int drw_field = DRW_NONE;
     const int drw_kind = draws_lookup(name, &drw_field);
     if (drw_kind >= 0) return set_draws_state(s, chain, drw_kind, drw_field, in, len);
@@ -3908,6 +3996,8 @@ int occ_profile(occ_sampler *s, int32_t reps, int64_t counts[OCC_N_KERNEL_KINDS]
             LAUNCH(s, s->stream, K_ITER, pe);
             s->ext_ev0 = s->ext_ev1 = nullptr;
             HIP_TRY(hipEventRecord(s->ev1, s->stream));
+            if (s->comp_on())  // (these are real iterations: the per-component correction stands where a sequence has it)
+                for (int k : {K_COMP_PART, K_COMP_COEF, K_COMP_ETA, K_COMP_BETA}) LAUNCH(s, s->stream, k, pe);
             if (ev) HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_side[pe], 0));
             LAUNCH(s, s->stream, K_Z_OB, pe);
             if (ev) HIP_TRY(hipEventRecord(s->ev_z[pe], s->stream));
@@ -4110,6 +4200,10 @@ int occ_cond_eta(occ_sampler *s, int32_t chain, const double *omega_b, const dou
         if ((long long)k > c.maxiter + 3) return set_error(s, OCC_E_MINRES, "MINRES solver did not converge!");
     }
     hipLaunchKernelGGL(pick_beta_partial(s->plan.generic ? 0 : c.p), gs, blk, s->plan.generic ? generic_lds_bytes(nacc(c.p), s->plan.tpb) : 0, s->stream, OCC_CARGS, k_last);
+    if (s->comp_on()) {  // the per-component correction, of this chain (occ_comp.hpp)
+        for (CompStage stage : {COMP_PART, COMP_COEF, COMP_ETA}) comp_launch(s->comp.args, c.sc, stage, chain, 1, e, s->stream);
+        hipLaunchKernelGGL(OCC_PICK_P(k_beta_sums, s->plan.generic ? 0 : c.p), gs, blk, s->plan.generic ? generic_lds_bytes(nacc(c.p), s->plan.tpb) : 0, s->stream, OCC_CARGS);
+    }
     ChainScalars sc;
     if ((rc = cond_end(s, chain, &sc))) return rc;
     if ((rc = copy_out(s, rhs_out, c.rhs + co, n))) return rc;

@@ -184,27 +184,7 @@ struct Ctx {
 // Partial sums are kept per WAVE (not per block), so producing and consuming them needs no
 // __syncthreads at all; every wave of the consumer re-reduces all partials in the same fixed order,
 // which makes the derived scalars bit-identical in every wave, block and run (no float atomics).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_shifted(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double wave_sum(double v)
-{
-    v += dpp_shifted<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v += dpp_shifted<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-    v += dpp_shifted<0x141, 0xf>(v);  // row_half_mirror
-    v += dpp_shifted<0x140, 0xf>(v);  // row_mirror: every lane of a 16-lane row holds the row sum
-    v += dpp_shifted<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
-    v += dpp_shifted<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3: lane 63 holds the wave sum
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, 63), hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);  // uniform
-}
-
+// (dpp_shifted and wave_sum themselves: occ_state.hpp, shared with the translation units that include nothing else of the kernels)
 // Four wave sums at once, each in wave_sum's order (bit-identical to four calls): written level by level so that the four
 // independent dependency chains sit next to each other -- a DPP move has to wait for the add that feeds it, and four
 // calls in a row expose that wait 24 times.  (Kept as the statement of the order; wave_sum4 below returns the same bits

@@ -287,7 +287,8 @@ inline void plan_settle(Plan &P, int form)
 //   TAIL   k_z_ob (beta, z, omega_b): after both
 // The kernel kinds: occ_profile's indices first (include/occ_gibbs.h), then the ones it does not report.
 enum Kind { K_OMEGA_B = 0, K_NOISE, K_ETA_INIT, K_MINRES, K_BETA_PARTIAL, K_OMEGA_A, K_ALPHA_DRAW, K_Z_OB, K_ITER, K_GATE /* internal: not a profiled kind */,
-            K_RSR_GRAM, K_RSR_SOLVE, K_RSR_ETA_BETA /* reduced-rank model */ };
+            K_RSR_GRAM, K_RSR_SOLVE, K_RSR_ETA_BETA /* reduced-rank model */,
+            K_COMP_PART, K_COMP_COEF, K_COMP_ETA, K_COMP_BETA /* sum-to-zero per component: occ_comp.hpp */ };
 static_assert(K_ITER + 1 == OCC_N_KERNEL_KINDS, "kernel kinds out of sync with the header");
 
 // launch sequences (iterations) per captured graph on the paths that need no host decision between iterations:
@@ -325,10 +326,17 @@ struct SeqLaunch { int kind, e, extra; };
 constexpr int EXTRA_HOST_WATCHED = -1, EXTRA_K_LAST = -2;
 
 // The launches of one part with sequence parity e, in order, handed to emit(SeqLaunch).  cap: the captured Krylov cap
-// (iteration j of a solve is tested by launch j + 3: cap + 3 launches).
+// (iteration j of a solve is tested by launch j + 3: cap + 3 launches).  comp: the handle has more than one connected
+// component to centre (ICAR model, state name component_id) -- the correction pass stands behind the solve's last launch,
+// whatever the solve's shape, and so in front of the z update.  A solve that is carried to the next sequence is a decision of
+// the device (Ctl::koff): the four launches stand in every sequence and leave a carrying chain alone, as k_z_ob does.
 template <class Emit>
-void seq_launches(SeqPart part, SeqSolve sv, int e, int cap, SeqGate gate, Emit &&emit)
+void seq_launches(SeqPart part, SeqSolve sv, int e, int cap, SeqGate gate, Emit &&emit, bool comp = false)
 {
+    auto correction = [&]() {
+        if (comp)
+            for (int k : {K_COMP_PART, K_COMP_COEF, K_COMP_ETA, K_COMP_BETA}) emit(SeqLaunch{k, e, 0});
+    };
     switch (part) {
         case PART_SIDE:
             if (gate == GATE_KERNEL) emit(SeqLaunch{K_GATE, 0, 0});
@@ -338,12 +346,16 @@ void seq_launches(SeqPart part, SeqSolve sv, int e, int cap, SeqGate gate, Emit 
         case PART_SOLVE:
             if (sv == SOLVE_RSR)  // the theta conditional stands where the ICAR solve is
                 for (int k : {K_RSR_GRAM, K_RSR_SOLVE, K_RSR_ETA_BETA}) emit(SeqLaunch{k, e, 0});
-            if (sv == SOLVE_FUSED) emit(SeqLaunch{K_ITER, e, 0});
+            if (sv == SOLVE_FUSED) {
+                emit(SeqLaunch{K_ITER, e, 0});
+                correction();
+            }
             if (sv <= SOLVE_FUSED) break;
             emit(SeqLaunch{K_ETA_INIT, e, 0});  // one launch per MINRES step
             if (sv == SOLVE_EAGER) emit(SeqLaunch{K_MINRES, e, EXTRA_HOST_WATCHED});
             else for (int k = 1; k <= cap + 3; ++k) emit(SeqLaunch{K_MINRES, e, k});
             emit(SeqLaunch{K_BETA_PARTIAL, e, sv == SOLVE_EAGER ? EXTRA_K_LAST : cap + 3});
+            correction();
             break;
         case PART_TAIL: emit(SeqLaunch{K_Z_OB, e, 0}); break;
         default: break;  // (the event nodes are the engine's: no launch)

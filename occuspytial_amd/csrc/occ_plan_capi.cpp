@@ -63,7 +63,14 @@ int32_t occ_order_sequences_per_enqueue(int32_t mode) { return sequences_per_enq
 
 // What one enqueue of a mode puts `where` (a SeqWhere; 3: an eager sequence instead) from sequence parity p, as
 // {kind, e, extra} triples; an event wait / record node is {-1 / -2, e, 0}.  The number of triples, -1 beyond `max`.
+// occ_order_launches_comp: the same with `comp` != 0 -- a handle with more than one connected component to centre
+// (tests/test_components_cpu.py).
+int32_t occ_order_launches_comp(int32_t mode, int32_t where, int32_t solve, int32_t p, int32_t cap, int32_t gate_kernel, int32_t comp, int32_t *out, int32_t max);
 int32_t occ_order_launches(int32_t mode, int32_t where, int32_t solve, int32_t p, int32_t cap, int32_t gate_kernel, int32_t *out, int32_t max)
+{
+    return occ_order_launches_comp(mode, where, solve, p, cap, gate_kernel, 0, out, max);
+}
+int32_t occ_order_launches_comp(int32_t mode, int32_t where, int32_t solve, int32_t p, int32_t cap, int32_t gate_kernel, int32_t comp, int32_t *out, int32_t max)
 {
     const SeqMode m = (SeqMode)mode;
     const SeqParts parts = where == 3 ? seq_eager() : seq_parts(m, (SeqWhere)where);
@@ -75,7 +82,7 @@ int32_t occ_order_launches(int32_t mode, int32_t where, int32_t solve, int32_t p
                 ++n;
             };
             if (parts.part[i] == PART_WAIT || parts.part[i] == PART_RECORD) emit(SeqLaunch{parts.part[i] == PART_WAIT ? -1 : -2, seq_parity(p, t), 0});
-            else seq_launches(parts.part[i], (SeqSolve)solve, seq_parity(p, t), cap, where == 3 ? GATE_NONE : seq_gate(m, gate_kernel != 0), emit);
+            else seq_launches(parts.part[i], (SeqSolve)solve, seq_parity(p, t), cap, where == 3 ? GATE_NONE : seq_gate(m, gate_kernel != 0), emit, comp != 0);
         }
     return n <= max ? n : -1;
 }

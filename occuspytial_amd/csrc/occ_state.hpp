@@ -1,5 +1,5 @@
 // occ_state.hpp -- what more than one translation unit of the engine reads: the limits, the chains' scalars (ChainScalars, Ctl)
-// and a few device functions -- expit, the covariate dot product, the 64-bit integer wave sum.  occ_kernels.hpp includes
+// and a few device functions -- expit, the covariate dot product, the wave sums of a double and of a 64-bit integer.  occ_kernels.hpp includes
 // it; occ_spatial.hip is a unit of its own and includes nothing else of the kernels (occ_kernels.hpp defines kernels, which
 // must exist once per library).
 #pragma once
@@ -61,6 +61,29 @@ __device__ __forceinline__ double xdot(const double *Xt, int n, int i, const dou
     double acc = 0.0;
     for (int a = 0; a < p; ++a) acc = fma(Xt[(size_t)a * n + i], coef[a], acc);
     return acc;
+}
+
+// The wave-level sum of a double (the reductions of occ_kernels.hpp say why DPP and why this order); occ_comp.hip adds a
+// component's chunk sums with it.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_shifted(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, ROW_MASK, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+__device__ __forceinline__ double wave_sum(double v)
+{
+    v += dpp_shifted<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
+    v += dpp_shifted<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
+    v += dpp_shifted<0x141, 0xf>(v);  // row_half_mirror
+    v += dpp_shifted<0x140, 0xf>(v);  // row_mirror: every lane of a 16-lane row holds the row sum
+    v += dpp_shifted<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
+    v += dpp_shifted<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3: lane 63 holds the wave sum
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane((int)b, 63), hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);  // uniform
 }
 
 template <int CTRL, int ROW_MASK>

@@ -12,6 +12,7 @@ from scipy.sparse import csc_matrix, isspmatrix_csc
 from .._problem import FlatProblem, default_start
 from ..chain import Chain
 from ..data import Data
+from ..graph import CONSTRAINTS
 from ..posterior import PosteriorParameter
 from ..utils import get_generator
 from . import options
@@ -47,8 +48,22 @@ class GibbsBase:
         raise NotImplementedError(f'{self.__class__.__name__} must implement a `step` method.')
 
     # ------------------------------------------------------------------ configuration (base.py:107-186)
-    def _configure(self, Q, hparams, verify_precision=True, prior_draw='auto', **kwargs):
-        prob = FlatProblem(Q, self.W._data, self.X, self.y._data, hparams, check_singular=verify_precision, prior_draw=prior_draw)
+    def _check_constraint(self, constraint, carries_none=None):
+        """Refuse a ``constraint`` this sampler cannot honour, before a problem or an engine exists: any value but
+        ``'global'`` and ``'component'``; ``'component'`` for a sampler whose spatial effect carries no sum-to-zero constraint
+        (``carries_none`` says why) or that steps in Python (the per-component projection is the engine's)."""
+        if constraint not in CONSTRAINTS:
+            raise ValueError("constraint must be 'global' or 'component'")
+        if constraint == 'component' and carries_none:
+            raise ValueError(f"{self.__class__.__name__} has no constraint='component': {carries_none}")
+        if constraint == 'component' and not hasattr(self, '_run_chains'):
+            raise ValueError(f"{self.__class__.__name__} steps in Python: constraint='component' is applied by the engine's "
+                             'correction pass behind the eta solve')
+
+    def _configure(self, Q, hparams, verify_precision=True, prior_draw='auto', constraint='global', **kwargs):
+        self._check_constraint(constraint)
+        prob = FlatProblem(Q, self.W._data, self.X, self.y._data, hparams, check_singular=verify_precision, prior_draw=prior_draw,
+                           constraint=constraint)
         self._problem = prob
 
         self.state = _GibbsState()

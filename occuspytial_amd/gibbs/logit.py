@@ -38,17 +38,25 @@ class LogitICARGibbs(GibbsBase):
       ``devices[c % len(devices)]`` -- the reference's one-process-per-chain fan-out (``gibbs/parallel.py:20-41``) with
       GPUs for processes: the problem is uploaded once and broadcast device to device over RCCL, every GPU is driven by
       its own host thread, and chain ``k`` still owns the generator the reference would give it, so the draws do not
-      depend on how many devices share the work.
+      depend on how many devices share the work;
+    * ``constraint='component'`` (the default ``'global'`` is the reference's one constraint :math:`1^\top\eta = 0`): on a
+      graph of ``k`` connected components -- islands, habitat fragments, isolated cells -- the spatial effect sums to zero
+      on EVERY component, a site without neighbours has :math:`\eta = 0`, and the default ``tau_shape`` is
+      ``0.5 + 0.5 (n - k)``, the rank of ``Q`` (Freni-Sterrantino, Ventrucci & Rue 2018).  Under ``'global'`` the prior
+      leaves ``k - 1`` component levels flat and a component with few surveyed sites drifts.
+      :func:`occuspytial_amd.graph.components` returns the components; with one component the two settings are the same
+      chain bit for bit.  Any other value is refused.
     """
 
-    def __init__(self, Q, W, X, y, hparams=None, random_state=None, device=0, devices=None, prior_draw='auto'):
+    def __init__(self, Q, W, X, y, hparams=None, random_state=None, device=0, devices=None, prior_draw='auto',
+                 constraint='global'):
         super().__init__(Q, W, X, y, hparams, random_state)
         self.devices = [int(d) for d in devices] if devices is not None else None
         self.device = self.devices[0] if self.devices else device
-        self._configure(Q, hparams, prior_draw=prior_draw)
+        self._configure(Q, hparams, prior_draw=prior_draw, constraint=constraint)
 
-    def _configure(self, Q, hparams, prior_draw='auto'):
-        super()._configure(Q, hparams, prior_draw=prior_draw)
+    def _configure(self, Q, hparams, prior_draw='auto', constraint='global'):
+        super()._configure(Q, hparams, prior_draw=prior_draw, constraint=constraint)
 
     # ------------------------------------------------------------------ engine management
     def _get_engine(self, keys):
@@ -275,9 +283,11 @@ class LogitRSRGibbs(LogitICARGibbs):
     and up to a rotation inside a cluster of near-equal eigenvalues; any value but ``'host'`` and ``'device'`` is refused.
     """
 
-    def __init__(self, Q, W, X, y, hparams=None, random_state=None, r=0.5, q=None, device=0, devices=None, basis='host'):
+    def __init__(self, Q, W, X, y, hparams=None, random_state=None, r=0.5, q=None, device=0, devices=None, basis='host',
+                 constraint='global'):
         if basis not in ('host', 'device'):
             raise ValueError("basis must be 'host' or 'device'")
+        self._check_constraint(constraint, 'its spatial effect K theta carries no sum-to-zero constraint')
         super().__init__(Q, W, X, y, hparams, random_state, device=device, devices=devices, prior_draw='edge')
         self._configure_rsr(r, q, hparams, basis)
 

@@ -30,9 +30,10 @@ class ProbitRSRGibbs(GibbsBase):
     rotation inside a cluster of near-equal eigenvalues); any value but ``'host'`` and ``'device'`` is refused.
     """
 
-    def __init__(self, Q, W, X, y, hparams=None, random_state=None, r=0.5, q=None, device=0, basis='host'):
+    def __init__(self, Q, W, X, y, hparams=None, random_state=None, r=0.5, q=None, device=0, basis='host', constraint='global'):
         if basis not in ('host', 'device'):
             raise ValueError("basis must be 'host' or 'device'")
+        self._check_constraint(constraint, 'its spatial effect K theta carries no sum-to-zero constraint')
         super().__init__(Q, W, X, y, hparams, random_state)
         self.devices = None
         self.device = device
