@@ -33,6 +33,34 @@ def components(Q):
     return int(k), rank[raw].astype(np.int32)
 
 
+def scale(Q, draws=1024, random_state=None, device=0, field=None):
+    """``(Q_scaled, factors)``: the ICAR precision scaled so that ``tau`` has a size-free meaning (Sorbye & Rue 2014; per
+    connected component as Freni-Sterrantino et al. 2018 recommend).
+
+    Every component ``k`` of two or more sites has its block of ``Q`` multiplied by
+    ``c_k = exp(mean_i log var_i - (psi(nu / 2) - log(nu / 2)))``, ``var`` the marginal variances ``diag(Q^+)`` estimated from
+    ``nu = draws`` device-drawn fields (:func:`occuspytial_amd.simulate.marginal_variance`); the subtracted term is the exact
+    bias of the logarithm of a chi-square(nu) / nu variate.  Under ``Q_scaled`` the geometric mean of the marginal variances
+    is 1 on every such component.  Singletons are untouched (factor 1).  ``Q_scaled`` is CSR and still an ICAR precision:
+    it goes straight into the samplers.  ``field`` replaces ``icar_field`` as in ``marginal_variance``.
+    """
+    from scipy.special import digamma
+
+    from .simulate import marginal_variance
+    Qc = sparse.csr_matrix(Q).astype(np.float64)
+    var, nu = marginal_variance(Qc, draws=draws, random_state=random_state, device=device, field=field)
+    k, labels = components(Qc)
+    size = np.bincount(labels, minlength=k)
+    many = size[labels] > 1
+    if np.any(var[many] <= 0):
+        raise ValueError('a site with neighbours has no variance: too few draws')
+    logv = np.where(many, np.log(np.where(many, var, 1.0)), 0.0)
+    factors = np.exp(np.bincount(labels, weights=logv, minlength=k) / size - (digamma(0.5 * nu) - np.log(0.5 * nu)))
+    factors[size == 1] = 1.0
+    Qs = sparse.csr_matrix(sparse.diags(factors[labels]) @ Qc)
+    return Qs, factors
+
+
 def centre(eta, labels):
     """``eta`` minus the mean of its component at every site (a site alone in its component: exactly 0.0)."""
     eta = np.asarray(eta, dtype=np.float64)
