@@ -263,6 +263,9 @@ struct occ_sampler {
     double *pin_rec = nullptr;
     size_t pin_rec_cap = 0;
     bool marks_done = false;       // ev1 and the copy of the records are enqueued behind the call's last batch
+    // OCC_VERBOSE: host stamps behind the stages of one occ_run (stamp(); run_impl prints them at its end)
+    bool stamps_on = false;
+    std::vector<std::pair<const char *, std::chrono::steady_clock::time_point>> stamps;
     bool debug_close_window = false;  // tests (occ_set_state "debug_close_window"): the NEXT call's window is opened with zero iterations on the device
     bool wedged = false;           // a host wait ran into its deadline: the streams never drained; nothing of this engine is freed or reused
     int probe_wait = 0, probe_backoff = 1;  // calls until the stream probe is asked again after a negative answer
@@ -321,6 +324,11 @@ namespace {
             return OCC_E_HIP;                                                                      \
         }                                                                                          \
     } while (0)
+
+static inline void stamp(occ_sampler *s, const char *stage)
+{
+    if (s->stamps_on) s->stamps.emplace_back(stage, std::chrono::steady_clock::now());
+}
 
 // ---- host waits have a deadline and name themselves ------------------------------------------------------------------
 // Every device-side wait of the engine is bounded (SYNC_SPIN_LIMIT, ITER_SPIN_LIMIT), so a host wait on one of its streams
@@ -729,14 +737,26 @@ int take_launch_rc(occ_sampler *s)
     return rc;
 }
 
-int read_scalars(occ_sampler *s, std::vector<ChainScalars> &h)
+// join_on_device (the end of an occ_run's batch): the MAIN STREAM waits for the side stream's last k_noise, through an event,
+// so the copy is enqueued behind the batch at once and the host waits once, for the main stream -- not first for the side
+// stream and then, a launch and a round trip later, for a copy it could not enqueue before.
+int read_scalars(occ_sampler *s, std::vector<ChainScalars> &h, bool join_on_device = false)
 {
     h.resize(s->ctx.C);
-    if (s->run.flag_sync) WAIT_TRY(s->side);  // its last k_noise is not waited for by the main stream
+    if (s->run.flag_sync && join_on_device) {
+        HIP_TRY(hipEventRecord(s->ev_side[0], s->side));  // (the counters' mode records no event of its own)
+        HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_side[0], 0));
+    } else if (s->run.flag_sync) {
+        WAIT_TRY(s->side);  // its last k_noise is not waited for by the main stream
+    }
+    stamp(s, "read_scalars: side stream joined");
     if (!s->pin_sc) HIP_TRY(hipHostMalloc((void **)&s->pin_sc, 2 * sizeof(ChainScalars) * h.size(), hipHostMallocDefault));
     ChainScalars *back = s->pin_sc + h.size();
     HIP_TRY(hipMemcpyAsync(back, s->ctx.sc, sizeof(ChainScalars) * h.size(), hipMemcpyDeviceToHost, s->stream));
+    stamp(s, "read_scalars: copy enqueued");
     WAIT_TRY(s->stream);
+    if (s->run.flag_sync && join_on_device) WAIT_TRY(s->side);  // (drained before the main stream's wait for it ended: one query)
+    stamp(s, "read_scalars: main stream drained");
     std::memcpy(h.data(), back, sizeof(ChainScalars) * h.size());
     return OCC_OK;
 }
@@ -904,8 +924,9 @@ int capture_graph(occ_sampler *s, hipStream_t st, SeqWhere where, int p, int n_s
 // Capture the mode's graphs: GRAPH_SEQ sequences from the engine's parity per stream, or one sequence per parity.  Iteration
 // j of a solve is tested by launch j + 3, so `cap` iterations need cap + 3 Krylov launches; a solve that needs more is
 // carried into the next sequence by the kernels themselves (Ctl::koff), so `cap` trades empty launches against carried
-// sequences.  Only the main-stream graphs depend on `cap`; the side graphs are captured once.
-int build_graph(occ_sampler *s, int cap)
+// sequences.  Only the main-stream graphs depend on `cap`; the side graphs are captured once.  with_long (the modes of
+// GRAPH_SEQ sequences per graph): a second pair of GRAPH_SEQ_LONG sequences from the same parity, in slot 1.
+int build_graph(occ_sampler *s, int cap, bool with_long = false)
 {
     const auto host_t0 = std::chrono::steady_clock::now();
     WAIT_TRY(s->stream);
@@ -927,12 +948,13 @@ int build_graph(occ_sampler *s, int cap)
         HIP_TRY(fill_on(s, s->ctx.sync, 0, sizeof(unsigned) * SYNC_DEBUG));
     }
     int rc;
-    for (int g = 0; g < (n_seq > 1 ? 1 : 2); ++g) {
+    for (int g = 0; g < (n_seq > 1 && !with_long ? 1 : 2); ++g) {
         const int p = n_seq > 1 ? s->parity : g;
-        if ((rc = capture_graph(s, s->stream, ON_MAIN, p, n_seq, cap, s->ev_side[p], s->ev_z[p], &s->head_graph[g]))) return rc;
+        const int len = n_seq > 1 && g == 1 ? GRAPH_SEQ_LONG : n_seq;
+        if ((rc = capture_graph(s, s->stream, ON_MAIN, p, len, cap, s->ev_side[p], s->ev_z[p], &s->head_graph[g]))) return rc;
         HIP_TRY(hipGraphInstantiate(&s->head[g], s->head_graph[g], nullptr, nullptr, 0));
         if (s->tail[g] || seq_parts(mode, ON_SIDE).n == 0) continue;
-        if ((rc = capture_graph(s, s->side, ON_SIDE, p, n_seq, cap, s->ev_z[p ^ 1], s->ev_side[p], &s->tail_graph[g]))) return rc;
+        if ((rc = capture_graph(s, s->side, ON_SIDE, p, len, cap, s->ev_z[p ^ 1], s->ev_side[p], &s->tail_graph[g]))) return rc;
         HIP_TRY(hipGraphInstantiate(&s->tail[g], s->tail_graph[g], nullptr, nullptr, 0));
     }
     if (n_seq > 1) s->graph_parity = s->parity;
@@ -947,16 +969,21 @@ int build_graph(occ_sampler *s, int cap)
 // Enqueue the mode's graphs once (sequences_per_enqueue: one Gibbs iteration of every chain or a carried solve, or
 // GRAPH_SEQ of them) without any host synchronisation.  DAG: side chain after the previous k_z_ob; k_z_ob after head and
 // side chain.
-int enqueue_sequence(occ_sampler *s)
+int enqueue_sequence(occ_sampler *s, int len = GRAPH_SEQ)
 {
     const int e = s->parity;
     const SeqMode mode = seq_mode(s);
+    const int g = len == GRAPH_SEQ_LONG ? 1 : 0;  // (the modes of GRAPH_SEQ sequences per graph: the long pair is in slot 1)
+    static_assert(seq_main_first(SEQ_COUNTERS) && !seq_main_first(SEQ_EVENT_NODES) && !seq_main_first(SEQ_STREAM_EVENTS) && !seq_main_first(SEQ_ONE_STREAM),
+                  "the order of each mode's two launches below is occ_plan.hpp's");
     switch (mode) {
-        case SEQ_COUNTERS:  // GRAPH_SEQ sequences on each stream
-            HIP_TRY(hipGraphLaunch(s->tail[0], s->side));
-            [[fallthrough]];
-        case SEQ_RSR_ONE_STREAM:  // GRAPH_SEQ sequences
-            HIP_TRY(hipGraphLaunch(s->head[0], s->stream));
+        case SEQ_COUNTERS:  // `len` sequences on each stream, the main stream's first (seq_main_first)
+            HIP_TRY(hipGraphLaunch(s->head[g], s->stream));
+            stamp(s, "main graph launched");
+            HIP_TRY(hipGraphLaunch(s->tail[g], s->side));
+            return OCC_OK;
+        case SEQ_RSR_ONE_STREAM:  // `len` sequences
+            HIP_TRY(hipGraphLaunch(s->head[g], s->stream));
             return OCC_OK;
         case SEQ_EVENT_NODES:  // the graphs carry their own waits and records
             HIP_TRY(hipGraphLaunch(s->tail[e], s->side));
@@ -2758,13 +2785,22 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     const int64_t keep = n_iter - burnin;
     const size_t rw = (size_t)q + p + 1;
     const size_t need = (size_t)C * keep * rw;
-    int rc = grow_device(s, &s->rec_buf, &s->rec_cap, need);  // (its address lives in the device descriptor)
+    stamp(s, "run_impl entered");
+    // (its address lives in the device descriptor.  Never less than REC_FLOOR doubles: a longer call after a short one -- a
+    // warm-up, a chunk -- does not free and allocate, 15 us of host time in front of its first kernel, for a few kilobytes)
+    constexpr size_t REC_FLOOR = 8192;
+    int rc = grow_device(s, &s->rec_buf, &s->rec_cap, std::max(need, REC_FLOOR));
     if (rc) return rc;
+    stamp(s, "rec_buf grown");
     if ((rc = records_open(s, C, keep))) return rc;  // (zeroed here, in front of the window: also when the call is re-run)
+    stamp(s, "records_open");
     if ((rc = records_publish(s))) return rc;
+    stamp(s, "records_publish");
     if ((rc = open_window(s, n_iter, burnin, keep, snapshot, true))) return rc;
+    stamp(s, "open_window");
     std::vector<ChainScalars> h;
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
+    stamp(s, "ev0");
     s->marks_done = false;
 
     // calibration (no graph yet): a few eager sequences measure the Krylov launches a solve needs;
@@ -2789,7 +2825,8 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
             if ((rc = eager_sequence(s))) return rc;
             done_min = 1;
         }
-        if (!s->head[0] && n_iter > 1 && (rc = build_graph(s, 0))) return rc;
+        // (the long pair of graphs with the short one, whatever this call's length: no later call captures anything)
+        if (!s->head[0] && n_iter > 1 && (rc = build_graph(s, 0, true))) return rc;
         if (n_iter == 1 && done_min == 0) {
             if ((rc = eager_sequence(s))) return rc;
             done_min = 1;
@@ -2821,12 +2858,18 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
         int64_t batch = std::min<int64_t>(left, s->graph_launches < 128 ? 32 : 256);
         batch = (batch + seq_per_enqueue - 1) / seq_per_enqueue * seq_per_enqueue;  // a surplus sequence idles (it_stop)
         const auto hl0 = std::chrono::steady_clock::now();
-        for (int64_t b = 0; b < batch; b += seq_per_enqueue)
-            if ((rc = enqueue_sequence(s))) return rc;
+        stamp(s, "first enqueue reached");
+        for (int64_t b = 0; b < batch;) {  // long replays while that many sequences are left, then short ones (graph_len)
+            const int len = seq_per_enqueue > 1 ? graph_len(batch - b, s->head[1] != nullptr) : 1;
+            if ((rc = enqueue_sequence(s, len))) return rc;
+            stamp(s, "enqueue_sequence");
+            b += len;
+        }
         const auto hl1 = std::chrono::steady_clock::now();
         s->graph_launches += batch;
         if ((rc = finish_marks(s, done_min + batch >= n_iter, (size_t)C * keep * rw))) return rc;
-        if ((rc = read_scalars(s, h))) return rc;
+        stamp(s, "finish_marks");
+        if ((rc = read_scalars(s, h, true))) return rc;
         if (std::getenv("OCC_VERBOSE")) {
             const auto hl2 = std::chrono::steady_clock::now();
             std::fprintf(stderr, "[occ] host: %.1f us per sequence to enqueue, %.1f us per sequence until the batch finished\n",
@@ -2881,7 +2924,7 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     }
     if (!s->marks_done) {  // (every iteration was stepped eagerly: nothing was enqueued above)
         if ((rc = finish_marks(s, true, (size_t)C * keep * rw))) return rc;
-        if ((rc = read_scalars(s, h))) return rc;
+        if ((rc = read_scalars(s, h, true))) return rc;
         if ((rc = check_device_errors(s, h))) return rc;
     }
     // (ev1 and the records were enqueued behind the last batch; the read of the scalars that followed waited for both)
@@ -2896,7 +2939,18 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
 
     split_rows(s->pin_rec, C, keep, q, p, out_alpha, out_beta, out_tau);
     records_close(s, keep, h);
+    stamp(s, "rows split, records closed");
     return OCC_OK;
+}
+
+// OCC_VERBOSE: the host's timeline of the call, one line per stage (microseconds since occ_run was entered, and since the
+// stage before)
+static void print_stamps(occ_sampler *s)
+{
+    for (size_t i = 1; i < s->stamps.size(); ++i)
+        std::fprintf(stderr, "[occ] stamp %9.1f us  +%8.1f  %s\n", std::chrono::duration<double, std::micro>(s->stamps[i].second - s->stamps[0].second).count(),
+                     std::chrono::duration<double, std::micro>(s->stamps[i].second - s->stamps[i - 1].second).count(), s->stamps[i].first);
+    s->stamps.clear();
 }
 
 
@@ -3079,6 +3133,9 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
     if (s->probit) return pb_run(s, n_iter, burnin, out_alpha, out_beta, out_tau);
+    Scoped<bool> stamps(&s->stamps_on, std::getenv("OCC_VERBOSE") != nullptr);  // (off again however the call ends)
+    s->stamps.clear();
+    stamp(s, "occ_run entered");
     int rc;
     if ((rc = hist_admit(s, n_iter - burnin))) return rc;
     if ((rc = refresh_paths(s))) return rc;
@@ -3089,6 +3146,7 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
         if ((rc = fallback_to_launch_per_step(s))) return rc;
         rc = run_impl(s, n_iter, burnin, out_alpha, out_beta, out_tau, false);
     }
+    print_stamps(s);
     return rc;
 }
 

@@ -293,7 +293,14 @@ static_assert(K_ITER + 1 == OCC_N_KERNEL_KINDS, "kernel kinds out of sync with t
 
 // launch sequences (iterations) per captured graph on the paths that need no host decision between iterations:
 // even, so that the sequence parity is the same at every replay; a graph boundary costs several microseconds
-constexpr int GRAPH_SEQ = 2;  // (16 per graph measured the same: the boundary between two replays is not what costs)
+constexpr int GRAPH_SEQ = 2;
+// ... and per LONG graph, captured beside the short one when a call has that many iterations to run.  The boundary between two
+// replays costs the device about 9 us on each stream (profiles/call_cost_timeline.txt: nothing runs between the last kernel
+// of one replay and the first of the next, although the host enqueued both long before): 4.5 us per iteration with the
+// short graph alone.  A batch is cut into long replays while that many sequences are left, then short ones: no surplus
+// sequence beyond the short graph's.
+constexpr int GRAPH_SEQ_LONG = 8;
+constexpr int graph_len(long long left, bool have_long) { return have_long && left >= GRAPH_SEQ_LONG ? GRAPH_SEQ_LONG : GRAPH_SEQ; }
 
 enum SeqMode : int {
     SEQ_COUNTERS = 0,        // hand-overs by device counters: two graphs of GRAPH_SEQ sequences, main and side
@@ -376,6 +383,14 @@ constexpr SeqParts seq_parts(SeqMode m, SeqWhere w)
         default: return w == ON_MAIN ? SeqParts{1, {PART_SOLVE}} : w == ON_SIDE ? SeqParts{1, {PART_SIDE}} : SeqParts{1, {PART_TAIL}};
     }
 }
+// Which stream's graph an enqueue launches FIRST.  With the counters: the main stream's.  On an idle device (the head of a
+// call) k_iter is then resident and through the part of its head that needs no noise while the host launches the side
+// graph; the noise itself was left by the previous call, but it is ANNOUNCED by the gate at the head of this sequence's
+// k_omega_a (SYNC_NOISE), so k_iter's bounded wait ends when that kernel starts -- the wait it has in every sequence, for
+// microseconds of host time here.  The side stream is released by the main stream's kernels, never the other way round.
+// Measured: the 20-iteration call 7 to 15 us shorter than with the side graph first, two sessions of six alternating runs
+// whose ranges overlap (profiles/call_cost_ab.txt): a small gain.  The event modes launch the side graph first, as they did.
+constexpr bool seq_main_first(SeqMode m) { return m == SEQ_COUNTERS; }
 // An eager sequence in every mode: everything on the main stream, the reference's order of conditionals (logit.py:254-266)
 // with omega_a / alpha moved up front -- stream order is the synchronisation
 constexpr SeqParts seq_eager() { return SeqParts{3, {PART_SIDE, PART_SOLVE, PART_TAIL}}; }

@@ -60,6 +60,10 @@ int32_t occ_order_mode(int32_t flag_sync, int32_t rsr, int32_t event_nodes, int3
     return seq_mode_runs(m, (SeqSolve)solve) ? (int32_t)m : -1;
 }
 int32_t occ_order_sequences_per_enqueue(int32_t mode) { return sequences_per_enqueue((SeqMode)mode); }
+// The long graph's length; the length of the next replay with `left` sequences to go; whether a mode launches its main graph first
+int32_t occ_order_graph_seq_long(void) { return GRAPH_SEQ_LONG; }
+int32_t occ_order_graph_len(int64_t left, int32_t have_long) { return graph_len(left, have_long != 0); }
+int32_t occ_order_main_first(int32_t mode) { return seq_main_first((SeqMode)mode); }
 
 // What one enqueue of a mode puts `where` (a SeqWhere; 3: an eager sequence instead) from sequence parity p, as
 // {kind, e, extra} triples; an event wait / record node is {-1 / -2, e, 0}.  The number of triples, -1 beyond `max`.
