@@ -447,12 +447,16 @@ static void joint_matvec(long n, const int64_t *indptr, const int64_t *indices, 
         double *oh = out + h * n;
         for (long i = 0; i < n; ++i) {
             double acc = 0.0;
+            int met_diag = 0;
             for (int64_t k = indptr[i]; k < indptr[i + 1]; ++k) {
                 long j = (long)indices[k];
                 double a = tau * qdata[k];
-                if (j == i) a = a + omega[i];
+                if (j == i) { a = a + omega[i]; met_diag = 1; }
                 acc += a * vh[j];
             }
+            /* a row that stores no diagonal (a site without neighbours: its row of Q is empty) still has omega on the
+             * operator's diagonal; a row that stores one runs exactly the operations above */
+            if (!met_diag) acc += omega[i] * vh[i];
             oh[i] = acc;
         }
     }

@@ -57,16 +57,25 @@ def test_group_broadcast_through_rccl_with_one_device(monkeypatch):
     grp.close()
 
 
-@pytest.mark.parametrize('transport', ['peer', 'default'])
-def test_chains_sharded_over_two_samplers_equal_one_batch(monkeypatch, transport):
+def _sharded_problem(graph):
+    if graph == 'ref_graph300_weighted':
+        return _problem_from_golden(graph)[0]
+    from . import _layout_graphs as G
+    return G.survey(G.graph(graph), G.SEEDS[graph])
+
+
+@pytest.mark.parametrize('transport, graph', [('peer', 'ref_graph300_weighted'), ('default', 'ref_graph300_weighted'), ('peer', 'hub')],
+                         ids=['peer', 'default', 'peer-hub'])
+def test_chains_sharded_over_two_samplers_equal_one_batch(monkeypatch, transport, graph):
     """Two samplers of one group (both on device 0: the box has one GPU): the second receives the laid-out arrays
     device to device, chain c runs on sampler c % 2 from its own host thread -- same chains as one batch, bit for bit.
     `default` asks RCCL first (ncclCommInitAll refuses a device listed twice, so the hand-over falls to hipMemcpyPeer
-    and says why); `peer` forces hipMemcpyPeer."""
+    and says why); `peer` forces hipMemcpyPeer.  `hub` (tests/_layout_graphs.py): true SELL-64 bases -- the second sampler
+    sizes its slot arrays from the header and sell_ptr, and receives sell_ptr and ell_w = 0 with the rest."""
     from occuspytial_amd._engine import Engine, EngineGroup
     if transport == 'peer':
         monkeypatch.setenv('OCC_GROUP_TRANSPORT', 'peer')
-    prob, _ = _problem_from_golden('ref_graph300_weighted')
+    prob = _sharded_problem(graph)
     keys = [KEY + 3 * c for c in range(5)]
     plain = Engine(prob, keys)
     ref = _run(plain, prob, 5)

@@ -4,7 +4,7 @@ Per kept draw two kernels behind the z update add eight signed integer sums in 2
 the occupancy residuals r = z - psi, and the same of one replicate r* = z* - psi.  Integer sums do not depend on the order of
 addition, so every comparison between two ways of running the engine is equality; the comparison with numpy (``_columns``)
 is within one quantum per site.  Workloads: 13x17 and 30x40 queen lattices, the weighted 300-node graph of the golden
-fixtures, 17x19 with nine covariates of each kind (the generic kernels), the reduced-rank model at 40 columns.  Every test
+fixtures, the 700-site `hub` graph of tests/_layout_graphs.py (true SELL-64 bases, one row of 46 off-diagonals), 17x19 with nine covariates of each kind (the generic kernels), the reduced-rank model at 40 columns.  Every test
 runs under its own time limit (``_time_limit``).
 """
 
@@ -80,6 +80,12 @@ def _lattice(rows, cols, chains, seed):
     return prob, [KEY + 13 * c for c in range(chains)], [_random_start(prob, 40 + c) for c in range(chains)]
 
 
+def _hub(chains):
+    from . import _layout_graphs as G
+    prob = G.survey(G.graph('hub'), G.SEEDS['hub'])
+    return prob, [KEY + 13 * c for c in range(chains)], [_random_start(prob, 40 + c) for c in range(chains)]
+
+
 # ------------------------------------------------------------------ 1: restatement
 WORKLOADS = {
     'queen13x17': lambda chains: _lattice(13, 17, chains, 6),
@@ -87,8 +93,10 @@ WORKLOADS = {
     'weighted300': lambda chains: (lambda pr: (pr[0], [KEY], [pr[1]]))(_problem_from_golden('ref_graph300_weighted')),
     'generic': lambda chains: _workload_g(),
     'rsr40': lambda chains: _rsr_problem(40),
+    'hub': lambda chains: _hub(chains),   # true SELL bases (ell_w = 0): the sums rebuild a CSR from sell_ptr as it comes back
 }
-CASES = [('queen13x17', 1), ('queen30x40', 1), ('queen30x40', 2), ('queen30x40', 4), ('weighted300', 1), ('generic', 1), ('rsr40', 2)]
+CASES = [('queen13x17', 1), ('queen30x40', 1), ('queen30x40', 2), ('queen30x40', 4), ('weighted300', 1), ('generic', 1), ('rsr40', 2),
+         ('hub', 2)]
 
 
 @pytest.mark.parametrize('name, chains', CASES)

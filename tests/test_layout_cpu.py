@@ -261,7 +261,7 @@ def test_a_prior_factor_lifts_the_sign_and_row_sum_checks(lib):
 GOLDEN_BRANCHES = {
     'ref_graph300_weighted': (10, 0), 'ref_queen150_hparams': (8, 8), 'ref_queen150_ragged': (8, 8), 'ref_queen400_v3': (8, 8),
     'ref_rook400_v3': (4, 4), 'ref_rsr150_q10': (8, 8), 'ref_rsr150_r05': (8, 8),
-}  # none reaches true SELL bases (ell_w = 0): DESIGN.md, "Data layout"
+}  # none reaches true SELL bases (ell_w = 0): the graphs of tests/_layout_graphs.py do (test_layout_graphs_cpu.py pins them)
 
 
 def test_branches_of_the_golden_fixtures(lib):
