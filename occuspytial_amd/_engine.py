@@ -6,10 +6,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-
-
-def _ptr(a):
-    return C.c_void_p(a.ctypes.data)
+from ._native import ptr as _ptr
 
 
 def _keys_array(keys):

@@ -8,6 +8,8 @@ import ctypes as C
 import os
 from typing import NamedTuple
 
+from ._native import EngineUnavailable, load_library  # noqa: F401  (EngineUnavailable: the name its users import from here)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libocc_gibbs.so')
 
@@ -157,12 +159,6 @@ SYMBOLS = (
 )
 
 _lib = None
-
-
-class EngineUnavailable(RuntimeError):
-    """The HIP engine cannot be used (library not built, or no usable gfx950 device)."""
-
-
 ABI_VERSION = 7  # OCC_ABI_VERSION of include/occ_gibbs.h this binding was written against
 
 
@@ -170,19 +166,7 @@ def load():
     """Load the shared library and declare its prototypes (no GPU call is made here)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise EngineUnavailable(
-                f'{LIB_PATH} is missing: the HIP engine has not been built '
-                '(run __graft_entry__.build() or `make -C occuspytial_amd/csrc`). There is no CPU fallback.')
-        lib = C.CDLL(LIB_PATH)
-        for name, restype, argtypes in SYMBOLS:
-            fn = getattr(lib, name)
-            fn.restype = restype
-            fn.argtypes = argtypes
-        if lib.occ_abi_version() != ABI_VERSION:  # a stale build: struct layouts would not match
-            raise EngineUnavailable(f'{LIB_PATH} has ABI version {lib.occ_abi_version()}, this binding needs {ABI_VERSION}: rebuild it '
-                                    '(`make -C occuspytial_amd/csrc`)')
-        _lib = lib
+        _lib = load_library(LIB_PATH, SYMBOLS, 'occ_abi_version', ABI_VERSION, 'the HIP engine', version_noun='ABI version')
     return _lib
 
 

@@ -14,21 +14,18 @@
 // quarter-wave loads in every kernel here.  k_basis_gram and k_basis_rotate run on v_mfma_f64_16x16x4_f64 with the operand
 // layout occ_rsr.hpp states (wave64: lane l carries A[l % 16][l / 16] and B[l / 16][l % 16], receives D[4 v + l / 16][l % 16]).
 // No kernel waits on the device, none uses an atomic: every sum has one fixed order, so a repeated call returns the same
-// bits.  One plain stream per handle (not CU-masked, not from the engine's pool); every host wait is a deadline poll.
+// bits.  The handle's device, stream, allocations, deadline wait and create / destroy are occ_handle.hpp's.
 #include "../../include/occ_basis.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
+#include "occ_handle.hpp"
 #include "occ_layout.hpp"
 
 namespace occ_basis_impl {
@@ -281,87 +278,23 @@ __global__ void __launch_bounds__(256) k_basis_res_sum(const double *__restrict_
 
 using namespace occ_basis_impl;
 
-struct occ_basis {
-    int device = 0, n = 0, p = 0, ld = 0, b = 0, b_max = 0, ell_w = 0, wmax = 0, nslice = 0, ntile = 0;
+struct occ_basis : occ::HandleBase {
+    int n = 0, p = 0, ld = 0, b = 0, b_max = 0, ell_w = 0, wmax = 0, nslice = 0, ntile = 0;
     double s = 0.0, rho = 0.0;
-    hipStream_t st = nullptr;
     int *sell_ptr = nullptr, *sell_col = nullptr;
     double *sell_val = nullptr, *X = nullptr, *AX = nullptr, *Xi = nullptr;
     double *blk[3] = {nullptr, nullptr, nullptr};
     int slot[3] = {0, 1, 2};  // logical -> physical block
     double *part = nullptr, *D = nullptr, *Y = nullptr, *G = nullptr, *lam = nullptr, *res = nullptr;
     bool w_valid = false;  // logical block 1 holds Omega . (logical block 0)
-    std::string err;
     std::vector<double> stage;
 };
+OCC_HANDLE_CODES(OCC_BASIS_OK, OCC_BASIS_E_BADARG, OCC_BASIS_E_HIP);
 
 static thread_local std::string g_create_err;
 
-static double host_wait_limit_s()
-{
-    const char *e = std::getenv("OCC_HOST_WAIT_S");
-    const double v = e ? std::atof(e) : 20.0;
-    return v > 0.0 ? v : 20.0;
-}
-
-// the handle's stream has drained, or the deadline has passed (the manner of the engine's wait_on)
-static int wait_on(occ_basis *h, const char *what)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    const double limit = host_wait_limit_s();
-    for (unsigned polls = 1;; ++polls) {
-        const hipError_t q = hipStreamQuery(h->st);
-        if (q == hipSuccess) return OCC_BASIS_OK;
-        if (q != hipErrorNotReady) {
-            h->err = std::string(what) + ": " + hipGetErrorString(q);
-            return OCC_BASIS_E_HIP;
-        }
-        (void)hipGetLastError();
-        if ((polls & 63u) == 0u) {
-            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (sec > limit) {
-                char lim[64];
-                std::snprintf(lim, sizeof(lim), "%.0f s", limit);
-                h->err = std::string(what) + ": the stream did not drain within " + lim;
-                return OCC_BASIS_E_HIP;
-            }
-            if (sec > 0.002) std::this_thread::yield();
-        }
-    }
-}
-
-#define BH_TRY(expr)                                                                   \
-    do {                                                                               \
-        const hipError_t e_ = (expr);                                                  \
-        if (e_ != hipSuccess) {                                                        \
-            h->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
-            return OCC_BASIS_E_HIP;                                                    \
-        }                                                                              \
-    } while (0)
-#define BH_WAIT(what)                                   \
-    do {                                                \
-        const int w_ = wait_on(h, what);                \
-        if (w_ != OCC_BASIS_OK) return w_;              \
-    } while (0)
-#define BH_ARG(cond, msg)                   \
-    do {                                    \
-        if (!(cond)) {                      \
-            h->err = (msg);                 \
-            return OCC_BASIS_E_BADARG;      \
-        }                                   \
-    } while (0)
-
 static int bc_of(int b) { return (b + 15) / 16 * 16; }
 static double *blk(occ_basis *h, int logical) { return h->blk[h->slot[logical]]; }
-
-template <class T>
-static int upload(occ_basis *h, T **dst, const std::vector<T> &src)
-{
-    BH_TRY(hipMalloc((void **)dst, std::max<size_t>(src.size(), 1) * sizeof(T)));
-    if (!src.empty()) BH_TRY(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, h->st));
-    BH_WAIT("upload");  // (the host vector may go away after this)
-    return OCC_BASIS_OK;
-}
 
 // D = (X'X)^-1 X' src
 static int launch_xt(occ_basis *h, const double *src)
@@ -383,7 +316,7 @@ static int launch_apply(occ_basis *h, const double *src, double *out, double alp
     launch_xt(h, out);
     hipLaunchKernelGGL(h->p <= FASTP ? k_basis_combine<FASTP> : k_basis_combine<MAXP>, dim3(h->nslice, (bc + 63) / 64), dim3(256), 0, h->st, (const double *)out, out, h->X, h->D, y1, y0,
                        alpha * h->s, beta, gamma, h->n, h->p, h->ld, bc);
-    BH_TRY(hipGetLastError());
+    H_TRY(hipGetLastError());
     return OCC_BASIS_OK;
 }
 
@@ -401,38 +334,25 @@ int32_t occ_basis_version(void) { return OCC_BASIS_VERSION; }
 
 const char *occ_basis_last_error(const occ_basis *h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
-int occ_basis_destroy(occ_basis *h)
-{
-    if (!h) return OCC_BASIS_OK;
-    (void)hipSetDevice(h->device);
-    if (h->st) {
-        (void)wait_on(h, "occ_basis_destroy");
-        (void)hipStreamDestroy(h->st);
-    }
-    void *ptrs[] = {h->sell_ptr, h->sell_col, h->sell_val, h->X, h->AX, h->Xi, h->blk[0], h->blk[1], h->blk[2], h->part, h->D, h->Y, h->G, h->lam, h->res};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
-    delete h;
-    return OCC_BASIS_OK;
-}
+int occ_basis_destroy(occ_basis *h) { return occ::handle_destroy(h, "occ_basis_destroy"); }
 
 static int create_impl(occ_basis *h, int64_t n64, const int32_t *indptr, const int32_t *indices, const double *qdata, const double *X, int32_t p,
                        const double *XtX_inv, int32_t b_max, int32_t device)
 {
-    BH_ARG(n64 >= 1 && n64 < (int64_t)1 << 30, "n must lie in [1, 2^30)");
-    BH_ARG(p >= 1 && p <= MAXP, "p must lie in [1, 32]");
-    BH_ARG(b_max >= 1 && b_max <= 16384, "b_max must lie in [1, 16384]");
-    BH_ARG(indptr && indices && qdata && X && XtX_inv, "null input");
+    H_ARG(n64 >= 1 && n64 < (int64_t)1 << 30, "n must lie in [1, 2^30)");
+    H_ARG(p >= 1 && p <= MAXP, "p must lie in [1, 32]");
+    H_ARG(b_max >= 1 && b_max <= 16384, "b_max must lie in [1, 16384]");
+    H_ARG(indptr && indices && qdata && X && XtX_inv, "null input");
     const int n = (int)n64;
     std::vector<int32_t> ip(indptr, indptr + n + 1);
     std::string why;
-    if (!occ::layout_q_indptr(n, ip, &why)) BH_ARG(false, why);
-    for (int i = 0; i < n; ++i) BH_ARG(ip[i + 1] >= ip[i], "malformed Q indptr");
+    if (!occ::layout_q_indptr(n, ip, &why)) H_ARG(false, why);
+    for (int i = 0; i < n; ++i) H_ARG(ip[i + 1] >= ip[i], "malformed Q indptr");
     std::vector<int32_t> ix(indices, indices + ip[n]);
     std::vector<double> qd(qdata, qdata + ip[n]);
     occ::HostLayout L;
     // (has_prior_factor: weights of either sign, no singularity test -- the basis needs neither)
-    if (!occ::layout_q(n, ip, ix, qd, true, L, &why)) BH_ARG(false, why);
+    if (!occ::layout_q(n, ip, ix, qd, true, L, &why)) H_ARG(false, why);
     double total = 0.0, rowmax = 0.0;
     std::vector<double> AX((size_t)n * p, 0.0);
     for (int i = 0; i < n; ++i) {
@@ -447,9 +367,8 @@ static int create_impl(occ_basis *h, int64_t n64, const int32_t *indptr, const i
         }
         rowmax = std::max(rowmax, rowabs);
     }
-    BH_ARG(total > 0.0 && std::isfinite(total), "the off-diagonals of -Q must have a positive sum");
+    H_ARG(total > 0.0 && std::isfinite(total), "the off-diagonals of -Q must have a positive sum");
     for (double &v : L.sell_val) v = -v;  // A = -offdiag(Q)
-    h->device = device;
     h->n = n;
     h->p = p;
     h->b_max = b_max;
@@ -462,58 +381,33 @@ static int create_impl(occ_basis *h, int64_t n64, const int32_t *indptr, const i
     h->s = (double)n / total;
     h->rho = h->s * rowmax;
 
-    int ndev = 0;
-    BH_TRY(hipGetDeviceCount(&ndev));
-    BH_ARG(device >= 0 && device < ndev, "no such device");
-    BH_TRY(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    BH_TRY(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        h->err = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950";
-        return OCC_BASIS_E_HIP;
-    }
-    BH_TRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
     int rc;
-    if ((rc = upload(h, &h->sell_ptr, L.sell_ptr)) != OCC_BASIS_OK) return rc;
-    if ((rc = upload(h, &h->sell_col, L.sell_col)) != OCC_BASIS_OK) return rc;
-    if ((rc = upload(h, &h->sell_val, L.sell_val)) != OCC_BASIS_OK) return rc;
-    if ((rc = upload(h, &h->X, std::vector<double>(X, X + (size_t)n * p))) != OCC_BASIS_OK) return rc;
-    if ((rc = upload(h, &h->AX, AX)) != OCC_BASIS_OK) return rc;
-    if ((rc = upload(h, &h->Xi, std::vector<double>(XtX_inv, XtX_inv + (size_t)p * p))) != OCC_BASIS_OK) return rc;
-    const size_t ld = (size_t)h->ld, blk_bytes = (size_t)n * ld * sizeof(double);
-    for (int k = 0; k < 3; ++k) {
-        BH_TRY(hipMalloc((void **)&h->blk[k], blk_bytes));
-        BH_TRY(hipMemsetAsync(h->blk[k], 0, blk_bytes, h->st));
-    }
+    if ((rc = h->open(device)) != OCC_BASIS_OK) return rc;
+    if ((rc = h->upload(&h->sell_ptr, L.sell_ptr)) != OCC_BASIS_OK) return rc;
+    if ((rc = h->upload(&h->sell_col, L.sell_col)) != OCC_BASIS_OK) return rc;
+    if ((rc = h->upload(&h->sell_val, L.sell_val)) != OCC_BASIS_OK) return rc;
+    if ((rc = h->upload(&h->X, std::vector<double>(X, X + (size_t)n * p))) != OCC_BASIS_OK) return rc;
+    if ((rc = h->upload(&h->AX, AX)) != OCC_BASIS_OK) return rc;
+    if ((rc = h->upload(&h->Xi, std::vector<double>(XtX_inv, XtX_inv + (size_t)p * p))) != OCC_BASIS_OK) return rc;
+    const size_t ld = (size_t)h->ld;
+    for (int k = 0; k < 3; ++k)
+        if ((rc = h->alloc(&h->blk[k], (size_t)n * ld, true)) != OCC_BASIS_OK) return rc;
     const size_t mp = p <= FASTP ? FASTP : MAXP;  // (the rows the instantiation in use lays `part` and D out by: launch_xt)
-    BH_TRY(hipMalloc((void **)&h->part, (size_t)h->ntile * mp * ld * sizeof(double)));
-    BH_TRY(hipMalloc((void **)&h->D, mp * ld * sizeof(double)));
-    BH_TRY(hipMalloc((void **)&h->Y, ld * ld * sizeof(double)));
-    BH_TRY(hipMalloc((void **)&h->G, ld * ld * sizeof(double)));
-    BH_TRY(hipMalloc((void **)&h->lam, ld * sizeof(double)));
-    BH_TRY(hipMalloc((void **)&h->res, ld * sizeof(double)));
-    BH_WAIT("occ_basis_create");
+    if ((rc = h->alloc(&h->part, (size_t)h->ntile * mp * ld, false)) != OCC_BASIS_OK) return rc;
+    if ((rc = h->alloc(&h->D, mp * ld, false)) != OCC_BASIS_OK) return rc;
+    if ((rc = h->alloc(&h->Y, ld * ld, false)) != OCC_BASIS_OK) return rc;
+    if ((rc = h->alloc(&h->G, ld * ld, false)) != OCC_BASIS_OK) return rc;
+    if ((rc = h->alloc(&h->lam, ld, false)) != OCC_BASIS_OK) return rc;
+    if ((rc = h->alloc(&h->res, ld, false)) != OCC_BASIS_OK) return rc;
+    H_WAIT("occ_basis_create");
     return OCC_BASIS_OK;
 }
 
 int occ_basis_create(int64_t n, const int32_t *q_indptr, const int32_t *q_indices, const double *q_data, const double *X, int32_t p,
                      const double *XtX_inv, int32_t b_max, int32_t device, occ_basis **out)
 {
-    if (!out) {
-        g_create_err = "null output pointer";
-        return OCC_BASIS_E_BADARG;
-    }
-    *out = nullptr;
-    occ_basis *h = new occ_basis();
-    const int rc = create_impl(h, n, q_indptr, q_indices, q_data, X, p, XtX_inv, b_max, device);
-    if (rc != OCC_BASIS_OK) {
-        g_create_err = h->err;
-        (void)hipGetLastError();
-        occ_basis_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return OCC_BASIS_OK;
+    return occ::handle_create(out, g_create_err, "occ_basis_destroy",
+                              [&](occ_basis *h) { return create_impl(h, n, q_indptr, q_indices, q_data, X, p, XtX_inv, b_max, device); });
 }
 
 int occ_basis_info(const occ_basis *h, double *info6)
@@ -531,14 +425,14 @@ int occ_basis_info(const occ_basis *h, double *info6)
 int occ_basis_set_block(occ_basis *h, int32_t which, const double *V, int32_t b)
 {
     if (!h) return OCC_BASIS_E_BADARG;
-    BH_ARG(which >= 0 && which < 3 && V, "block index must be 0, 1 or 2");
-    BH_ARG(b >= 1 && b <= h->b_max, "b must lie in [1, b_max]");
-    BH_TRY(hipSetDevice(h->device));
+    H_ARG(which >= 0 && which < 3 && V, "block index must be 0, 1 or 2");
+    H_ARG(b >= 1 && b <= h->b_max, "b must lie in [1, b_max]");
+    H_TRY(hipSetDevice(h->device));
     double *dst = blk(h, which);
-    BH_TRY(hipMemsetAsync(dst, 0, (size_t)h->n * h->ld * sizeof(double), h->st));
-    BH_TRY(hipMemcpy2DAsync(dst, (size_t)h->ld * sizeof(double), V, (size_t)b * sizeof(double), (size_t)b * sizeof(double), (size_t)h->n,
+    H_TRY(hipMemsetAsync(dst, 0, (size_t)h->n * h->ld * sizeof(double), h->st));
+    H_TRY(hipMemcpy2DAsync(dst, (size_t)h->ld * sizeof(double), V, (size_t)b * sizeof(double), (size_t)b * sizeof(double), (size_t)h->n,
                             hipMemcpyHostToDevice, h->st));
-    BH_WAIT("occ_basis_set_block");
+    H_WAIT("occ_basis_set_block");
     h->b = b;
     h->w_valid = false;
     return OCC_BASIS_OK;
@@ -547,52 +441,52 @@ int occ_basis_set_block(occ_basis *h, int32_t which, const double *V, int32_t b)
 int occ_basis_get_block(occ_basis *h, int32_t which, double *V, int32_t b)
 {
     if (!h) return OCC_BASIS_E_BADARG;
-    BH_ARG(which >= 0 && which < 3 && V, "block index must be 0, 1 or 2");
-    BH_ARG(b >= 1 && b <= h->b_max, "b must lie in [1, b_max]");
-    BH_TRY(hipSetDevice(h->device));
-    BH_TRY(hipMemcpy2DAsync(V, (size_t)b * sizeof(double), blk(h, which), (size_t)h->ld * sizeof(double), (size_t)b * sizeof(double), (size_t)h->n,
+    H_ARG(which >= 0 && which < 3 && V, "block index must be 0, 1 or 2");
+    H_ARG(b >= 1 && b <= h->b_max, "b must lie in [1, b_max]");
+    H_TRY(hipSetDevice(h->device));
+    H_TRY(hipMemcpy2DAsync(V, (size_t)b * sizeof(double), blk(h, which), (size_t)h->ld * sizeof(double), (size_t)b * sizeof(double), (size_t)h->n,
                             hipMemcpyDeviceToHost, h->st));
-    BH_WAIT("occ_basis_get_block");
+    H_WAIT("occ_basis_get_block");
     return OCC_BASIS_OK;
 }
 
 int occ_basis_apply(occ_basis *h, int32_t src, int32_t dst)
 {
     if (!h) return OCC_BASIS_E_BADARG;
-    BH_ARG(src >= 0 && src < 3 && dst >= 0 && dst < 3 && src != dst, "src and dst must be two different blocks of 0, 1, 2");
-    BH_ARG(h->b >= 1, "no block has been set");
-    BH_TRY(hipSetDevice(h->device));
+    H_ARG(src >= 0 && src < 3 && dst >= 0 && dst < 3 && src != dst, "src and dst must be two different blocks of 0, 1, 2");
+    H_ARG(h->b >= 1, "no block has been set");
+    H_TRY(hipSetDevice(h->device));
     const int rc = launch_apply(h, blk(h, src), blk(h, dst), 1.0, 0.0, nullptr, 0.0, nullptr);
     if (rc != OCC_BASIS_OK) return rc;
     if (dst == 0) h->w_valid = false;
     else if (dst == 1) h->w_valid = (src == 0);
-    BH_WAIT("occ_basis_apply");
+    H_WAIT("occ_basis_apply");
     return OCC_BASIS_OK;
 }
 
 int occ_basis_project(occ_basis *h)
 {
     if (!h) return OCC_BASIS_E_BADARG;
-    BH_ARG(h->b >= 1, "no block has been set");
-    BH_TRY(hipSetDevice(h->device));
+    H_ARG(h->b >= 1, "no block has been set");
+    H_TRY(hipSetDevice(h->device));
     const int bc = bc_of(h->b);
     double *v = blk(h, 0);
     launch_xt(h, v);
     hipLaunchKernelGGL(h->p <= FASTP ? k_basis_combine<FASTP> : k_basis_combine<MAXP>, dim3(h->nslice, (bc + 63) / 64), dim3(256), 0, h->st, (const double *)v, v, h->X, h->D, (const double *)nullptr,
                        (const double *)nullptr, 1.0, 0.0, 0.0, h->n, h->p, h->ld, bc);
-    BH_TRY(hipGetLastError());
+    H_TRY(hipGetLastError());
     h->w_valid = false;
-    BH_WAIT("occ_basis_project");
+    H_WAIT("occ_basis_project");
     return OCC_BASIS_OK;
 }
 
 int occ_basis_filter(occ_basis *h, int32_t degree, double lo, double hi, double top)
 {
     if (!h) return OCC_BASIS_E_BADARG;
-    BH_ARG(h->b >= 1, "no block has been set");
-    BH_ARG(degree >= 1 && degree <= 4096, "degree must lie in [1, 4096]");
-    BH_ARG(lo < hi && hi < top && std::isfinite(lo) && std::isfinite(top), "the damped interval needs lo < hi < top");
-    BH_TRY(hipSetDevice(h->device));
+    H_ARG(h->b >= 1, "no block has been set");
+    H_ARG(degree >= 1 && degree <= 4096, "degree must lie in [1, 4096]");
+    H_ARG(lo < hi && hi < top && std::isfinite(lo) && std::isfinite(top), "the damped interval needs lo < hi < top");
+    H_TRY(hipSetDevice(h->device));
     const double c = 0.5 * (lo + hi), e = 0.5 * (hi - lo);
     // sigma_k = T_{k-1}(x0) / T_k(x0), x0 = (top - c) / e > 1: in (0, 1], so every coefficient below is bounded
     const double sigma1 = e / (top - c);
@@ -616,16 +510,16 @@ int occ_basis_filter(occ_basis *h, int32_t degree, double lo, double hi, double 
     h->slot[0] = y1;  // the result becomes V
     h->slot[1] = y0;
     h->slot[2] = y2;
-    BH_WAIT("occ_basis_filter");
+    H_WAIT("occ_basis_filter");
     return OCC_BASIS_OK;
 }
 
 int occ_basis_gram(occ_basis *h, int32_t which, double *out)
 {
     if (!h) return OCC_BASIS_E_BADARG;
-    BH_ARG((which == 0 || which == 1) && out, "which must be 0 (V'V) or 1 (V' Omega V)");
-    BH_ARG(h->b >= 1, "no block has been set");
-    BH_TRY(hipSetDevice(h->device));
+    H_ARG((which == 0 || which == 1) && out, "which must be 0 (V'V) or 1 (V' Omega V)");
+    H_ARG(h->b >= 1, "no block has been set");
+    H_TRY(hipSetDevice(h->device));
     const int b = h->b, bc = bc_of(b), T = bc / 16, ld = h->ld;
     if (which == 1) {
         const int rc = ensure_w(h);
@@ -633,11 +527,11 @@ int occ_basis_gram(occ_basis *h, int32_t which, double *out)
     }
     hipLaunchKernelGGL(k_basis_gram, dim3(T * (T + 1) / 2), dim3(64 * GRAM_WAVES), 0, h->st, (const double *)blk(h, 0), (const double *)blk(h, which), h->G,
                        h->n, ld, T);
-    BH_TRY(hipGetLastError());
+    H_TRY(hipGetLastError());
     h->stage.resize((size_t)bc * bc);
-    BH_TRY(hipMemcpy2DAsync(h->stage.data(), (size_t)bc * sizeof(double), h->G, (size_t)ld * sizeof(double), (size_t)bc * sizeof(double), (size_t)bc,
+    H_TRY(hipMemcpy2DAsync(h->stage.data(), (size_t)bc * sizeof(double), h->G, (size_t)ld * sizeof(double), (size_t)bc * sizeof(double), (size_t)bc,
                             hipMemcpyDeviceToHost, h->st));
-    BH_WAIT("occ_basis_gram");
+    H_WAIT("occ_basis_gram");
     for (int i = 0; i < b; ++i)
         for (int j = i; j < b; ++j) out[(size_t)i * b + j] = out[(size_t)j * b + i] = h->stage[(size_t)i * bc + j];
     return OCC_BASIS_OK;
@@ -646,20 +540,20 @@ int occ_basis_gram(occ_basis *h, int32_t which, double *out)
 int occ_basis_rotate(occ_basis *h, const double *Y, int32_t b_out)
 {
     if (!h) return OCC_BASIS_E_BADARG;
-    BH_ARG(h->b >= 1, "no block has been set");
-    BH_ARG(Y && b_out >= 1 && b_out <= h->b_max, "b_out must lie in [1, b_max]");
-    BH_TRY(hipSetDevice(h->device));
+    H_ARG(h->b >= 1, "no block has been set");
+    H_ARG(Y && b_out >= 1 && b_out <= h->b_max, "b_out must lie in [1, b_max]");
+    H_TRY(hipSetDevice(h->device));
     const int b = h->b, kend = bc_of(b), ldy = bc_of(b_out), Tout = ldy / 16;
     h->stage.assign((size_t)kend * ldy, 0.0);
     for (int k = 0; k < b; ++k) std::memcpy(&h->stage[(size_t)k * ldy], Y + (size_t)k * b_out, (size_t)b_out * sizeof(double));
-    BH_TRY(hipMemcpyAsync(h->Y, h->stage.data(), h->stage.size() * sizeof(double), hipMemcpyHostToDevice, h->st));
+    H_TRY(hipMemcpyAsync(h->Y, h->stage.data(), h->stage.size() * sizeof(double), hipMemcpyHostToDevice, h->st));
     double *dst = blk(h, 2);
-    BH_TRY(hipMemsetAsync(dst, 0, (size_t)h->n * h->ld * sizeof(double), h->st));
+    H_TRY(hipMemsetAsync(dst, 0, (size_t)h->n * h->ld * sizeof(double), h->st));
     const int nst = (h->n + 15) / 16;
     hipLaunchKernelGGL(k_basis_rotate, dim3((nst + 3) / 4, (Tout + ROT_NJ - 1) / ROT_NJ), dim3(256), 0, h->st, (const double *)blk(h, 0), (const double *)h->Y,
                        dst, h->n, h->ld, kend, ldy, Tout);
-    BH_TRY(hipGetLastError());
-    BH_WAIT("occ_basis_rotate");
+    H_TRY(hipGetLastError());
+    H_WAIT("occ_basis_rotate");
     std::swap(h->slot[0], h->slot[2]);
     h->b = b_out;
     h->w_valid = false;
@@ -669,21 +563,21 @@ int occ_basis_rotate(occ_basis *h, const double *Y, int32_t b_out)
 int occ_basis_residual(occ_basis *h, const double *lam, double *out)
 {
     if (!h) return OCC_BASIS_E_BADARG;
-    BH_ARG(h->b >= 1, "no block has been set");
-    BH_ARG(lam && out, "null input");
-    BH_TRY(hipSetDevice(h->device));
+    H_ARG(h->b >= 1, "no block has been set");
+    H_ARG(lam && out, "null input");
+    H_TRY(hipSetDevice(h->device));
     const int b = h->b, bc = bc_of(b);
     h->stage.assign((size_t)bc, 0.0);
     std::memcpy(h->stage.data(), lam, (size_t)b * sizeof(double));
-    BH_TRY(hipMemcpyAsync(h->lam, h->stage.data(), (size_t)bc * sizeof(double), hipMemcpyHostToDevice, h->st));
+    H_TRY(hipMemcpyAsync(h->lam, h->stage.data(), (size_t)bc * sizeof(double), hipMemcpyHostToDevice, h->st));
     const int rc = ensure_w(h);
     if (rc != OCC_BASIS_OK) return rc;
     hipLaunchKernelGGL(k_basis_res, dim3(h->ntile, (bc + 255) / 256), dim3(256), 0, h->st, (const double *)blk(h, 1), (const double *)blk(h, 0),
                        (const double *)h->lam, h->part, h->n, h->ld, bc);
     hipLaunchKernelGGL(k_basis_res_sum, dim3((bc + 255) / 256), dim3(256), 0, h->st, (const double *)h->part, h->res, h->ntile, h->ld, bc);
-    BH_TRY(hipGetLastError());
-    BH_TRY(hipMemcpyAsync(out, h->res, (size_t)b * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    BH_WAIT("occ_basis_residual");
+    H_TRY(hipGetLastError());
+    H_TRY(hipMemcpyAsync(out, h->res, (size_t)b * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    H_WAIT("occ_basis_residual");
     return OCC_BASIS_OK;
 }
 

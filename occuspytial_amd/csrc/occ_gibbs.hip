@@ -31,6 +31,7 @@
 #include "occ_accum.hpp"
 #include "occ_draws.hpp"
 #include "occ_layout.hpp"
+#include "occ_wait.hpp"
 
 using namespace occ;
 
@@ -350,28 +351,19 @@ static std::string host_state(const occ_sampler *s)
                   (long long)s->graph_launches, (long long)s->eager_iterations, (long long)s->fused_fallbacks);
     return buf;
 }
-static double host_wait_limit_s()
-{
-    const char *e = std::getenv("OCC_HOST_WAIT_S");
-    const double v = e ? std::atof(e) : 20.0;
-    return v > 0.0 ? v : 20.0;
-}
 // hipSuccess when `st` has drained; hipErrorNotReady after the deadline (*late = true); any other error as the runtime gave it
+// (the poll, its cadence and the limit: occ_wait.hpp)
 static hipError_t poll_stream(hipStream_t st, bool *late)
 {
-    *late = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    const double limit = host_wait_limit_s();
-    for (unsigned polls = 1;; ++polls) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q != hipErrorNotReady) return q;
-        (void)hipGetLastError();  // (not ready is not an error to keep)
-        if ((polls & 63u) == 0u) {
-            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (sec > limit) { *late = true; return hipErrorNotReady; }
-            if (sec > 0.002) std::this_thread::yield();  // (a long wait: the host thread need not own a core)
-        }
-    }
+    const WaitResult r = poll_until(
+        [st] {
+            const hipError_t q = hipStreamQuery(st);
+            if (q == hipErrorNotReady) (void)hipGetLastError();  // (not ready is not an error to keep)
+            return (int)q;
+        },
+        (int)hipErrorNotReady, host_wait_limit_s());
+    *late = r.end == WaitEnd::late;
+    return (hipError_t)r.code;
 }
 static int wait_on(occ_sampler *s, hipStream_t st, const char *func, int line)
 {

@@ -20,21 +20,19 @@
 // added in thread order through LDS; the scalar kernels add the tiles in tile order.  So every sum has one fixed order that
 // depends neither on b nor on a grid nor on timing: a column is a CG of its own, and its bits are (Q, key, draw, tol)'s.
 // No kernel waits on the device, none uses an atomic.  alpha, beta, r'z, ||r||^2 and done stay on the device; the host
-// reads only the done flags, every check_every iterations.  One plain stream per handle; every host wait is a deadline poll.
+// reads only the done flags, every check_every iterations.  The handle's device, stream, allocations, deadline wait and
+// create / destroy are occ_handle.hpp's.
 #include "../../include/occ_sim.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
+#include "occ_handle.hpp"
 #include "occ_rng.hpp"
 #include "occ_sim_plan.hpp"
 
@@ -304,10 +302,9 @@ __global__ void __launch_bounds__(256) k_sim_comp_apply(double *__restrict__ X, 
 
 using namespace occ_sim_impl;
 
-struct occ_sim {
-    int device = 0, n = 0, ld = 0, b = 0, b_max = 0, ell_w = 0, nslice = 0, ntile = 0, k = 0, nchunk = 0;
+struct occ_sim : occ::HandleBase {
+    int n = 0, ld = 0, b = 0, b_max = 0, ell_w = 0, nslice = 0, ntile = 0, k = 0, nchunk = 0;
     bool have_u = false;
-    hipStream_t st = nullptr;
     int *sell_ptr = nullptr, *sell_col = nullptr, *list = nullptr, *chunk_start = nullptr, *comp_chunk = nullptr, *comp_size = nullptr;
     uint32_t *site_lab = nullptr;
     double *sell_val = nullptr, *sgn_root = nullptr, *diag = nullptr, *dinv = nullptr;
@@ -317,74 +314,10 @@ struct occ_sim {
     int *done = nullptr, *iters = nullptr;
     int *host_flags = nullptr;   // pinned: done[ld], then iters[ld]
     double *host_res = nullptr;  // pinned: res[ld]
-    std::string err;
 };
+OCC_HANDLE_CODES(OCC_SIM_OK, OCC_SIM_E_BADARG, OCC_SIM_E_HIP);
 
 static thread_local std::string g_create_err;
-
-static double host_wait_limit_s()
-{
-    const char *e = std::getenv("OCC_HOST_WAIT_S");
-    const double v = e ? std::atof(e) : 20.0;
-    return v > 0.0 ? v : 20.0;
-}
-
-// the handle's stream has drained, or the deadline has passed (the manner of the engine's wait_on)
-static int wait_on(occ_sim *h, const char *what)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    const double limit = host_wait_limit_s();
-    for (unsigned polls = 1;; ++polls) {
-        const hipError_t q = hipStreamQuery(h->st);
-        if (q == hipSuccess) return OCC_SIM_OK;
-        if (q != hipErrorNotReady) {
-            h->err = std::string(what) + ": " + hipGetErrorString(q);
-            return OCC_SIM_E_HIP;
-        }
-        (void)hipGetLastError();
-        if ((polls & 63u) == 0u) {
-            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (sec > limit) {
-                char lim[64];
-                std::snprintf(lim, sizeof(lim), "%.0f s", limit);
-                h->err = std::string(what) + ": the stream did not drain within " + lim;
-                return OCC_SIM_E_HIP;
-            }
-            if (sec > 0.002) std::this_thread::yield();
-        }
-    }
-}
-
-#define SH_TRY(expr)                                                    \
-    do {                                                                \
-        const hipError_t e_ = (expr);                                   \
-        if (e_ != hipSuccess) {                                         \
-            h->err = std::string(#expr) + ": " + hipGetErrorString(e_); \
-            return OCC_SIM_E_HIP;                                       \
-        }                                                               \
-    } while (0)
-#define SH_WAIT(what)                     \
-    do {                                  \
-        const int w_ = wait_on(h, what);  \
-        if (w_ != OCC_SIM_OK) return w_;  \
-    } while (0)
-#define SH_ARG(cond, msg)              \
-    do {                               \
-        if (!(cond)) {                 \
-            h->err = (msg);            \
-            return OCC_SIM_E_BADARG;   \
-        }                              \
-    } while (0)
-
-template <class T, class S>
-static int upload(occ_sim *h, T **dst, const std::vector<S> &src)
-{
-    static_assert(sizeof(T) == sizeof(S), "upload: same width");
-    SH_TRY(hipMalloc((void **)dst, std::max<size_t>(src.size(), 1) * sizeof(T)));
-    if (!src.empty()) SH_TRY(hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, h->st));
-    SH_WAIT("upload");  // (the host vector may go away after this)
-    return OCC_SIM_OK;
-}
 
 extern "C" {
 
@@ -392,41 +325,23 @@ int32_t occ_sim_version(void) { return OCC_SIM_VERSION; }
 
 const char *occ_sim_last_error(const occ_sim *h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
-int occ_sim_destroy(occ_sim *h)
-{
-    if (!h) return OCC_SIM_OK;
-    (void)hipSetDevice(h->device);
-    if (h->st) {
-        (void)wait_on(h, "occ_sim_destroy");
-        (void)hipStreamDestroy(h->st);
-    }
-    void *ptrs[] = {h->sell_ptr, h->sell_col, h->list, h->chunk_start, h->comp_chunk, h->comp_size, h->site_lab, h->sell_val, h->sgn_root, h->diag,
-                    h->dinv, h->X, h->U, h->R, h->P, h->AP, h->part_a, h->part_b, h->chunk_sum, h->mean, h->rz, h->rr, h->rr0, h->alpha, h->beta,
-                    h->res, h->done, h->iters};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
-    if (h->host_flags) (void)hipHostFree(h->host_flags);
-    if (h->host_res) (void)hipHostFree(h->host_res);
-    delete h;
-    return OCC_SIM_OK;
-}
+int occ_sim_destroy(occ_sim *h) { return occ::handle_destroy(h, "occ_sim_destroy"); }
 
 static int create_impl(occ_sim *h, int64_t n64, const int32_t *indptr, const int32_t *indices, const double *qdata, const int32_t *labels, int32_t b_max,
                        int32_t device)
 {
     std::string why;
-    if (!occ::sim_check_sizes(n64, b_max, &why)) SH_ARG(false, why);
-    SH_ARG(indptr && indices && qdata && labels, "null input");
+    if (!occ::sim_check_sizes(n64, b_max, &why)) H_ARG(false, why);
+    H_ARG(indptr && indices && qdata && labels, "null input");
     const int n = (int)n64;
     std::vector<int32_t> ip(indptr, indptr + n + 1);
-    if (!occ::layout_q_indptr(n, ip, &why)) SH_ARG(false, why);
+    if (!occ::layout_q_indptr(n, ip, &why)) H_ARG(false, why);
     std::vector<int32_t> ix(indices, indices + ip[n]);
     std::vector<double> qd(qdata, qdata + ip[n]);
     std::vector<int32_t> lab(labels, labels + n);
     occ::SimPlan S;
-    if (!occ::sim_plan_build(n64, ip, ix, qd, lab, b_max, &S, &why)) SH_ARG(false, why);
-    if (!occ::sim_plan_ok(lab, S, &why)) SH_ARG(false, std::string("internal: the plan is wanting: ") + why);
-    h->device = device;
+    if (!occ::sim_plan_build(n64, ip, ix, qd, lab, b_max, &S, &why)) H_ARG(false, why);
+    if (!occ::sim_plan_ok(lab, S, &why)) H_ARG(false, std::string("internal: the plan is wanting: ") + why);
     h->n = n;
     h->b_max = b_max;
     h->ld = S.ld;
@@ -436,72 +351,41 @@ static int create_impl(occ_sim *h, int64_t n64, const int32_t *indptr, const int
     h->k = S.comp.k;
     h->nchunk = S.comp.nchunk();
 
-    int ndev = 0;
-    SH_TRY(hipGetDeviceCount(&ndev));
-    SH_ARG(device >= 0 && device < ndev, "no such device");
-    SH_TRY(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    SH_TRY(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        h->err = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950";
-        return OCC_SIM_E_HIP;
-    }
-    SH_TRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
     int rc;
-    if ((rc = upload(h, &h->sell_ptr, S.sell_ptr)) != OCC_SIM_OK) return rc;
-    if ((rc = upload(h, &h->sell_col, S.sell_col)) != OCC_SIM_OK) return rc;
-    if ((rc = upload(h, &h->sell_val, S.sell_val)) != OCC_SIM_OK) return rc;
-    if ((rc = upload(h, &h->sgn_root, S.sgn_root)) != OCC_SIM_OK) return rc;
-    if ((rc = upload(h, &h->diag, S.diag)) != OCC_SIM_OK) return rc;
-    if ((rc = upload(h, &h->dinv, S.diag_inv)) != OCC_SIM_OK) return rc;
-    if ((rc = upload(h, &h->list, S.comp.list)) != OCC_SIM_OK) return rc;
-    if ((rc = upload(h, &h->chunk_start, S.comp.chunk_start)) != OCC_SIM_OK) return rc;
-    if ((rc = upload(h, &h->comp_chunk, S.comp.comp_chunk)) != OCC_SIM_OK) return rc;
-    if ((rc = upload(h, &h->comp_size, S.comp_size)) != OCC_SIM_OK) return rc;
-    if ((rc = upload(h, &h->site_lab, S.comp.site_lab)) != OCC_SIM_OK) return rc;
-    const size_t ld = (size_t)h->ld, blk_bytes = (size_t)n * ld * sizeof(double);
-    double **blocks[] = {&h->X, &h->U, &h->R, &h->P, &h->AP};
-    for (double **bp : blocks) {
-        SH_TRY(hipMalloc((void **)bp, blk_bytes));
-        SH_TRY(hipMemsetAsync(*bp, 0, blk_bytes, h->st));
-    }
-    SH_TRY(hipMalloc((void **)&h->part_a, (size_t)h->ntile * ld * sizeof(double)));
-    SH_TRY(hipMalloc((void **)&h->part_b, (size_t)h->ntile * ld * sizeof(double)));
-    SH_TRY(hipMalloc((void **)&h->chunk_sum, (size_t)std::max(h->nchunk, 1) * ld * sizeof(double)));
-    SH_TRY(hipMalloc((void **)&h->mean, (size_t)std::max(h->k, 1) * ld * sizeof(double)));
-    double **scal[] = {&h->rz, &h->rr, &h->rr0, &h->alpha, &h->beta, &h->res};
-    for (double **sp : scal) {
-        SH_TRY(hipMalloc((void **)sp, ld * sizeof(double)));
-        SH_TRY(hipMemsetAsync(*sp, 0, ld * sizeof(double), h->st));
-    }
-    SH_TRY(hipMalloc((void **)&h->done, ld * sizeof(int)));
-    SH_TRY(hipMalloc((void **)&h->iters, ld * sizeof(int)));
-    SH_TRY(hipMemsetAsync(h->done, 0, ld * sizeof(int), h->st));
-    SH_TRY(hipMemsetAsync(h->iters, 0, ld * sizeof(int), h->st));
-    SH_TRY(hipHostMalloc((void **)&h->host_flags, 2 * ld * sizeof(int), hipHostMallocDefault));
-    SH_TRY(hipHostMalloc((void **)&h->host_res, ld * sizeof(double), hipHostMallocDefault));
-    SH_WAIT("occ_sim_create");
+    if ((rc = h->open(device)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->sell_ptr, S.sell_ptr)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->sell_col, S.sell_col)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->sell_val, S.sell_val)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->sgn_root, S.sgn_root)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->diag, S.diag)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->dinv, S.diag_inv)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->list, S.comp.list)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->chunk_start, S.comp.chunk_start)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->comp_chunk, S.comp.comp_chunk)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->comp_size, S.comp_size)) != OCC_SIM_OK) return rc;
+    if ((rc = h->upload(&h->site_lab, S.comp.site_lab)) != OCC_SIM_OK) return rc;
+    const size_t ld = (size_t)h->ld;
+    for (double **bp : {&h->X, &h->U, &h->R, &h->P, &h->AP})
+        if ((rc = h->alloc(bp, (size_t)n * ld, true)) != OCC_SIM_OK) return rc;
+    if ((rc = h->alloc(&h->part_a, (size_t)h->ntile * ld, false)) != OCC_SIM_OK) return rc;
+    if ((rc = h->alloc(&h->part_b, (size_t)h->ntile * ld, false)) != OCC_SIM_OK) return rc;
+    if ((rc = h->alloc(&h->chunk_sum, (size_t)std::max(h->nchunk, 1) * ld, false)) != OCC_SIM_OK) return rc;
+    if ((rc = h->alloc(&h->mean, (size_t)std::max(h->k, 1) * ld, false)) != OCC_SIM_OK) return rc;
+    for (double **sp : {&h->rz, &h->rr, &h->rr0, &h->alpha, &h->beta, &h->res})
+        if ((rc = h->alloc(sp, ld, true)) != OCC_SIM_OK) return rc;
+    if ((rc = h->alloc(&h->done, ld, true)) != OCC_SIM_OK) return rc;
+    if ((rc = h->alloc(&h->iters, ld, true)) != OCC_SIM_OK) return rc;
+    if ((rc = h->alloc_pinned(&h->host_flags, 2 * ld)) != OCC_SIM_OK) return rc;
+    if ((rc = h->alloc_pinned(&h->host_res, ld)) != OCC_SIM_OK) return rc;
+    H_WAIT("occ_sim_create");
     return OCC_SIM_OK;
 }
 
 int occ_sim_create(int64_t n, const int32_t *q_indptr, const int32_t *q_indices, const double *q_data, const int32_t *labels, int32_t b_max,
                    int32_t device, occ_sim **out)
 {
-    if (!out) {
-        g_create_err = "null output pointer";
-        return OCC_SIM_E_BADARG;
-    }
-    *out = nullptr;
-    occ_sim *h = new occ_sim();
-    const int rc = create_impl(h, n, q_indptr, q_indices, q_data, labels, b_max, device);
-    if (rc != OCC_SIM_OK) {
-        g_create_err = h->err;
-        (void)hipGetLastError();
-        occ_sim_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return OCC_SIM_OK;
+    return occ::handle_create(out, g_create_err, "occ_sim_destroy",
+                              [&](occ_sim *h) { return create_impl(h, n, q_indptr, q_indices, q_data, labels, b_max, device); });
 }
 
 int occ_sim_info(const occ_sim *h, double *info6)
@@ -520,14 +404,14 @@ int occ_sim_draw(occ_sim *h, uint64_t key, int64_t first, int32_t b)
 {
     if (!h) return OCC_SIM_E_BADARG;
     std::string why;
-    if (!occ::sim_check_draw(first, b, h->b_max, &why)) SH_ARG(false, why);
-    SH_TRY(hipSetDevice(h->device));
+    if (!occ::sim_check_draw(first, b, h->b_max, &why)) H_ARG(false, why);
+    H_TRY(hipSetDevice(h->device));
     const int bc = occ::sim_bc(b);
     h->have_u = false;
     hipLaunchKernelGGL(k_sim_draw, dim3(h->ntile, bc / 16), dim3(256), 0, h->st, h->U, (const int *)h->sell_ptr, (const int *)h->sell_col,
                        (const double *)h->sgn_root, h->ell_w, key, (uint32_t)first, h->n, h->ld, (int)b);
-    SH_TRY(hipGetLastError());
-    SH_WAIT("occ_sim_draw");
+    H_TRY(hipGetLastError());
+    H_WAIT("occ_sim_draw");
     h->b = b;
     h->have_u = true;
     return OCC_SIM_OK;
@@ -549,16 +433,16 @@ int occ_sim_solve(occ_sim *h, double tol, int64_t max_iter, int32_t check_every,
 {
     if (!h) return OCC_SIM_E_BADARG;
     std::string why;
-    if (!occ::sim_check_solve(tol, max_iter, check_every, &why)) SH_ARG(false, why);
-    SH_ARG(h->have_u && h->b >= 1, "no right-hand side has been drawn");
-    SH_TRY(hipSetDevice(h->device));
+    if (!occ::sim_check_solve(tol, max_iter, check_every, &why)) H_ARG(false, why);
+    H_ARG(h->have_u && h->b >= 1, "no right-hand side has been drawn");
+    H_TRY(hipSetDevice(h->device));
     const int b = h->b, bc = occ::sim_bc(b), ld = h->ld, n = h->n, nt = h->ntile;
     const dim3 grid(nt, bc / 16), blk(256);
     const double tol2 = tol * tol;
     hipLaunchKernelGGL(k_sim_start, grid, blk, 0, h->st, (const double *)h->U, (const double *)h->dinv, h->X, h->R, h->P, h->part_a, h->part_b, n, ld);
     hipLaunchKernelGGL(k_sim_scal_start, dim3(1), dim3(64), 0, h->st, (const double *)h->part_a, (const double *)h->part_b, h->rz, h->rr, h->rr0, h->alpha,
                        h->beta, h->done, h->iters, nt, ld, bc);
-    SH_TRY(hipGetLastError());
+    H_TRY(hipGetLastError());
     bool all_done = false;
     for (int64_t it = 0; it < max_iter && !all_done;) {
         const int64_t stop = std::min<int64_t>(max_iter, it + check_every);
@@ -575,9 +459,9 @@ int occ_sim_solve(occ_sim *h, double tol, int64_t max_iter, int32_t check_every,
             hipLaunchKernelGGL(k_sim_dir, grid, blk, 0, h->st, h->P, (const double *)h->R, (const double *)h->dinv, (const double *)h->beta,
                                (const int *)h->done, n, ld);
         }
-        SH_TRY(hipGetLastError());
-        SH_TRY(hipMemcpyAsync(h->host_flags, h->done, (size_t)bc * sizeof(int), hipMemcpyDeviceToHost, h->st));
-        SH_WAIT("occ_sim_solve");
+        H_TRY(hipGetLastError());
+        H_TRY(hipMemcpyAsync(h->host_flags, h->done, (size_t)bc * sizeof(int), hipMemcpyDeviceToHost, h->st));
+        H_WAIT("occ_sim_solve");
         all_done = true;
         for (int c = 0; c < bc; ++c) all_done = all_done && h->host_flags[c] != 0;
     }
@@ -585,11 +469,11 @@ int occ_sim_solve(occ_sim *h, double tol, int64_t max_iter, int32_t check_every,
     hipLaunchKernelGGL(k_sim_spmv<1>, grid, blk, 0, h->st, (const double *)h->X, (double *)nullptr, (const double *)h->U, (const double *)h->diag,
                        (const int *)h->sell_ptr, (const int *)h->sell_col, (const double *)h->sell_val, h->ell_w, (const int *)h->done, h->part_a, n, ld);
     hipLaunchKernelGGL(k_sim_scal_res, dim3(1), dim3(64), 0, h->st, (const double *)h->part_a, (const double *)h->rr0, h->res, nt, ld, bc);
-    SH_TRY(hipGetLastError());
-    SH_TRY(hipMemcpyAsync(h->host_flags, h->done, (size_t)bc * sizeof(int), hipMemcpyDeviceToHost, h->st));
-    SH_TRY(hipMemcpyAsync(h->host_flags + ld, h->iters, (size_t)bc * sizeof(int), hipMemcpyDeviceToHost, h->st));
-    SH_TRY(hipMemcpyAsync(h->host_res, h->res, (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    SH_WAIT("occ_sim_solve");
+    H_TRY(hipGetLastError());
+    H_TRY(hipMemcpyAsync(h->host_flags, h->done, (size_t)bc * sizeof(int), hipMemcpyDeviceToHost, h->st));
+    H_TRY(hipMemcpyAsync(h->host_flags + ld, h->iters, (size_t)bc * sizeof(int), hipMemcpyDeviceToHost, h->st));
+    H_TRY(hipMemcpyAsync(h->host_res, h->res, (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, h->st));
+    H_WAIT("occ_sim_solve");
     if (info)
         for (int c = 0; c < b; ++c) {
             info[c] = (double)h->host_flags[ld + c];
@@ -604,20 +488,20 @@ int occ_sim_solve(occ_sim *h, double tol, int64_t max_iter, int32_t check_every,
         }
     launch_centre(h, bc);
     launch_centre(h, bc);
-    SH_TRY(hipGetLastError());
-    SH_WAIT("occ_sim_solve");
+    H_TRY(hipGetLastError());
+    H_WAIT("occ_sim_solve");
     return OCC_SIM_OK;
 }
 
 int occ_sim_get(occ_sim *h, int32_t which, double *out, int32_t b)
 {
     if (!h) return OCC_SIM_E_BADARG;
-    SH_ARG((which == 0 || which == 1) && out, "which must be 0 (x) or 1 (u)");
-    SH_ARG(b >= 1 && b <= h->b_max, "b must lie in [1, b_max]");
-    SH_TRY(hipSetDevice(h->device));
-    SH_TRY(hipMemcpy2DAsync(out, (size_t)b * sizeof(double), which == 0 ? h->X : h->U, (size_t)h->ld * sizeof(double), (size_t)b * sizeof(double),
+    H_ARG((which == 0 || which == 1) && out, "which must be 0 (x) or 1 (u)");
+    H_ARG(b >= 1 && b <= h->b_max, "b must lie in [1, b_max]");
+    H_TRY(hipSetDevice(h->device));
+    H_TRY(hipMemcpy2DAsync(out, (size_t)b * sizeof(double), which == 0 ? h->X : h->U, (size_t)h->ld * sizeof(double), (size_t)b * sizeof(double),
                             (size_t)h->n, hipMemcpyDeviceToHost, h->st));
-    SH_WAIT("occ_sim_get");
+    H_WAIT("occ_sim_get");
     return OCC_SIM_OK;
 }
 

@@ -183,6 +183,32 @@ def test_bad_arguments_are_refused():
     ops.close()
 
 
+def test_a_refused_create_leaves_the_library_usable_and_close_is_idempotent():
+    """10 x 13 queen lattice, n = 130 (three SELL-64 slices, the last partial; one partial tile of 256 sites), p = 2, b = 5 padded
+    to 16 columns.  A device number past the last is the bad-argument path: nothing is launched."""
+    from occuspytial_amd import _lib
+    from occuspytial_amd._basis_lib import DeviceBasisOps
+    from occuspytial_amd.utils import rand_precision_mat
+    n, b = 130, 5
+    Q = sparse.csr_matrix(rand_precision_mat(10, 13)).astype(float)
+    X = np.column_stack([np.ones(n), np.random.default_rng(5).standard_normal(n)])
+    with pytest.raises(ValueError, match='no such device'):
+        DeviceBasisOps(Q, X, b, device=_lib.load().occ_device_count())
+    ops = DeviceBasisOps(Q, X, b, device=0)
+    assert (ops.ld, ops.info()['ell_w']) == (16, 8)
+    V = np.random.default_rng(11).standard_normal((n, b))
+    ops.set_block(V)
+    omega, _, _ = dense_omega(Q, X)
+    G = ops.gram(1)
+    norms = np.linalg.norm(V, axis=0)
+    err = (np.abs(G - V.T @ (omega @ V)) / (np.outer(norms, norms) * np.abs(np.linalg.eigvalsh(omega)).max())).max()
+    print('gram(1) after a refused create: worst relative error', err, 'bound', 1e-13 * n)
+    assert err <= 1e-13 * n                                  # (test_gram's bound)
+    ops.close()
+    ops.close()                                              # a second close is a no-op
+    assert not ops._h
+
+
 # ------------------------------------------------------------------ end to end, 30 x 40, p = 2
 @pytest.fixture(scope='module')
 def e2e():

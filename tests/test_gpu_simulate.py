@@ -219,6 +219,42 @@ def test_a_column_that_is_not_done_is_an_error_and_the_handle_lives():
     assert str(e.value) == REFUSALS['singular']
 
 
+def test_a_refused_create_leaves_the_library_usable_and_close_is_idempotent():
+    """10 x 13 queen lattice, n = 130 (three SELL-64 slices, the last partial; one partial tile of 256 sites), cut into rows 0-4,
+    rows 5-9 without the last site, and the last site alone; b = 5 padded to 16 columns.  A device number past the last is the
+    bad-argument path: nothing is launched.  The bounds are those of tests 2 and 3 above."""
+    from occuspytial_amd import _lib
+    from occuspytial_amd._sim_lib import DeviceFieldOps
+    from occuspytial_amd.graph import components
+    from occuspytial_amd.utils import lattice_adjacency
+    n, b = 130, 5
+    part = (np.arange(n) >= 65).astype(int)
+    part[n - 1] = 2
+    W = lattice_adjacency(10, 13, 'queen').tocoo()
+    keep = part[W.row] == part[W.col]
+    W = sparse.csr_matrix((W.data[keep].astype(float), (W.row[keep], W.col[keep])), shape=(n, n))
+    Q = (sparse.diags(np.asarray(W.sum(axis=1)).ravel()) - W).tocsr()
+    k, labels = components(Q)
+    assert k == 3 and np.bincount(labels).tolist() == [65, 64, 1]
+    with pytest.raises(ValueError, match='no such device'):
+        DeviceFieldOps(Q, labels, b, device=_lib.load().occ_device_count())
+    ops = DeviceFieldOps(Q, labels, b, device=0)
+    assert (ops.info()['ld'], ops.info()['components']) == (16, 3)
+    ops.draw(KEY, 0, b)
+    info = ops.solve(tol=TOL)
+    X, U = ops.get(0), ops.get(1)
+    res = np.linalg.norm(U - Q @ X, axis=0) / np.linalg.norm(U, axis=0)
+    sums = np.abs(sparse.csr_matrix((np.ones(n), (labels, np.arange(n))), shape=(k, n)) @ X)
+    bound = n * 2.0 ** -52 * np.abs(X).max()
+    print('after a refused create: reported residual', info['residual'].max(), 'recomputed', res.max(), 'bound', 2 * TOL, 'worst component sum',
+          sums.max(), 'bound', bound)
+    assert info['residual'].max() <= TOL and res.max() <= 2 * TOL
+    assert sums.max() <= bound and np.all(X[n - 1] == 0.0) and np.all(U[n - 1] == 0.0)
+    ops.close()
+    ops.close()                                                # a second close is a no-op
+    assert not ops._h
+
+
 # ------------------------------------------------------------------ 7. Python, end to end
 def test_icar_field_tau_and_batch():
     from occuspytial_amd.simulate import icar_field

@@ -37,8 +37,11 @@ def test_every_hist_state_name_is_in_header_and_binding():
     # the switch is a word of the handle and the kernel is launched behind the z update: the planner does not know of it
     assert 'hist' not in open(os.path.join(ROOT, 'occuspytial_amd', 'csrc', 'occ_plan.hpp')).read()
     makefile = open(os.path.join(ROOT, 'occuspytial_amd', 'csrc', 'Makefile')).read()
-    assert len(re.findall(r'-shared -o \$@ occ_gibbs\.hip occ_spatial\.hip occ_hist\.hip', makefile)) == 2
-    assert re.search(r'^SRC := .*\bocc_hist\.hip\b.*\bocc_hist\.hpp\b', makefile, flags=re.M)
+    # (the translation units are named once, in UNITS: the library and the stamps build compile them, SRC makes both depend on them)
+    units = re.search(r'^UNITS := (.*)$', makefile, flags=re.M).group(1).split()
+    assert units[:3] == ['occ_gibbs.hip', 'occ_spatial.hip', 'occ_hist.hip']
+    assert len(re.findall(r'-shared -o \$@ \$\(UNITS\)$', makefile, flags=re.M)) == 2
+    assert re.search(r'^SRC := \$\(UNITS\) .*\bocc_hist\.hpp\b', makefile, flags=re.M)
 
 
 def test_the_kernel_is_launched_only_while_a_switch_is_on():

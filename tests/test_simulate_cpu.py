@@ -98,6 +98,38 @@ def test_icar_field_refuses_before_a_handle_exists(monkeypatch):
             icar_field(Q, batch=batch)
 
 
+def test_icar_field_without_the_library_is_an_error(monkeypatch, tmp_path):
+    from occuspytial_amd import _sim_lib
+    from occuspytial_amd._lib import EngineUnavailable
+    monkeypatch.setattr(_sim_lib, 'LIB_PATH', str(tmp_path / 'libocc_sim.so'))
+    monkeypatch.setattr(_sim_lib, '_lib', None)
+    with pytest.raises(EngineUnavailable, match='libocc_sim.so is missing.*There is no CPU fallback for icar_field'):
+        icar_field(lattice(5, 6))
+    assert _sim_lib._lib is None
+
+
+def test_csr_arrays_are_what_the_libraries_take():
+    from occuspytial_amd._native import csr_arrays
+    # row 0 holds (0, 2) twice and its columns out of order; as COO, so that nothing is summed or sorted beforehand
+    rows, cols = [0, 0, 0, 0, 1, 2, 2], [2, 0, 2, 1, 1, 2, 0]
+    vals = [-1.0, 3, -1.0, -1, 1, 2, -2]
+    Q = sparse.coo_matrix((np.array(vals, dtype=np.float32), (rows, cols)), shape=(3, 3))
+    n, indptr, indices, data = csr_arrays(Q)
+    assert n == 3 and indptr.tolist() == [0, 3, 4, 6] and indices.tolist() == [0, 1, 2, 1, 0, 2]
+    assert data.tolist() == [3.0, -1.0, -2.0, 1.0, -2.0, 2.0]
+    assert (indptr.dtype, indices.dtype, data.dtype) == (np.int32, np.int32, np.float64)
+    assert all(a.flags['C_CONTIGUOUS'] and a.ndim == 1 for a in (indptr, indices, data))
+    assert Q.nnz == 7                                          # the caller's matrix is left as it was
+    same = csr_arrays(Q.toarray(), 3)                          # a dense array, and n given: the same arrays
+    assert same[0] == 3 and all(np.array_equal(a, b) for a, b in zip(same[1:], (indptr, indices, data)))
+    with pytest.raises(ValueError, match='^Q must be square$'):
+        csr_arrays(sparse.csr_matrix(np.ones((3, 4))))
+    with pytest.raises(ValueError, match=r'^Q must be n x n with n = X.shape\[0\]$'):
+        csr_arrays(Q, 4)
+    with pytest.raises(ValueError, match=r'^Q must be n x n with n = X.shape\[0\]$'):
+        csr_arrays(sparse.csr_matrix(np.ones((3, 4))), 3)
+
+
 def test_make_spatial_data_contract():
     from occuspytial_amd._problem import FlatProblem
     Q = lattice()
