@@ -30,6 +30,7 @@
 #include "occ_holdout.hpp"
 #include "occ_accum.hpp"
 #include "occ_draws.hpp"
+#include "occ_call.hpp"
 #include "occ_layout.hpp"
 #include "occ_wait.hpp"
 
@@ -151,12 +152,12 @@ struct occ_sampler {
     // family drops them) and which records a call opens.
     uint32_t outputs_on = 0u;
     int z_ob_kind() const { return output_level(outputs_on); }
-    // per-site running sums, kind by kind (SUMS): part of what a call is re-run from.  snap: [nacc C n] sums, then [C]
-    // counts; snapped: taken for the running call.
-    struct SumsRun {
-        bool snapped = false;
-        double *snap = nullptr;
-    } sums[N_SUMS];
+    // per-site running sums, kind by kind (SUMS): part of what a call is re-run from.  snap: [nacc C n] sums, then [C] counts.
+    struct SumsRun { double *snap = nullptr; } sums[N_SUMS];
+    // What the running call is re-run from beside eta, z, x (theta): the sums and accumulators that are on, sums then counts of
+    // each, as open_window copied them (live -> snap) and fallback_to_launch_per_step copies them back.
+    struct RerunPart { void *live, *snap; size_t bytes; } rerun[2 * (N_SUMS + N_ACCUM)];
+    int n_rerun = 0;
     // The record of one occ_run of one kind of draws (occ_draws.hpp: DRAWS), [C][keep][width] elements of the kind's size, in
     // bytes: `rec` on the device, sized like rec_buf and grown between calls, zeroed on the stream when the call's window
     // opens and copied out (pin) behind its last batch; last: that of the last completed occ_run on the host, for the chains
@@ -204,11 +205,11 @@ struct occ_sampler {
     } spatial;
     // An accumulator behind the z update (occ_accum.hpp: ACCUM; logit models).  ready: its arrays are on the device -- data,
     // [slots][C][unit] elements, count, [C], and the switches; unit: the per-chain, per-slot length the data were allocated for.
-    // snap: the data, then the counts, part of what a call is re-run from; snapped: taken for the running call.  The kinds
+    // snap: the data, then the counts, part of what a call is re-run from.  The kinds
     // add their kernel's argument block, filled from here (the addresses and B, L or the sizes travel by value in the captured
     // launches: a change drops them).
     struct AccumRun : Switches {
-        bool ready = false, snapped = false;
+        bool ready = false;
         uint8_t *data = nullptr, *count = nullptr, *snap = nullptr;
         size_t unit = 0;
     };
@@ -247,7 +248,7 @@ struct occ_sampler {
     int64_t stream_probes = 0, repromotions = 0;
     unsigned *sync_buf = nullptr;     // the hand-over counters (Ctx::sync points here while they are in use)
     bool demoted = false;             // running without device-side waits after one of them gave up (back to `plan`: try_repromote)
-    int promote_wait = 0, promote_backoff = 1;  // calls until the next attempt to come back; doubled after a failed one
+    Backoff promote;                  // calls until the next attempt to come back (occ_call.hpp)
     std::string pair_note;            // why the engine did not get the masked pair it wanted (empty: it did, or wanted none)
     // The chains' scalars as the last occ_run / occ_step read them at its end (round 3: a call of a dozen iterations was mostly
     // host round trips -- ~170 us per occ_run beyond its iterations).  ONE flag says whether the device still holds exactly
@@ -269,7 +270,7 @@ struct occ_sampler {
     std::vector<std::pair<const char *, std::chrono::steady_clock::time_point>> stamps;
     bool debug_close_window = false;  // tests (occ_set_state "debug_close_window"): the NEXT call's window is opened with zero iterations on the device
     bool wedged = false;           // a host wait ran into its deadline: the streams never drained; nothing of this engine is freed or reused
-    int probe_wait = 0, probe_backoff = 1;  // calls until the stream probe is asked again after a negative answer
+    Backoff probe;                 // calls until the stream probe is asked again after a negative answer
     int graph_parity = 0;    // fused mode: sequence parity the captured pair of iterations starts with
     std::vector<void *> allocs;
     std::string err;
@@ -1042,23 +1043,26 @@ int open_window(occ_sampler *s, int64_t n_iter, int64_t burnin, int64_t keep, bo
         }
         s->snap_sc = h;
         s->snap_parity = s->parity;
+        s->n_rerun = 0;
+        auto part = [&](void *live, void *snap, size_t bytes) {  // -> the list, and the copy behind what the stream holds
+            s->rerun[s->n_rerun++] = {live, snap, bytes};
+            return hipMemcpyAsync(snap, live, bytes, hipMemcpyDeviceToDevice, s->stream);
+        };
         for (int k = 0; k < N_SUMS; ++k) {  // the per-site sums are part of what the call is re-run from: no iteration is counted twice
             occ_sampler::SumsRun &r = s->sums[k];
             const size_t nsum = (size_t)SUMS[k].nacc * Cn;
-            r.snapped = (s->outputs_on & SUMS[k].bit) != 0u;
-            if (!r.snapped) continue;
+            if (!(s->outputs_on & SUMS[k].bit)) continue;
             if (!r.snap && (rc = dev_alloc(s, &r.snap, nsum + (size_t)c.C, false))) return rc;
-            HIP_TRY(hipMemcpyAsync(r.snap, c.*SUMS[k].acc, sizeof(double) * nsum, hipMemcpyDeviceToDevice, s->stream));
-            HIP_TRY(hipMemcpyAsync(r.snap + nsum, c.*SUMS[k].count, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(part(c.*SUMS[k].acc, r.snap, sizeof(double) * nsum));
+            HIP_TRY(part(c.*SUMS[k].count, r.snap + nsum, sizeof(double) * (size_t)c.C));
         }
         for (int k = 0; k < N_ACCUM; ++k) {  // ... and so are the accumulators behind the z update, in bytes: data, then counts
             occ_sampler::AccumRun &r = s->accum(k);
             const size_t nd = (size_t)ACCUM[k].elem * accum_words(ACCUM[k], (size_t)c.C, r.unit), nc = (size_t)ACCUM[k].elem * (size_t)c.C;
-            r.snapped = r.any != 0u;
-            if (!r.snapped) continue;
+            if (!r.any) continue;
             if (!r.snap && (rc = dev_alloc(s, &r.snap, nd + nc, false))) return rc;
-            HIP_TRY(hipMemcpyAsync(r.snap, r.data, nd, hipMemcpyDeviceToDevice, s->stream));
-            HIP_TRY(hipMemcpyAsync(r.snap + nd, r.count, nc, hipMemcpyDeviceToDevice, s->stream));
+            HIP_TRY(part(r.data, r.snap, nd));
+            HIP_TRY(part(r.count, r.snap + nd, nc));
         }
         hipLaunchKernelGGL(k_snapshot, dim3((unsigned)std::min<size_t>((Cn + 255) / 256, 2048)), dim3(256), 0, s->stream, c.eta, s->snap_eta, c.z, s->snap_z, c.Xv, s->snap_x,
                            (unsigned long long)Cn, s->rsr.m > 0 ? s->rsr.theta : nullptr, s->snap_theta, (unsigned long long)c.C * (unsigned long long)std::max(s->rsr.m, 0),
@@ -2049,7 +2053,7 @@ static int create_impl(occ_sampler *s, const HostLayout &L, int32_t n_chains, co
                 if ((rc = stream_probe(s, &beside))) return rc;
                 if (!beside) {  // hand-overs by event nodes (ICAR) / everything on one stream (reduced-rank model); asked again at
                     s->run.flag_sync = false, s->streams_serialised = true;  // the head of the next call (refresh_paths)
-                    s->probe_wait = s->probe_backoff = 1;
+                    s->probe.arm();
                 }
             }
         } else if (std::getenv("OCC_VERBOSE")) {
@@ -2795,60 +2799,33 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
     stamp(s, "ev0");
     s->marks_done = false;
 
-    // calibration (no graph yet): a few eager sequences measure the Krylov launches a solve needs;
-    // the count of the last, warm-started solve sizes the captured graph
+    // what stands in front of the first batch (occ_call.hpp: call_head), step by step
     const SeqMode mode = seq_mode(s);
     const SeqSolve solve = seq_solve(s, false);
     const int64_t seq_per_enqueue = sequences_per_enqueue(mode);
     int64_t done_min = 0;
     const char *force = std::getenv("OCC_FORCE_KRYLOV_CAP");  // tests
-    if (std::getenv("OCC_EAGER_ONLY")) {  // counter collection cannot follow graph launches: same kernels, eager
-        for (int64_t i = 0; i < n_iter; ++i)
-            if ((rc = eager_sequence(s))) return rc;
-        done_min = n_iter;
-    } else if (solve == SOLVE_FUSED && seq_per_enqueue == 1) {
-        if (!s->head[0] && (rc = build_graph(s, 0))) return rc;  // the solve is one launch: nothing to calibrate
-        if (s->need_prologue && (rc = launch_prologue(s))) return rc;
-    } else if (seq_per_enqueue > 1) {
-        if (s->need_prologue && (rc = launch_prologue(s))) return rc;
-        // the solve is one launch: nothing to calibrate.  The captured pair of iterations starts with one
-        // sequence parity: an odd number of stepped iterations since the capture is realigned by one more step.
-        if (s->head[0] && s->parity != s->graph_parity) {
-            if ((rc = eager_sequence(s))) return rc;
-            done_min = 1;
-        }
-        // (the long pair of graphs with the short one, whatever this call's length: no later call captures anything)
-        if (!s->head[0] && n_iter > 1 && (rc = build_graph(s, 0, true))) return rc;
-        if (n_iter == 1 && done_min == 0) {
-            if ((rc = eager_sequence(s))) return rc;
-            done_min = 1;
-        }
-    } else if (!s->head[0]) {
-        const int64_t n_calib = std::min<int64_t>(n_iter, 3);
-        s->calib_max = 0;
-        for (int64_t i = 0; i < n_calib; ++i) {
-            if (i == n_calib - 1) s->calib_max = 0;
+    const CallHead head = call_head(std::getenv("OCC_EAGER_ONLY") != nullptr, solve, seq_per_enqueue, s->head[0] != nullptr, s->parity == s->graph_parity, n_iter, s->need_prologue);
+    for (int i = 0; i < head.n; ++i) {
+        const HeadStep &st = head.step[i];
+        if (st.kind == HEAD_PROLOGUE && (rc = launch_prologue(s))) return rc;
+        if (st.kind == HEAD_BUILD && (rc = build_graph(s, st.from_calib ? cap_from_calibration(s->calib_max, force) : 0, st.long_pair))) return rc;
+        for (int64_t k = 0; k < st.n; ++k) {  // HEAD_EAGER, HEAD_CALIBRATE
+            if (st.kind == HEAD_CALIBRATE && (k == 0 || k == st.n - 1)) s->calib_max = 0;
             if ((rc = eager_sequence(s))) return rc;
         }
-        done_min = n_calib;
-        int cap = std::max(4, s->calib_max + 2);
-        if (force) cap = std::max(1, std::atoi(force));
-        if (done_min < n_iter && (rc = build_graph(s, cap))) return rc;
-    } else if (s->need_prologue) {
-        if ((rc = launch_prologue(s))) return rc;
+        done_min += st.n;
     }
     // the first side chain waits for "the previous k_z_ob": everything enqueued so far
     if (done_min < n_iter && (mode == SEQ_EVENT_NODES || mode == SEQ_STREAM_EVENTS)) HIP_TRY(hipEventRecord(s->ev_z[s->parity ^ 1], s->stream));
 
     // (iteration, launches spent on a carried solve) of every chain after the previous batch: every sequence moves every
     // unfinished chain -- by one iteration, or by the captured launches of a solve it carries on (Ctl::koff)
-    std::vector<std::pair<uint32_t, uint32_t>> seen((size_t)C, {0xffffffffu, 0xffffffffu});
+    std::vector<SeenAt> seen((size_t)C, {0xffffffffu, 0xffffffffu});
     while (done_min < n_iter) {
         // every sequence advances each unfinished chain by one iteration, or (rarely) carries its eta
         // solve into the next sequence; finished chains idle.  No host work inside a batch.
-        const int64_t left = n_iter - done_min;
-        int64_t batch = std::min<int64_t>(left, s->graph_launches < 128 ? 32 : 256);
-        batch = (batch + seq_per_enqueue - 1) / seq_per_enqueue * seq_per_enqueue;  // a surplus sequence idles (it_stop)
+        const int64_t batch = call_batch(n_iter - done_min, s->graph_launches, seq_per_enqueue);
         const auto hl0 = std::chrono::steady_clock::now();
         stamp(s, "first enqueue reached");
         for (int64_t b = 0; b < batch;) {  // long replays while that many sequences are left, then short ones (graph_len)
@@ -2869,33 +2846,26 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
                          std::chrono::duration<double, std::micro>(hl2 - hl0).count() / batch);
         }
         if ((rc = check_device_errors(s, h))) return rc;
-        done_min = n_iter;
         unsigned long long tot = 0, sq = 0, solves = 0;
-        for (int ch = 0; ch < C; ++ch) {
-            done_min = std::min<int64_t>(done_min, (int64_t)h[ch].ctl[s->parity].it - (int64_t)h[ch].it_base);
-            tot += h[ch].krylov_total; sq += h[ch].krylov_sq_total; solves += h[ch].solves;
-        }
+        for (int ch = 0; ch < C; ++ch) { tot += h[ch].krylov_total; sq += h[ch].krylov_sq_total; solves += h[ch].solves; }
         // A batch that leaves an unfinished chain exactly where it was -- same iteration, same carried launches, no error
         // word -- cannot happen while the chain's window is open on the device: the call ends with what it saw instead of
         // enqueuing idle sequences for ever (round 3 recorded a call that never returned; the text below is what
         // a recurrence reports).
-        for (int ch = 0; ch < C; ++ch) {
-            const Ctl &ctl = h[ch].ctl[s->parity];
-            const bool unfinished = (int64_t)ctl.it - (int64_t)h[ch].it_base < n_iter;
-            if (unfinished && seen[(size_t)ch].first == ctl.it && seen[(size_t)ch].second == ctl.koff) {
-                std::string msg = "no progress: a batch of " + std::to_string((long long)batch) + " sequences left chain " + std::to_string(ch) +
-                                  " where it was (the window of iterations is not open on the device?); per chain {it, koff | other parity | mid | it_base, it_stop, err}:";
-                for (int k2 = 0; k2 < C && k2 < 16; ++k2) {
-                    const ChainScalars &q2 = h[k2];
-                    char b[192];
-                    std::snprintf(b, sizeof(b), " [%d] {%u, %u | %u, %u | %u, %u / %u, %u | %u, %u, %d}", k2, q2.ctl[s->parity].it, q2.ctl[s->parity].koff, q2.ctl[s->parity ^ 1].it,
-                                  q2.ctl[s->parity ^ 1].koff, q2.mid[0].it, q2.mid[0].koff, q2.mid[1].it, q2.mid[1].koff, q2.it_base, q2.it_stop, (int)q2.err);
-                    msg += b;
-                }
-                msg += "; the host wanted " + std::to_string((long long)n_iter) + " iterations, done_min " + std::to_string((long long)done_min) + "; " + host_state(s);
-                return set_error(s, OCC_E_HIP, msg.c_str());
+        const CallProgress pr = call_progress(C, [&](int ch) { return ChainAt{h[ch].ctl[s->parity].it, h[ch].ctl[s->parity].koff, h[ch].it_base}; }, seen.data(), n_iter);
+        done_min = pr.done_min;
+        if (pr.stuck >= 0) {
+            std::string msg = "no progress: a batch of " + std::to_string((long long)batch) + " sequences left chain " + std::to_string(pr.stuck) +
+                              " where it was (the window of iterations is not open on the device?); per chain {it, koff | other parity | mid | it_base, it_stop, err}:";
+            for (int k2 = 0; k2 < C && k2 < 16; ++k2) {
+                const ChainScalars &q2 = h[k2];
+                char b[192];
+                std::snprintf(b, sizeof(b), " [%d] {%u, %u | %u, %u | %u, %u / %u, %u | %u, %u, %d}", k2, q2.ctl[s->parity].it, q2.ctl[s->parity].koff, q2.ctl[s->parity ^ 1].it,
+                              q2.ctl[s->parity ^ 1].koff, q2.mid[0].it, q2.mid[0].koff, q2.mid[1].it, q2.mid[1].koff, q2.it_base, q2.it_stop, (int)q2.err);
+                msg += b;
             }
-            seen[(size_t)ch] = {ctl.it, ctl.koff};
+            msg += "; the host wanted " + std::to_string((long long)n_iter) + " iterations, done_min " + std::to_string((long long)done_min) + "; " + host_state(s);
+            return set_error(s, OCC_E_HIP, msg.c_str());
         }
         if (std::getenv("OCC_VERBOSE")) {
             unsigned long long car = 0;
@@ -2903,16 +2873,10 @@ static int run_impl(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_
             std::fprintf(stderr, "[occ] batch of %lld sequences: done_min %lld / %lld, carries so far %llu, cap %d\n",
                          (long long)batch, (long long)done_min, (long long)n_iter, car, s->krylov_cap);
         }
-        // re-size the captured solve from the solves since the last decision: mean + 2.5 sd
-        const unsigned long long ds = solves - s->seen_solves;
-        if (!force && solve == SOLVE_CAPTURED && ds >= 32 && done_min < n_iter) {
-            const double mean = (double)(tot - s->seen_tot) / ds;
-            const double var = std::max(0.0, (double)(sq - s->seen_sq) / ds - mean * mean);
-            const int want = std::max(4, (int)std::ceil(mean + 2.5 * std::sqrt(var)));
-            s->seen_tot = tot; s->seen_sq = sq; s->seen_solves = solves;
-            // hysteresis: grow at once, shrink only when two launches too many are captured
-            if ((want > s->krylov_cap || want < s->krylov_cap - 1) && (rc = build_graph(s, want))) return rc;
-        }
+        // re-size the captured solve from the solves since the last decision (cap_resize; 0: too few of them yet)
+        const int want = !force && solve == SOLVE_CAPTURED && done_min < n_iter ? cap_resize(s->krylov_cap, tot - s->seen_tot, sq - s->seen_sq, solves - s->seen_solves) : 0;
+        if (want) s->seen_tot = tot, s->seen_sq = sq, s->seen_solves = solves;
+        if (want && want != s->krylov_cap && (rc = build_graph(s, want))) return rc;
     }
     if (!s->marks_done) {  // (every iteration was stepped eagerly: nothing was enqueued above)
         if ((rc = finish_marks(s, true, (size_t)C * keep * rw))) return rc;
@@ -2990,19 +2954,7 @@ static int fallback_to_launch_per_step(occ_sampler *s)
     HIP_TRY(copy_on(s, c.z, s->snap_z, Cn, hipMemcpyDeviceToDevice));
     HIP_TRY(copy_on(s, c.Xv, s->snap_x, sizeof(double2) * Cn, hipMemcpyDeviceToDevice));
     if (s->rsr.m > 0) HIP_TRY(copy_on(s, s->rsr.theta, s->snap_theta, sizeof(double) * (size_t)c.C * s->rsr.m, hipMemcpyDeviceToDevice));
-    for (int k = 0; k < N_SUMS; ++k) {
-        const size_t nsum = (size_t)SUMS[k].nacc * Cn;
-        if (!s->sums[k].snapped) continue;
-        HIP_TRY(copy_on(s, c.*SUMS[k].acc, s->sums[k].snap, sizeof(double) * nsum, hipMemcpyDeviceToDevice));
-        HIP_TRY(copy_on(s, c.*SUMS[k].count, s->sums[k].snap + nsum, sizeof(double) * (size_t)c.C, hipMemcpyDeviceToDevice));
-    }
-    for (int k = 0; k < N_ACCUM; ++k) {
-        const occ_sampler::AccumRun &r = s->accum(k);
-        const size_t nd = (size_t)ACCUM[k].elem * accum_words(ACCUM[k], (size_t)c.C, r.unit);
-        if (!r.snapped) continue;
-        HIP_TRY(copy_on(s, r.data, r.snap, nd, hipMemcpyDeviceToDevice));
-        HIP_TRY(copy_on(s, r.count, r.snap + nd, (size_t)ACCUM[k].elem * (size_t)c.C, hipMemcpyDeviceToDevice));
-    }
+    for (int i = 0; i < s->n_rerun; ++i) HIP_TRY(copy_on(s, s->rerun[i].live, s->rerun[i].snap, s->rerun[i].bytes, hipMemcpyDeviceToDevice));
     for (auto &sc : s->snap_sc) sc.err = 0;
     if ((rc = write_scalars(s, s->snap_sc))) return rc;
     s->parity = s->snap_parity;
@@ -3010,7 +2962,7 @@ static int fallback_to_launch_per_step(occ_sampler *s)
     s->calib_max = 0;
     s->fused_fallbacks += 1;
     s->demoted = true;                       // ... until try_repromote finds the device as creation found it
-    s->promote_wait = s->promote_backoff;
+    s->promote.arm();
     return OCC_OK;
 }
 
@@ -3023,13 +2975,12 @@ static int fallback_to_launch_per_step(occ_sampler *s)
 static int try_repromote(occ_sampler *s)
 {
     if (!s->demoted || std::getenv("OCC_NO_REPROMOTE")) return OCC_OK;
-    if (--s->promote_wait > 0) return OCC_OK;
+    if (!s->promote.due()) return OCC_OK;
     const Plan &P = s->plan;
     int rc;
     auto stay = [&](const char *why) {
         if (std::getenv("OCC_VERBOSE")) std::fprintf(stderr, "[occ] not back on the fused path: %s\n", why);
-        s->promote_backoff = std::min(64, s->promote_backoff * 2);
-        s->promote_wait = s->promote_backoff;
+        s->promote.fail();
         return OCC_OK;
     };
     WAIT_TRY(s->stream);
@@ -3057,7 +3008,7 @@ static int try_repromote(occ_sampler *s)
     if (!P.flag_sync) HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
     s->streams_serialised = false;
     s->demoted = false;
-    s->promote_backoff = 1;
+    s->promote.pass();
     s->repromotions += 1;
     if (std::getenv("OCC_VERBOSE")) std::fprintf(stderr, "[occ] back on the paths creation chose (fused kernel %d, device-side hand-overs %d)\n", (int)s->fused(), (int)s->run.flag_sync);
     return OCC_OK;
@@ -3069,18 +3020,37 @@ static int refresh_paths(occ_sampler *s)
 {
     int rc;
     if ((rc = try_repromote(s))) return rc;
-    // (a negative answer is not for life either: asked again after 1, 2, 4 ... 64 calls, as try_repromote does)
+    // (a negative answer is not for life either: asked again after 2, 4 ... 64 calls -- after 1 first when the answer was
+    // creation's; a probe the stream generation forces does not count a call)
     bool ask = s->probe_gen != g_stream_gen.load();
-    if (!ask && s->streams_serialised && !s->run.flag_sync && --s->probe_wait <= 0) ask = true;
+    if (!ask && s->streams_serialised && !s->run.flag_sync && s->probe.due()) ask = true;
     if (!s->demoted && s->run.main_cus > 0 && s->sync_buf && s->plan.flag_sync && ask) {
         bool beside = true;
         if ((rc = stream_probe(s, &beside))) return rc;
         s->streams_serialised = !beside;
-        if (beside) s->probe_backoff = 1;
-        else { s->probe_backoff = std::min(64, s->probe_backoff * 2); s->probe_wait = s->probe_backoff; }
+        if (beside) s->probe.pass();
+        else s->probe.fail();
         if ((rc = set_handover(s, beside))) return rc;
     }
     return OCC_OK;
+}
+
+// A call of occ_step / occ_run, impl(snapshot), on the paths refresh_paths leaves it.  Paths with device-side waits: re-run
+// without them, from the snapshot, if one gives up.  (The stamps are occ_run's.)
+extern "C++" template <class Impl>
+static int with_rerun(occ_sampler *s, Impl &&impl)
+{
+    int rc;
+    if ((rc = refresh_paths(s))) return rc;
+    const bool fused = (s->fused() && s->rsr.m == 0) || s->run.flag_sync;
+    s->device_timeout = false;
+    rc = impl(fused);
+    if (rc == OCC_E_HIP && fused && s->device_timeout) {
+        if ((rc = fallback_to_launch_per_step(s))) return rc;
+        rc = impl(false);
+    }
+    if (s->stamps_on) print_stamps(s);
+    return rc;
 }
 
 // Per-site intervals: a call that accumulates `add` iterations is admitted only if no count of a chain whose switch is on
@@ -3106,15 +3076,7 @@ int occ_step(occ_sampler *s)
     if (s->probit) return pb_step(s);
     int rc;
     if ((rc = hist_admit(s, 1))) return rc;
-    if ((rc = refresh_paths(s))) return rc;
-    const bool fused = (s->fused() && s->rsr.m == 0) || s->run.flag_sync;  // paths with device-side waits: re-run without them if one gives up
-    s->device_timeout = false;
-    rc = step_impl(s, fused);
-    if (rc == OCC_E_HIP && fused && s->device_timeout) {
-        if ((rc = fallback_to_launch_per_step(s))) return rc;
-        rc = step_impl(s, false);
-    }
-    return rc;
+    return with_rerun(s, [&](bool snapshot) { return step_impl(s, snapshot); });
 }
 
 int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, double *out_beta, double *out_tau)
@@ -3130,16 +3092,7 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
     stamp(s, "occ_run entered");
     int rc;
     if ((rc = hist_admit(s, n_iter - burnin))) return rc;
-    if ((rc = refresh_paths(s))) return rc;
-    const bool fused = (s->fused() && s->rsr.m == 0) || s->run.flag_sync;
-    s->device_timeout = false;
-    rc = run_impl(s, n_iter, burnin, out_alpha, out_beta, out_tau, fused);
-    if (rc == OCC_E_HIP && fused && s->device_timeout) {
-        if ((rc = fallback_to_launch_per_step(s))) return rc;
-        rc = run_impl(s, n_iter, burnin, out_alpha, out_beta, out_tau, false);
-    }
-    print_stamps(s);
-    return rc;
+    return with_rerun(s, [&](bool snapshot) { return run_impl(s, n_iter, burnin, out_alpha, out_beta, out_tau, snapshot); });
 }
 
 // The state names of the per-site sums, of any kind (SUMS): -> kind and 0.. the sum's place in the kind's array, SITE_COUNT,
@@ -3510,7 +3463,7 @@ static int accum_alloc(occ_sampler *s, int kind, size_t unit)
         HIP_TRY(hipFree(*old));
         *old = nullptr;
     }
-    r.snapped = false;
+    s->n_rerun = 0;  // (the list is a call's: the next one that can be re-run writes it anew)
     r.unit = unit;
     if ((rc = dev_alloc(s, &r.data, elem * accum_words(ACCUM[kind], C, unit)))) return rc;
     if (!r.on_dev) {
@@ -3897,8 +3850,14 @@ int occ_get_stats(occ_sampler *s, occ_stats *out)
     if (!s || !out) return OCC_E_BADARG;
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
-    if (s->probit) {  // no Krylov solve, no fused kernel, no CU partition: those fields stay 0
-        std::memset(out, 0, sizeof(*out));
+    if (s->probit) std::memset(out, 0, sizeof(*out));  // no Krylov solve, no fused kernel, no CU partition: those fields stay 0
+    int masked = 0, plain = 0, idle = 0;  // the process's stream pairs on the device: either model
+    count_pairs(s->device, &masked, &plain, &idle);
+    out->stream_pairs_masked = masked;
+    out->stream_pairs_plain = plain;
+    out->stream_pairs_idle = idle;
+    out->stream_pairs_evicted = (int32_t)g_pairs_evicted.load();
+    if (s->probit) {
         std::vector<PbChain> hp;
         int prc = pb_read_chains(s, hp);
         if (prc) return prc;
@@ -3911,12 +3870,6 @@ int occ_get_stats(occ_sampler *s, occ_stats *out)
         out->threads_per_block = PB_WG;
         out->n_chains = s->pb.C;
         out->handover_mode = 1;
-        int masked = 0, plain = 0, idle = 0;
-        count_pairs(s->device, &masked, &plain, &idle);
-        out->stream_pairs_masked = masked;
-        out->stream_pairs_plain = plain;
-        out->stream_pairs_idle = idle;
-        out->stream_pairs_evicted = (int32_t)g_pairs_evicted.load();
         return OCC_OK;
     }
     std::vector<ChainScalars> h;
@@ -3946,14 +3899,6 @@ int occ_get_stats(occ_sampler *s, occ_stats *out)
     out->repromotions = (int32_t)s->repromotions;
     out->stream_probes = (int32_t)s->stream_probes;
     out->handover_mode = s->run.flag_sync ? 2 : 1;
-    {
-        int masked = 0, plain = 0, idle = 0;
-        count_pairs(s->device, &masked, &plain, &idle);
-        out->stream_pairs_masked = masked;
-        out->stream_pairs_plain = plain;
-        out->stream_pairs_idle = idle;
-        out->stream_pairs_evicted = (int32_t)g_pairs_evicted.load();
-    }
     out->demoted = s->demoted ? 1 : 0;
     out->profile_iter_dispatch_us = s->profile_iter_dispatch_us;
     out->profile_minres_iterations = s->profile_minres_iterations;

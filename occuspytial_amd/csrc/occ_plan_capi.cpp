@@ -1,12 +1,13 @@
 // occ_plan_capi.cpp -- the planner, the launch order and the z update's outputs (occ_plan.hpp), the accumulators behind the z
-// update (occ_accum.hpp), the draws of a call (occ_draws.hpp) and the problem layout (occ_layout.hpp) behind C entry points for
-// tests/test_plan_cpu.py, tests/test_order_cpu.py, tests/test_outputs_cpu.py, tests/test_accum_cpu.py, tests/test_draws_cpu.py
-// and tests/test_layout_cpu.py (ctypes).  Test infrastructure: `make plan` builds it with g++ into build/; it is never linked
+// update (occ_accum.hpp), the draws of a call (occ_draws.hpp), a call's host decisions (occ_call.hpp) and the problem layout
+// (occ_layout.hpp) behind C entry points for tests/test_plan_cpu.py, tests/test_order_cpu.py, tests/test_outputs_cpu.py,
+// tests/test_accum_cpu.py, tests/test_draws_cpu.py, tests/test_call_cpu.py and tests/test_layout_cpu.py (ctypes).  Test infrastructure: `make plan` builds it with g++ into build/; it is never linked
 // into libocc_gibbs.so.
 #include <cstdio>
 #include <cstring>
 
 #include "occ_accum.hpp"
+#include "occ_call.hpp"
 #include "occ_draws.hpp"
 #include "occ_layout.hpp"
 
@@ -136,6 +137,39 @@ void occ_draws_row(int32_t k, const char *name[3], const char *refusal[5], int32
 int32_t occ_draws_lookup(const char *name, int32_t *field) { return draws_lookup(name, field); }
 double occ_draws_value(int32_t k, uint64_t raw, int64_t col) { return draws_value(DRAWS[k], &raw, (size_t)col); }
 int64_t occ_draws_length(int32_t field, int64_t n, int64_t keep, int64_t width) { return (int64_t)draws_length(field, (size_t)n, (size_t)keep, (size_t)width); }
+
+// What a call decides on the host (occ_call.hpp), as it is.  occ_call_head: the steps as {kind, n, from_calib, long_pair} rows,
+// -> how many.  occ_call_progress: at = [C]{it, koff, it_base}, seen = [C]{it, koff} (updated) -> the stuck chain or -1.
+// occ_call_backoff: one operation (0 arm, 1 fail, 2 pass, 3 due) on state = {wait, step} -> due()'s answer, else 0.
+int32_t occ_call_head(int32_t eager_only, int32_t solve, int64_t seq_per_enqueue, int32_t have_graph, int32_t aligned, int64_t n_iter, int32_t need_prologue, int64_t out[3][4])
+{
+    const CallHead h = call_head(eager_only != 0, (SeqSolve)solve, seq_per_enqueue, have_graph != 0, aligned != 0, n_iter, need_prologue != 0);
+    for (int i = 0; i < h.n; ++i) { out[i][0] = h.step[i].kind; out[i][1] = h.step[i].n; out[i][2] = h.step[i].from_calib; out[i][3] = h.step[i].long_pair; }
+    return h.n;
+}
+int64_t occ_call_batch(int64_t left, int64_t graph_launches, int64_t seq_per_enqueue) { return call_batch(left, graph_launches, seq_per_enqueue); }
+int32_t occ_call_cap_from_calibration(int32_t calib_max, const char *force) { return cap_from_calibration(calib_max, force); }
+int32_t occ_call_cap_resize(int32_t cap, uint64_t d_tot, uint64_t d_sq, uint64_t d_solves) { return cap_resize(cap, d_tot, d_sq, d_solves); }
+int32_t occ_call_progress(int32_t C, const uint32_t *at, uint32_t *seen, int64_t n_iter, int64_t *done_min)
+{
+    std::vector<SeenAt> sn((size_t)C);
+    for (int ch = 0; ch < C; ++ch) sn[(size_t)ch] = {seen[2 * ch], seen[2 * ch + 1]};
+    const CallProgress r = call_progress(C, [&](int ch) { return ChainAt{at[3 * ch], at[3 * ch + 1], at[3 * ch + 2]}; }, sn.data(), n_iter);
+    for (int ch = 0; ch < C; ++ch) { seen[2 * ch] = sn[(size_t)ch].first; seen[2 * ch + 1] = sn[(size_t)ch].second; }
+    *done_min = r.done_min;
+    return r.stuck;
+}
+int32_t occ_call_backoff(int32_t state[2], int32_t op)
+{
+    Backoff b;
+    b.wait = state[0]; b.step = state[1];
+    const bool due = op == 3 && b.due();
+    if (op == 0) b.arm();
+    if (op == 1) b.fail();
+    if (op == 2) b.pass();
+    state[0] = b.wait; state[1] = b.step;
+    return due;
+}
 
 // The layout of a logit problem, by build_layout's steps in its order (occ_gibbs.hip), plus the probit model's row_t.
 // A handle for occ_layout_array / occ_layout_peer, or null with the refusal in err.
