@@ -157,6 +157,8 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  * SAME iterations as the sums above, at the SURVEYED sites only (an unsurveyed site's sums stay exactly 0).  The likelihood
  * is the site's marginal one, z integrated out.  With lsig(a) = min(a, 0) - log1p(exp(-|a|)) and r the site's visit rows:
  *   no detection at the site:  L = D = (1 - psi) + psi prod_r expit(-w_r alpha), the very D the z update divides by; l = log D
+ *                              (1 - psi is not subtracted where psi > 1/2: for x_i beta + eta_i = a >= 0 it is exp(-a) psi, so D
+ *                              keeps its digits where psi rounds to 1)
  *   a detection at the site:   l = lsig(x_i beta + eta_i) + sum_r lsig(+- w_r alpha), + where y_r = 1, rows in row order; L = exp(l)
  * Three float64 sums per site and one count per chain:
  *   ll_lik(n)    sum of L      -> log(ll_lik / count): the site's log pointwise predictive density
@@ -313,7 +315,8 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  * iteration past the call's burn-in -- the rule of the per-site intervals above, so occ_step counts as well -- of a chain
  * whose switch is on, one kernel launched directly behind the z update does, per entry, with a = x_i beta + eta_i (reduced
  * rank: eta = K theta), psi = expit(a), lsig(t) = min(t, 0) - log1p(exp(-|t|)) and P = prod_r expit(-w_r alpha):
- *   no detection in the withheld history:   D = (1 - psi) + psi P,   L = D,   l = log D
+ *   no detection in the withheld history:   D = (1 - psi) + psi P,   L = D,   l = log D   (1 - psi as the z update forms it:
+ *                                           exp(-a) psi for a >= 0, no subtraction where psi > 1/2)
  *   a detection:                            l = lsig(a) + sum_r lsig(+- w_r alpha)  (+ where y_r = 1, rows in row order),   L = exp(l)
  *   pd = psi (1 - P)                        the predictive probability of at least one detection in these visits
  *   cnt += 1;   sum L += L;   sum l += l;   sum l^2 += l l;   sum pd += pd

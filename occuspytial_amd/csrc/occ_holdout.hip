@@ -18,10 +18,9 @@ __device__ __forceinline__ bool holdout_counts_now(const HoldoutArgs &a, const C
     return a.on[chain] != 0u && a.sums != nullptr && after == t + 1u && sc.err == 0 && rel >= sc.burnin;
 }
 
-// log expit(t) = min(t, 0) - log1p(exp(-|t|)) and expit(t) itself, both from e = exp(-|t|): the second performs the
-// operations of expit() (exp(t) for t < 0, exp(-t) otherwise).  As the streaming WAIC's z update has them.
+// log expit(t) = min(t, 0) - log1p(exp(-|t|)) from e = exp(-|t|); expit(t) and 1 - expit(t) come from the same e by
+// expit_e and expit_c (occ_state.hpp).  As the streaming WAIC's z update has them.
 __device__ __forceinline__ double hold_lsig(double t, double e) { return fmin(t, 0.0) - log1p(e); }
-__device__ __forceinline__ double hold_expit(double t, double e) { return t < 0.0 ? e / (1.0 + e) : 1.0 / (1.0 + e); }
 
 __global__ void __launch_bounds__(256) k_holdout_sites(const HoldoutArgs a, const ChainScalars *__restrict__ scs, int e)
 {
@@ -34,13 +33,13 @@ __global__ void __launch_bounds__(256) k_holdout_sites(const HoldoutArgs a, cons
     const int i = a.site[h], r0 = a.ptr[h], r1 = a.ptr[h + 1];
     const bool seen = a.seen[h] != 0;
     const double a0 = xdot(a.Xt, n, i, sc.beta, a.p) + a.eta[(size_t)chain * n + i], e0 = exp(-fabs(a0));
-    const double psi = hold_expit(a0, e0);
+    const double psi = expit_e(a0, e0);
     double prod = 1.0, ll = seen ? hold_lsig(a0, e0) : 0.0;
     for (int r = r0; r < r1; ++r) {  // ONE loop for both kinds of entry: the same load, dot product and exponential
         double t = 0.0;
         for (int k = 0; k < a.q; ++k) t = fma(a.Wt[(size_t)k * a.R + r], -sc.alpha[k], t);
         const double et = exp(-fabs(t));
-        const double ex = hold_expit(t, et);
+        const double ex = expit_e(t, et);
         prod = (r == r0) ? ex : prod * ex;
         if (seen) ll += hold_lsig(a.y[r] ? -t : t, et);  // rows in row order
     }
@@ -48,7 +47,7 @@ __global__ void __launch_bounds__(256) k_holdout_sites(const HoldoutArgs a, cons
     if (seen) {
         lik = exp(ll);
     } else {
-        lik = (1.0 - psi) + psi * prod;
+        lik = z_den(a0, e0, psi, psi * prod);
         ll = log(lik);
     }
     const double pd = psi * (1.0 - prod);

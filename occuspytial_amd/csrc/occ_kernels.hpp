@@ -2023,10 +2023,9 @@ __device__ __forceinline__ void ll_add(const Ctx &c, int chain, int i, double li
     a[LL_LOG * Cn] += ll;
     a[LL_LOG2 * Cn] = fma(ll, ll, a[LL_LOG2 * Cn]);
 }
-// log expit(a) = min(a, 0) - log1p(exp(-|a|)), stable on both sides, and expit(a) itself, both from e = exp(-|a|): the
-// second performs the operations of expit() above (exp(a) for a < 0, exp(-a) otherwise), so it has its bits.
+// log expit(a) = min(a, 0) - log1p(exp(-|a|)), stable on both sides, from the e = exp(-|a|) that expit_e and expit_c
+// (occ_state.hpp) take expit(a), with the bits of expit(), and 1 - expit(a), without cancellation, from.
 __device__ __forceinline__ double lsig_e(double a, double e) { return fmin(a, 0.0) - log1p(e); }
-__device__ __forceinline__ double expit_e(double a, double e) { return a < 0.0 ? e / (1.0 + e) : 1.0 / (1.0 + e); }
 
 // The z update of one site of a chain that keeps the log-likelihood sums (k_z_ob_ll, `ll_on`): z_update_site with ONE loop
 // over the site's visit rows for both kinds of surveyed site.  A site with a detection needs lsig(+- w_r alpha) of every
@@ -2063,7 +2062,7 @@ __device__ __forceinline__ int z_update_site_ll(const Ctx &c, uint64_t key, int 
             return 1;
         }
         const double num = num1 * prod;
-        const double den = (1.0 - num1) + num;  // the site's likelihood: what the update divides by
+        const double den = z_den(a0, e0, num1, num);  // the site's likelihood: what the update divides by
         pr = num / den;
         ll_add(c, chain, i, den, log(den));
     }
@@ -2119,7 +2118,8 @@ __device__ __forceinline__ int z_update_site(const Ctx &c, uint64_t key, int cha
     double xb = 0.0;
 #pragma unroll
     for (int a = 0; a < P; ++a) xb = fma(c.Xt[(size_t)a * n + i], beta[a], xb);
-    const double num1 = expit(xb + eta_i);
+    const double a0 = xb + eta_i, e0 = exp(-fabs(a0));
+    const double num1 = expit_e(a0, e0);
     double pr = num1;
     if (!not_surveyed) {
         double prod = 1.0;
@@ -2133,7 +2133,7 @@ __device__ __forceinline__ int z_update_site(const Ctx &c, uint64_t key, int cha
             prod = (r == r0) ? ex : prod * ex;
         }
         const double num = num1 * prod;
-        pr = num / ((1.0 - num1) + num);
+        pr = num / (z_den(a0, e0, num1, num));
     }
     const double u = INJ ? c.inj->z_u[i] : block_uniform(key, (uint32_t)i, 0, it, STREAM_Z);
     c.z[(size_t)chain * n + i] = (u < pr) ? 1 : 0;
@@ -2271,7 +2271,7 @@ __device__ __forceinline__ int z_update_site_ppc(const Ctx &c, uint64_t key, int
             if (ll_on) ll_add(c, chain, i, exp(ll), ll);
         } else {
             const double num = num1 * prod;
-            const double den = (1.0 - num1) + num;  // the site's likelihood: what the update divides by
+            const double den = z_den(a0, e0, num1, num);  // the site's likelihood: what the update divides by
             pr = num / den;
             if (ll_on) ll_add(c, chain, i, den, log(den));
         }
@@ -2541,7 +2541,8 @@ __device__ __forceinline__ int z_update_site_g(const Ctx &c, const ChainScalars 
     const int n = c.n, P = c.p, Q = c.q;
     double xb = 0.0;
     for (int a = 0; a < P; ++a) xb = fma(c.Xt[(size_t)a * n + i], sc.beta[a], xb);
-    const double num1 = expit(xb + eta_i);
+    const double a0 = xb + eta_i, e0 = exp(-fabs(a0));
+    const double num1 = expit_e(a0, e0);
     double pr = num1;
     if (!not_surveyed) {
         double prod = 1.0;
@@ -2553,7 +2554,7 @@ __device__ __forceinline__ int z_update_site_g(const Ctx &c, const ChainScalars 
             prod = (r == r0) ? ex : prod * ex;
         }
         const double num = num1 * prod;
-        pr = num / ((1.0 - num1) + num);
+        pr = num / (z_den(a0, e0, num1, num));
     }
     const double u = INJ ? c.inj->z_u[i] : block_uniform(sc.key, (uint32_t)i, 0, it, STREAM_Z);
     c.z[(size_t)chain * n + i] = (u < pr) ? 1 : 0;

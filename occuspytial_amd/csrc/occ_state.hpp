@@ -54,6 +54,15 @@ __device__ __forceinline__ double expit(double x)
     if (x < 0.0) { const double e = exp(x); return e / (1.0 + e); }
     return 1.0 / (1.0 + exp(-x));
 }
+// expit(a) and 1 - expit(a), both from e = exp(-|a|).  The first performs the operations of expit() (exp(a) for a < 0,
+// exp(-a) otherwise), so it has its bits.  The second is formed without cancellation: for a < 0, psi <= 1/2 and 1 - psi is
+// exact to an ulp; for a >= 0 it is e psi = e / (1 + e), where 1 - psi would lose digits in proportion to 1 / (1 - psi)
+// and be 0 from a = 36.74 on.  z_den: the likelihood D = (1 - psi) + num, num = psi P, of a site without a detection, which
+// every z update divides by and the held-out score takes the logarithm of.  D <= 1; with P = 1 the rounded e psi + psi can
+// be 1 + 2^-52 (1 - psi, subtracted, gave exactly 1), so it is held to 1: log D <= 0 as before.
+__device__ __forceinline__ double expit_e(double a, double e) { return a < 0.0 ? e / (1.0 + e) : 1.0 / (1.0 + e); }
+__device__ __forceinline__ double expit_c(double a, double e, double psi) { return a < 0.0 ? 1.0 - psi : e * psi; }
+__device__ __forceinline__ double z_den(double a, double e, double psi, double num) { return fmin(expit_c(a, e, psi) + num, 1.0); }
 
 // x_i . coef over the structure-of-arrays design (explicit contractions: every caller evaluates the same operations)
 __device__ __forceinline__ double xdot(const double *Xt, int n, int i, const double *coef, int p)

@@ -389,13 +389,18 @@ void orc_alpha_system(long S, int q, const int64_t *site_ptr, const uint8_t *exi
     for (int a = 0; a < q; ++a) r[a] += a_prec_by_mu[a];
 }
 
-/* gibbs/logit.py:241-245 for one site */
+/* gibbs/logit.py:241-245 for one site, but for the 1 - psi of line 245: the subtraction loses digits in proportion to
+ * 1 / (1 - psi) and is 0 from a0 = 36.74 on, where the probability would be 1 whatever the visits say.  It is formed as
+ * the device forms it (expit_c and z_den, occ_state.hpp): 1 - psi for a0 < 0, exp(-a0) psi otherwise, and the denominator
+ * held to 1.  psi keeps the bits of orc_expit.  DESIGN.md section 2. */
 double orc_z_prob(int p, int q, const double *xrow, const double *beta, double eta_i, long nrows,
                   const double *Wrows, const double *alpha)
 {
     double lin = 0.0;
     for (int a = 0; a < p; ++a) lin += xrow[a] * beta[a];
-    double num1 = orc_expit(lin + eta_i);
+    const double a0 = lin + eta_i;
+    double num1 = orc_expit(a0);
+    const double den1 = a0 < 0.0 ? 1.0 - num1 : exp(-a0) * num1;
     double prod = 1.0;
     for (long v = 0; v < nrows; ++v) {
         double wa = 0.0;
@@ -404,7 +409,7 @@ double orc_z_prob(int p, int q, const double *xrow, const double *beta, double e
         prod = (v == 0) ? e : prod * e;
     }
     double num = num1 * prod;
-    return num / ((1.0 - num1) + num);
+    return num / fmin(den1 + num, 1.0);  /* z_den: the rounded exp(-a0) psi + psi can be 1 + 2^-52 */
 }
 
 /* Edge form of the prior term.  The reference draws E @ (sqrt(tau) eps) with E the dense

@@ -16,6 +16,7 @@ import pytest
 from scipy import sparse
 from scipy.special import expit
 
+from . import _z_theory as zt
 from ._outputs_gpu import engine_with, time_limit as _time_limit, two_calls  # noqa: F401 (autouse in this module)
 from .conftest import load_golden
 from .test_gpu_parity import KEY, _random_start
@@ -148,6 +149,7 @@ def holdout_terms(X, data, alpha, beta, eta):
     wa = W @ alpha
     wa_abs = np.abs(W * alpha).sum(axis=1)
     ll, lik, pd, b, bp = (np.zeros(H) for _ in range(5))
+    ref = zt.problem_terms(X, eta, beta, W, alpha, ptr, site)           # as if no entry had a detection
     for h in range(H):
         rows = slice(ptr[h], ptr[h + 1])
         psi = expit(a0[h])
@@ -163,9 +165,8 @@ def holdout_terms(X, data, alpha, beta, eta):
             ll[h], lik[h] = acc, np.exp(acc)
             b[h] = (a0_abs[h] + abs(t0) + 1.0) + np.sum(wa_abs[rows] + np.abs(terms) + 1.0)
         else:
-            D = (1.0 - psi) + psi * P
-            ll[h], lik[h] = np.log(D), D
-            b[h] = (a0_abs[h] + 1.0) / (1.0 - psi) + np.sum(wa_abs[rows] + 1.0) + abs(ll[h])
+            ll[h], lik[h] = ref['l'][h], ref['D'][h]                   # log space: nothing is subtracted (tests/_z_theory.py)
+            b[h] = ref['b'][h] + abs(ll[h])                            # (sum |products_0| + 1) + sum_r (sum |products_r| + 1) + |l|
     return ll, lik, pd, b, bp
 
 
@@ -207,16 +208,16 @@ def test_sums_equal_their_restatement_in_numpy(name, chains):
       for q <= 9).  lsig has slope <= 1, so the term inherits that; its own evaluation adds at most 4 u (|term| + 1).  Adding the
       <= 41 terms and then 13 iterations rounds at most (41 + 13) u sum |terms| = 6e-15 sum |terms|.  Held to
       B_l = 1e-12 sum_t sum_terms (sum |products| + |term| + 1), a margin of more than a hundred.
-    No detection.  l = log D, D = (1 - psi) + psi prod_r expit(-w_r alpha): D has the relative error
-      (2 |d psi| + 2 u) / (1 - psi) + sum_r (|d a_r| + 4 u), which is the absolute error of its logarithm, plus the logarithm's own
-      few ulp of |l|; held to B_l = 1e-12 sum_t ((sum |products_0| + 1) / (1 - psi) + sum_r (sum |products_r| + 1) + |l|) -- the
-      1 / (1 - psi) factor of tests/test_gpu_waic.py.
+    No detection.  l = log D, D = (1 - psi) + psi prod_r expit(-w_r alpha), on the host in log space (tests/_z_theory.py): both
+      terms of D are positive and each has the relative error of its logarithm, |d a_0| and |d a_0| + sum_r (|d a_r| + 4 u); the
+      device takes 1 - psi without cancellation, so no 1 / (1 - psi) enters.  Held to
+      B_l = 1e-12 sum_t ((sum |products_0| + 1) + sum_r (sum |products_r| + 1) + |l|), as tests/test_gpu_waic.py.
     sum L: L <= 1 and d L = L d l or D d l: the same absolute bound B_l.
     sum l^2: 2 max_t |l_t| B_l + 1e-12 sum l^2 (the fused multiply-adds round 13 times at u sum l^2).
     sum pd: pd = psi (1 - P), P = prod_r expit(-w_r alpha) <= 1.  |d psi| <= |d a_0| / 4 + 4 u, |d P| <= P sum_r (|d a_r| + 4 u),
       the product and the difference round at 2 u: |d pd| <= (p + 1) u sum |products_0| + 10 u + sum_r (2 (q + 1) u
       sum |products_r| + 4 u); held to B_pd = 1e-12 sum_t ((sum |products_0| + 1) + sum_r (sum |products_r| + 1)).
-    ``CAP``: B_l, which grows as 1 / (1 - psi), must stay below 1e-6 at every entry, so that it cannot grow until it hides a
+    ``CAP``: B_l must stay below 1e-6, as when it grew as 1 / (1 - psi), at every entry, so that it cannot grow until it hides a
     failure: an error in a sign, a row or a term moves l by more than 1e-3.
     The same thirteen iterations as one run(13, 0) give equal bits."""
     from occuspytial_amd.holdout import holdout_arg, unpack

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 from scipy.special import expit
 
+from . import _z_theory as zt
 from ._outputs_gpu import engine_with, two_calls
 from .test_gpu_parity import KEY, _problem_from_golden, _random_start
 
@@ -74,18 +75,13 @@ def _engine(prob, keys, starts, on=True):
 
 # ------------------------------------------------------------------ 1 / 7: against an independent restatement
 def _terms(prob, alpha, beta, eta):
-    """psi and P(z = 1 | alpha, beta, eta, y) of every site from the reference's formulas (logit.py:234-252), in numpy;
-    the probability written as the device writes it, num / ((1 - psi) + num)."""
+    """psi and P(z = 1 | alpha, beta, eta, y) of every site from the reference's formulas (logit.py:234-252), in numpy; the
+    probability of a surveyed site without a detection from the log-space reference of tests/_z_theory.py, which subtracts
+    nothing."""
     psi = expit(prob.X @ beta + eta)
     pr = psi.copy()                                   # unsurveyed sites
-    det = expit(-(prob.W @ alpha))                    # P(no detection at a visit | occupied)
-    for s in range(prob.S):
-        i = prob.site_id[s]
-        if prob.obs_site[s]:
-            pr[i] = 1.0
-            continue
-        num = psi[i] * np.prod(det[prob.site_ptr[s]:prob.site_ptr[s + 1]])
-        pr[i] = num / ((1.0 - psi[i]) + num)
+    ref = zt.problem_terms(prob.X, eta, beta, prob.W, alpha, prob.site_ptr, prob.site_id)
+    pr[prob.site_id] = np.where(np.asarray(prob.obs_site) != 0, 1.0, ref['pr'])
     return psi, pr
 
 
@@ -96,12 +92,13 @@ def _restatement(prob, keys, starts, cap, steps=12):
       site_eta, site_eta2: 1e-12 relative to sum |term| (12 additions of 2^-53 each, hundred-fold margin);
       site_psi / N: 1e-12 absolute (host and device form x beta + eta in different orders, |d| <= (p + 1) 2^-53 sum |terms|
         <= 1.5e-13 for p <= 12 even if the terms sum to 100; psi' <= 1/4; two expit implementations differ by a few ulp of 1);
-      site_occ / N at site i: 1e-12 + 2^-50 mean_t 1 / (1 - psi_ti) with the host's psi (d pr / d D = -pr (1 - pr) / D for
-        D = 1 - psi, |pr (1 - pr)| <= 1/4, D inherits psi's absolute error of up to four ulp: |d pr| <= 2^-53 / D; 2^-50 is
-        eight times that) -- and that bound is itself capped (``cap``) so that it cannot grow until it hides a failure."""
+      site_occ / N at site i: 1e-12 absolute, against the log-space reference of tests/_z_theory.py (pr has the slope
+        pr (1 - pr) <= 1/4 in its logit a_0 + sum_r lsig(t_r), which host and device form within 2 (p + 1) u sum |products| of
+        each other; the device takes 1 - psi without cancellation, so no 1 / (1 - psi) enters) -- and the bound stays capped
+        (``cap``) as it was when it grew with 1 / (1 - psi)."""
     eng = _engine(prob, keys, starts)
     C, n = len(keys), prob.n
-    acc = [{k: np.zeros(n) for k in ('psi', 'occ', 'z', 'eta', 'eta2', 'abs_eta', 'inv_d')} for _ in range(C)]
+    acc = [{k: np.zeros(n) for k in ('psi', 'occ', 'z', 'eta', 'eta2', 'abs_eta')} for _ in range(C)]
     for _ in range(steps):
         eng.step()
         for c in range(C):
@@ -114,12 +111,11 @@ def _restatement(prob, keys, starts, cap, steps=12):
             a['eta'] += eta
             a['eta2'] += eta * eta
             a['abs_eta'] += np.abs(eta)
-            a['inv_d'] += 1.0 / (1.0 - psi)
     N = float(steps)
     for c in range(C):
         count, dev = _read(eng, c)
         a = acc[c]
-        bound = 1e-12 + 2.0 ** -50 * a['inv_d'] / N
+        bound = np.full(n, 1e-12)
         fig = dict(chain=c, eta=np.max(np.abs(dev['site_eta'] - a['eta']) / a['abs_eta']),
                    eta2=np.max(np.abs(dev['site_eta2'] - a['eta2']) / a['eta2']),
                    psi=np.max(np.abs(dev['site_psi'] - a['psi'])) / N,

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 from scipy.special import expit
 
+from . import _z_theory as zt
 from ._outputs_gpu import engine_with, two_calls
 from .test_gpu_parity import KEY, _problem_from_golden, _random_start
 from .test_gpu_site_summaries import SUMS as SITE_SUMS
@@ -68,6 +69,7 @@ def _ll_terms(prob, alpha, beta, eta):
     wa_abs = np.abs(prob.W * alpha).sum(axis=1)
     y = np.asarray(prob.y).ravel() != 0
     ll, lik, b = np.zeros(n), np.zeros(n), np.zeros(n)
+    ref = zt.problem_terms(prob.X, eta, beta, prob.W, alpha, prob.site_ptr, prob.site_id)   # as if no site had a detection
     for s in range(prob.S):
         i = prob.site_id[s]
         rows = slice(prob.site_ptr[s], prob.site_ptr[s + 1])
@@ -80,10 +82,8 @@ def _ll_terms(prob, alpha, beta, eta):
             ll[i], lik[i] = acc, np.exp(acc)
             b[i] = (a0_abs[i] + abs(t0) + 1.0) + np.sum(wa_abs[rows] + np.abs(terms) + 1.0)
         else:
-            psi = expit(a0[i])
-            D = (1.0 - psi) + psi * np.prod(expit(-wa[rows]))
-            ll[i], lik[i] = np.log(D), D
-            b[i] = (a0_abs[i] + 1.0) / (1.0 - psi) + np.sum(wa_abs[rows] + 1.0) + abs(ll[i])
+            ll[i], lik[i] = ref['l'][s], ref['D'][s]                   # log space: nothing is subtracted (tests/_z_theory.py)
+            b[i] = ref['b'][s] + abs(ll[i])                            # (sum |products_0| + 1) + sum_r (sum |products_r| + 1) + |l|
     return ll, lik, b
 
 
@@ -117,17 +117,16 @@ def _restatement(prob, keys, starts, cap, steps=12):
       <= log 2, one subtraction rounded at u |term| -- adds at most 4 u (|term| + 1).  Adding the <= 7 terms and then 12
       iterations rounds at most (7 + 12) u sum |terms|.  Together: below 2.2e-15 sum |products| + 2.6e-15 (|term| + 1) per
       term, held to   B_l = 1e-12 sum_t sum_terms (sum |products| + |term| + 1),   a margin of four hundred.
-    No detection.  l = log D, D = (1 - psi) + psi prod_r expit(-w_r alpha).  psi = expit(a_0) has the absolute error
-      |d a_0| / 4 + 4 u; each factor of the product the relative error |d a_r| + 4 u (slope of log expit <= 1); and
-      psi prod / D <= 1, D >= 1 - psi.  So D has the relative error (2 |d psi| + 2 u) / (1 - psi) + sum_r (|d a_r| + 4 u), which
-      is the absolute error of its logarithm, plus the logarithm's own few ulp of |l|:
-        |d l| <= ((p + 1) u sum |products_0| + 10 u) / (1 - psi) + sum_r (2 (q + 1) u sum |products_r| + 4 u) + 4 u |l|,
-      held to   B_l = 1e-12 sum_t ((sum |products_0| + 1) / (1 - psi) + sum_r (sum |products_r| + 1) + |l|)   -- the
-      1 / (1 - psi) factor of the site_occ check of test_gpu_site_summaries.py, for the same reason.
+    No detection.  l = log D, D = (1 - psi) + psi prod_r expit(-w_r alpha), on the host in log space (tests/_z_theory.py:
+      l = logaddexp(lsig(-a_0), lsig(a_0) + sum_r lsig(-w_r alpha)), nothing subtracted).  Both terms of D are positive and
+      each has the relative error of its logarithm: |d a_0| for 1 - psi and for psi (slope of lsig <= 1), |d a_r| + 4 u per
+      factor -- the device takes 1 - psi from exp(-|a_0|) without cancellation, so no 1 / (1 - psi) enters:
+        |d l| <= 2 (p + 1) u sum |products_0| + 10 u + sum_r (2 (q + 1) u sum |products_r| + 4 u) + 4 u |l|,
+      held to   B_l = 1e-12 sum_t ((sum |products_0| + 1) + sum_r (sum |products_r| + 1) + |l|).
     ll_lik: L <= 1 and d L = L d l (a detection: L = exp(l), plus one ulp of L) or D d l (none): the same absolute bound B_l.
     ll_log2: d(l^2) = 2 |l| d l, summed: 2 max_t |l_t| B_l; the fused multiply-adds round 12 times at u sum l^2, held to
       1e-12 sum l^2.
-    ``cap``: B_l, which grows as 1 / (1 - psi), must stay below it at every site, so that it cannot grow until it hides a
+    ``cap``: B_l must stay below it at every site, as when it grew as 1 / (1 - psi), so that it cannot grow until it hides a
     failure (an error in a sign, a row or a term moves l by far more than 1e-6).  The CPU restatement of the ABI, stepped
     through ``_host_sums`` on these four workloads, keeps B_l below 5.1e-9 (A), 3.0e-9 (wide rows), 5.8e-9 (generic) and
     5.3e-10 (reduced rank) -- the largest values belong to sites whose psi comes within 1e-3 of 1: the caps are 1e-8 (A, wide
