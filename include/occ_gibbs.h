@@ -133,7 +133,13 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
  *   the factor U (Lam = U'U) right of each 32-row panel's diagonal block (the rest is working storage)
  * occ_get_state copies into out (capacity cap doubles) and stores the length in *len.
  * occ_set_state accepts alpha beta tau eta z omega_a xz iter theta (theta also sets eta = K theta); omega_b of
- * the coming iteration is then redrawn from the new state.
+ * the coming iteration is then redrawn from the new state.  A probit handle's names: occ_problem::link.
+ * A read of a name the model does not have: OCC_E_STATE, "unknown state name".  A write of a name that is unknown, read-only
+ * or not the model's, and of alpha, beta, tau or iter with another length: "unknown state name or wrong length"; of any other
+ * name with another length: "wrong length".  With out = NULL occ_get_state stores the length alone; for these names it is a
+ * function of the problem's sizes and nothing is copied off the device.
+ * The engine reads all of this -- length, who reads, who writes, where the value lives, whether a write redraws -- off one
+ * table, STATE of occuspytial_amd/csrc/occ_names.hpp, which also routes every other family of names below to its own code.
  *
  * Per-site posterior summaries (logit models; ICAR and reduced rank), accumulated on the device by the z update of every
  * KEPT iteration of a chain whose switch is on: an iteration `it` of a call counts when it - (first iteration of the

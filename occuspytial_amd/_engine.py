@@ -227,7 +227,10 @@ class Engine:
         self.keys = [int(v) & (2 ** 64 - 1) for v in keys]
 
     # ---- checkpoint / resume (the reference has none) -------------------------------------
-    CHECKPOINT_FIELDS = ('alpha', 'beta', 'tau', 'eta', 'z', 'xz')
+    @property
+    def model(self):
+        """This engine's bit of the masks of ``_lib.STATE_NAMES``."""
+        return _lib.PROBIT if self.probit is not None else _lib.RSR if self.rsr is not None else _lib.ICAR
 
     def checkpoint(self):
         """Everything a chain needs to continue exactly where it is: the state the next iteration reads
@@ -237,10 +240,8 @@ class Engine:
         out = {'n_chains': np.int64(self.n_chains), 'keys': np.array(self.keys, dtype=np.uint64),
                'iter': np.array([int(self.get('iter', c)) for c in range(self.n_chains)], dtype=np.int64),
                'shape': np.array([self.prob.n, self.prob.p, self.prob.q, self.prob.R], dtype=np.int64)}
-        fields = self.CHECKPOINT_FIELDS if self.rsr is None else ('alpha', 'beta', 'tau', 'theta', 'z')
-        if self.probit is not None:   # the engine's own coordinates c and the eta it computed from them: bit-exact continuation
-            fields = ('alpha', 'beta', 'tau', 'theta', 'z', 'c', 'eta', 'eps')
-        for name in fields:
+        # (the probit model: also the engine's own coordinates c and the eta it computed from them, bit-exact continuation)
+        for name in (nm for nm, st in _lib.STATE_NAMES.items() if st.ckpt & self.model):
             out[name] = np.stack([np.atleast_1d(self.get(name, c)) for c in range(self.n_chains)])
         for kind, on in self._sums_on.items():
             if on:   # switch, count and the kind's per-site sums: a resumed run ends with the sums of the uninterrupted one

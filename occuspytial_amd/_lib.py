@@ -34,8 +34,43 @@ HOLDOUT_FIELDS = ('holdout_data', 'holdout_stats', 'holdout_count', 'holdout_sum
 KERNEL_KINDS = ('omega_b', 'noise', 'eta_init', 'minres', 'beta_partial', 'omega_a', 'alpha_draw', 'z_ob', 'iter')
 
 
+class StateName(NamedTuple):
+    """One plain state name of a chain (``STATE`` of csrc/occ_names.hpp), as Python sees it."""
+    unit: str           # its length: '1', 'n', 'S', 'R', 'p', 'q', 'm', '2n' or 'm*m'
+    read: int           # the models that answer a read ...
+    write: int          # ... and that accept a write: a mask over ICAR, RSR, PROBIT
+    prologue: bool      # a write on a logit handle makes the next call redraw omega_b
+    ckpt: int           # the models whose checkpoint holds it (``Engine.checkpoint``, in this order)
+
+
+ICAR, RSR, PROBIT = 1, 2, 4
+_LOGIT, _ALL = ICAR | RSR, ICAR | RSR | PROBIT
+STATE_NAMES = {
+    'alpha': StateName('q', _ALL, _ALL, True, _ALL),
+    'beta': StateName('p', _ALL, _ALL, True, _ALL),
+    'tau': StateName('1', _ALL, _ALL, True, _ALL),
+    'eta': StateName('n', _ALL, _ALL, True, ICAR | PROBIT),
+    'theta': StateName('m', RSR | PROBIT, RSR | PROBIT, True, RSR | PROBIT),
+    'z': StateName('n', _ALL, _ALL, True, _ALL),
+    'xz': StateName('2n', _LOGIT, _LOGIT, True, ICAR),
+    'c': StateName('m', PROBIT, PROBIT, False, PROBIT),
+    'eps': StateName('n', PROBIT, PROBIT, False, PROBIT),
+    'iter': StateName('1', _ALL, _ALL, True, 0),
+    'k': StateName('n', _ALL, 0, False, 0),
+    'exists': StateName('S', _ALL, 0, False, 0),
+    'omega_a': StateName('R', _ALL, _ALL, True, 0),
+    'omega_b': StateName('n', _ALL, 0, False, 0),
+    'rhs': StateName('n', _LOGIT, 0, False, 0),
+    'minres_itn': StateName('1', _LOGIT, 0, False, 0),
+    'rsr_gram': StateName('m*m', RSR, 0, False, 0),
+    'link': StateName('1', PROBIT, 0, False, 0),
+    'debug_close_window': StateName('1', 0, _LOGIT, False, 0),
+    'debug_maxiter': StateName('1', 0, _LOGIT, True, 0),
+}
+
+
 class SumsKind(NamedTuple):
-    """One kind of per-site running sums the engine keeps on the device (``SUMS`` of csrc/occ_gibbs.hip), as Python sees it."""
+    """One kind of per-site running sums the engine keeps on the device (``SUMS`` of csrc/occ_names.hpp), as Python sees it."""
     fields: tuple       # its state names: switch, count, sums (a sum's short name drops the kind's prefix, 'site_' / 'll_')
     what: str           # what messages call it
 

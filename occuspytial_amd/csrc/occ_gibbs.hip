@@ -30,6 +30,7 @@
 #include "occ_holdout.hpp"
 #include "occ_accum.hpp"
 #include "occ_draws.hpp"
+#include "occ_names.hpp"
 #include "occ_call.hpp"
 #include "occ_layout.hpp"
 #include "occ_wait.hpp"
@@ -87,22 +88,14 @@ using DeviceLease = std::unique_lock<std::recursive_mutex>;
 inline DeviceLease lease_device(int device) { return DeviceLease(device_slot(device).busy); }
 
 // ---- the kinds of per-site running sums, described once --------------------------------------------------------------
-// SUMS_SITE: the posterior summaries (state names site_*); SUMS_LL: the log-likelihood sums of streaming WAIC (ll_*).  A kind
-// is switched per chain (its bit of ChainScalars::site_on), is kept in arrays of its own ([nacc C n] sums, [C] counts of
-// accumulated iterations) by a z-update kernel of its own that stands where k_z_ob stands, and is read and written through
-// occ_get_state / occ_set_state.  Whatever the host does for a kind -- names, snapshot and restore around a call that may
-// be re-run -- is a loop over this table.  Which z-update kernel runs is not a kind's business: occ_plan.hpp's OUTPUTS.
-enum : int { SUMS_SITE = 0, SUMS_LL = 1, N_SUMS = 2 };
-struct SumsKind {
-    uint32_t bit;  // of ChainScalars::site_on
-    int nacc;
-    double *Ctx::*acc, *Ctx::*count;
-    const char *what, *sw, *cnt, *sum[SITE_NACC];  // in messages; state names: switch, count, the sums in their *_NACC order
-};
-const SumsKind SUMS[N_SUMS] = {
-    {OUT_SITE, SITE_NACC, &Ctx::site_acc, &Ctx::site_count, "site summaries", output_of(OUT_SITE).sw, "site_count",
-     {"site_psi", "site_occ", "site_z", "site_eta", "site_eta2"}},
-    {OUT_LL, LL_NACC, &Ctx::ll_acc, &Ctx::ll_count, "log-likelihood sums", output_of(OUT_LL).sw, "ll_count", {"ll_lik", "ll_log", "ll_log2"}}};
+// A kind (occ_names.hpp: SUMS -- the bit of ChainScalars::site_on, the number of sums, the names) is kept in arrays of its own
+// ([nacc C n] sums, [C] counts of accumulated iterations) by a z-update kernel of its own that stands where k_z_ob stands,
+// and is read and written through occ_get_state / occ_set_state.  Whatever the host does for a kind -- snapshot and restore
+// around a call that may be re-run, state access -- is a loop over that table and this one, the kind's members of Ctx.
+// Which z-update kernel runs is not a kind's business: occ_plan.hpp's OUTPUTS.
+struct SumsCtx { double *Ctx::*acc, *Ctx::*count; };
+const SumsCtx SUMS_CTX[N_SUMS] = {{&Ctx::site_acc, &Ctx::site_count}, {&Ctx::ll_acc, &Ctx::ll_count}};
+static_assert(N_SUMS == 2 && SUMS[SUMS_SITE].nacc == SITE_NACC && SUMS[SUMS_LL].nacc == LL_NACC, "SUMS: the kernels' sums");
 
 // The accumulators behind the z update have a table of their own (occ_accum.hpp: ACCUM, plain C++); it agrees with the kernels' headers.
 static_assert(ACCUM[ACC_HIST].slots == 1 && ACCUM[ACC_HIST].elem == sizeof(*HistArgs::cnt) && ACCUM[ACC_HIST].on_min == HIST_BINS_MIN && ACCUM[ACC_HIST].on_max == HIST_BINS_MAX, "ACCUM: hist");
@@ -1053,8 +1046,8 @@ int open_window(occ_sampler *s, int64_t n_iter, int64_t burnin, int64_t keep, bo
             const size_t nsum = (size_t)SUMS[k].nacc * Cn;
             if (!(s->outputs_on & SUMS[k].bit)) continue;
             if (!r.snap && (rc = dev_alloc(s, &r.snap, nsum + (size_t)c.C, false))) return rc;
-            HIP_TRY(part(c.*SUMS[k].acc, r.snap, sizeof(double) * nsum));
-            HIP_TRY(part(c.*SUMS[k].count, r.snap + nsum, sizeof(double) * (size_t)c.C));
+            HIP_TRY(part(c.*SUMS_CTX[k].acc, r.snap, sizeof(double) * nsum));
+            HIP_TRY(part(c.*SUMS_CTX[k].count, r.snap + nsum, sizeof(double) * (size_t)c.C));
         }
         for (int k = 0; k < N_ACCUM; ++k) {  // ... and so are the accumulators behind the z update, in bytes: data, then counts
             occ_sampler::AccumRun &r = s->accum(k);
@@ -1762,6 +1755,20 @@ int push_z(occ_sampler *s, uint8_t *z_dev, size_t n, const double *in, int64_t l
     HIP_TRY(copy_on(s, z_dev, z.data(), n, hipMemcpyHostToDevice));
     return OCC_OK;
 }
+// `count` doubles of one chain off a device array, and onto it (the length is the caller's check)
+int pull(occ_sampler *s, const double *src, size_t count, std::vector<double> &v)
+{
+    v.resize(count);
+    if (count) HIP_TRY(copy_on(s, v.data(), src, sizeof(double) * count, hipMemcpyDeviceToHost));
+    return OCC_OK;
+}
+int push(occ_sampler *s, double *dst, const double *in, size_t count)
+{
+    HIP_TRY(copy_on(s, dst, in, sizeof(double) * count, hipMemcpyHostToDevice));
+    return OCC_OK;
+}
+// alpha, beta or tau (an ST_ row) in one chain's scalars, of either model
+template <class Chain> double *chain_field(Chain &c, int row) { return row == ST_ALPHA ? c.alpha : row == ST_BETA ? c.beta : &c.tau; }
 // the end of occ_get_state: the length always, the values when the caller gave a buffer
 int give_state(occ_sampler *s, const std::vector<double> &v, double *out, int64_t cap, int64_t *len)
 {
@@ -1771,77 +1778,6 @@ int give_state(occ_sampler *s, const std::vector<double> &v, double *out, int64_
         std::copy(v.begin(), v.end(), out);
     }
     return OCC_OK;
-}
-
-int pb_get_state(occ_sampler *s, int chain, const std::string &nm, std::vector<double> &v)
-{
-    const PbArgs &A = s->pb;
-    const size_t n = (size_t)A.n, R = (size_t)A.R, m = (size_t)A.m;
-    auto pull = [&](const double *src, size_t count) -> int {
-        v.resize(count);
-        if (count) HIP_TRY(copy_on(s, v.data(), src, sizeof(double) * count, hipMemcpyDeviceToHost));
-        return OCC_OK;
-    };
-    std::vector<PbChain> h;
-    int rc = pb_read_chains(s, h);
-    if (rc) return rc;
-    const PbChain &c = h[chain];
-    if (nm == "eta") return pull(A.eta + chain * n, n);
-    if (nm == "eps") return pull(A.eps + chain * n, n);
-    if (nm == "omega_b") return pull(A.omega_b + chain * n, n);
-    if (nm == "omega_a") return pull(A.omega_a + chain * R, R);
-    if (nm == "c") return pull(A.c + chain * m, m);
-    if (nm == "theta") {
-        std::vector<double> cc;
-        if ((rc = pull(A.c + chain * m, m))) return rc;
-        cc.swap(v);
-        v.assign(m, 0.0);
-        for (size_t i = 0; i < m; ++i) {
-            double t = 0.0;
-            for (size_t j = 0; j < m; ++j) t = std::fma(s->pb_G[i * m + j], cc[j], t);
-            v[i] = t;
-        }
-        return OCC_OK;
-    }
-    if (nm == "z" || nm == "k" || nm == "exists") return pull_z_view(s, nm, A.z + chain * n, n, A.S, v);
-    if (nm == "alpha") v.assign(c.alpha, c.alpha + A.q);
-    else if (nm == "beta") v.assign(c.beta, c.beta + A.p);
-    else if (nm == "tau") v.assign(1, c.tau);
-    else if (nm == "iter") v.assign(1, (double)c.it);
-    else if (nm == "link") v.assign(1, 1.0);
-    else return set_error(s, OCC_E_STATE, "unknown state name");
-    return OCC_OK;
-}
-
-int pb_set_state(occ_sampler *s, int chain, const std::string &nm, const double *in, int64_t len)
-{
-    const PbArgs &A = s->pb;
-    const size_t n = (size_t)A.n, R = (size_t)A.R, m = (size_t)A.m;
-    auto need = [&](size_t want) { return (size_t)len == want; };
-    auto push = [&](double *dst, size_t count) -> int {
-        if (!need(count)) return set_error(s, OCC_E_STATE, "wrong length");
-        HIP_TRY(copy_on(s, dst, in, sizeof(double) * count, hipMemcpyHostToDevice));
-        return OCC_OK;
-    };
-    if (nm == "eta") return push(A.eta + chain * n, n);
-    if (nm == "eps") return push(A.eps + chain * n, n);
-    if (nm == "omega_a") return push(A.omega_a + chain * R, R);
-    if (nm == "c") return push(A.c + chain * m, m);
-    if (nm == "theta") {
-        if (!need(m)) return set_error(s, OCC_E_STATE, "wrong length");
-        return pb_set_theta(s, chain, in);
-    }
-    if (nm == "z") return push_z(s, A.z + chain * n, n, in, len);
-    std::vector<PbChain> h;
-    int rc = pb_read_chains(s, h);
-    if (rc) return rc;
-    PbChain &c = h[chain];
-    if (nm == "alpha" && need((size_t)A.q)) std::copy(in, in + A.q, c.alpha);
-    else if (nm == "beta" && need((size_t)A.p)) std::copy(in, in + A.p, c.beta);
-    else if (nm == "tau" && need(1)) c.tau = in[0];
-    else if (nm == "iter" && need(1)) c.it = (uint32_t)in[0];
-    else return set_error(s, OCC_E_STATE, "unknown state name or wrong length");
-    return pb_write_chains(s, h);
 }
 
 // occ_profile of a probit handle: `reps` launches of each kernel in a captured graph between two events, role by role.
@@ -3095,23 +3031,28 @@ int occ_run(occ_sampler *s, int64_t n_iter, int64_t burnin, double *out_alpha, d
     return with_rerun(s, [&](bool snapshot) { return run_impl(s, n_iter, burnin, out_alpha, out_beta, out_tau, snapshot); });
 }
 
-// The state names of the per-site sums, of any kind (SUMS): -> kind and 0.. the sum's place in the kind's array, SITE_COUNT,
-// SITE_SWITCH; SITE_NONE (then *kind says nothing).
-enum : int { SITE_NONE = -1, SITE_COUNT = -2, SITE_SWITCH = -3 };
-static int site_field(const std::string &nm, int *kind)
-{
-    for (int k = 0; k < N_SUMS; ++k) {
-        *kind = k;
-        if (nm == SUMS[k].sw) return SITE_SWITCH;
-        if (nm == SUMS[k].cnt) return SITE_COUNT;
-        for (int q = 0; q < SUMS[k].nacc; ++q)
-            if (nm == SUMS[k].sum[q]) return q;
-    }
-    return SITE_NONE;
-}
+// ---- occ_get_state / occ_set_state of the names of the per-site sums (SUMS; logit models) ---------------------------------
 static int sums_refused(occ_sampler *s, const SumsKind &k)
 {
     return set_error(s, OCC_E_STATE, (std::string(k.what) + " are not available for the probit model").c_str());
+}
+// The chain's switch (1), its count (1) or one of its sums (n); until the kind's first switch-on every name answers OCC_E_STATE.
+static int get_site_state(occ_sampler *s, int chain, int kind, int field, std::vector<double> &v)
+{
+    const SumsKind &k = SUMS[kind];
+    const SumsCtx &m = SUMS_CTX[kind];
+    if (s->probit) return sums_refused(s, k);
+    const Ctx &c = s->ctx;
+    const size_t n = (size_t)c.n;
+    if (!(c.*m.acc))
+        return set_error(s, OCC_E_STATE, (std::string(k.what) + " have not been switched on for this handle (set " + k.sw + " to 1 first)").c_str());
+    if (field == SITE_COUNT) return pull(s, c.*m.count + chain, 1, v);
+    if (field != SITE_SWITCH) return pull(s, c.*m.acc + (size_t)field * c.C * n + chain * n, n, v);
+    std::vector<ChainScalars> h;
+    const int rc = read_scalars(s, h);
+    if (rc) return rc;
+    v.assign(1, (h[chain].site_on & k.bit) ? 1.0 : 0.0);
+    return OCC_OK;
 }
 
 // One chain's switch of one output goes on or off, in the scalars `h` the caller has read (probit handle: in regions.pb_on;
@@ -3153,6 +3094,7 @@ static int flip_output(occ_sampler *s, std::vector<ChainScalars> &h, int chain, 
 static int set_site_state(occ_sampler *s, int chain, int kind, int field, const double *in, int64_t len)
 {
     const SumsKind &k = SUMS[kind];
+    const SumsCtx &m = SUMS_CTX[kind];
     if (s->probit) return sums_refused(s, k);
     Ctx &c = s->ctx;
     const size_t n = (size_t)c.n, Cn = (size_t)c.C * n;
@@ -3160,29 +3102,29 @@ static int set_site_state(occ_sampler *s, int chain, int kind, int field, const 
     std::vector<ChainScalars> h;
     if ((rc = read_scalars(s, h))) return rc;
     if (field != SITE_SWITCH) {
-        if (!(c.*k.acc) || !(h[chain].site_on & k.bit))
+        if (!(c.*m.acc) || !(h[chain].site_on & k.bit))
             return set_error(s, OCC_E_STATE, (std::string(k.what) + " are switched off for this chain (set " + k.sw + " to 1 first)").c_str());
         if ((size_t)len != (field == SITE_COUNT ? (size_t)1 : n)) return set_error(s, OCC_E_STATE, "wrong length");
         if (field == SITE_COUNT) {
             if (!(in[0] >= 0.0) || in[0] != std::floor(in[0])) return set_error(s, OCC_E_STATE, (std::string(k.cnt) + " is a whole number of iterations").c_str());
-            HIP_TRY(copy_on(s, c.*k.count + chain, in, sizeof(double), hipMemcpyHostToDevice));
+            HIP_TRY(copy_on(s, c.*m.count + chain, in, sizeof(double), hipMemcpyHostToDevice));
         } else {
-            HIP_TRY(copy_on(s, c.*k.acc + (size_t)field * Cn + chain * n, in, sizeof(double) * n, hipMemcpyHostToDevice));
+            HIP_TRY(copy_on(s, c.*m.acc + (size_t)field * Cn + chain * n, in, sizeof(double) * n, hipMemcpyHostToDevice));
         }
         return OCC_OK;
     }
     if (len != 1) return set_error(s, OCC_E_STATE, "wrong length");
     const bool on = in[0] != 0.0;
-    if (!on && !(c.*k.acc)) return OCC_OK;  // never switched on: nothing to switch off
+    if (!on && !(c.*m.acc)) return OCC_OK;  // never switched on: nothing to switch off
     WAIT_TRY(s->side);
-    if (on && !(c.*k.acc)) {
-        if ((rc = dev_alloc(s, &(c.*k.acc), (size_t)k.nacc * Cn))) return rc;
-        if ((rc = dev_alloc(s, &(c.*k.count), (size_t)c.C))) return rc;
+    if (on && !(c.*m.acc)) {
+        if ((rc = dev_alloc(s, &(c.*m.acc), (size_t)k.nacc * Cn))) return rc;
+        if ((rc = dev_alloc(s, &(c.*m.count), (size_t)c.C))) return rc;
         HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
     }
     if (on) {
-        for (int q = 0; q < k.nacc; ++q) HIP_TRY(fill_on(s, c.*k.acc + (size_t)q * Cn + chain * n, 0, sizeof(double) * n));
-        HIP_TRY(fill_on(s, c.*k.count + chain, 0, sizeof(double)));
+        for (int q = 0; q < k.nacc; ++q) HIP_TRY(fill_on(s, c.*m.acc + (size_t)q * Cn + chain * n, 0, sizeof(double) * n));
+        HIP_TRY(fill_on(s, c.*m.count + chain, 0, sizeof(double)));
     }
     return flip_output(s, h, chain, k.bit, on);
 }
@@ -3686,163 +3628,200 @@ static int set_accum_state(occ_sampler *s, int chain, int kind, int field, const
 }
 
 
+// ---- occ_get_state / occ_set_state of the plain state names (occ_names.hpp: STATE; every model) ----------------------------
+// Who has a name, its length and what a mistake earns are the table's (state_refusal, state_length); what follows is a switch
+// on where the value lives.  A model's own: the address of a device array, theta, xz, the parity of omega_b, iter's control
+// words, debug_maxiter.
+static unsigned state_model(const occ_sampler *s) { return s->probit ? MODEL_PROBIT : s->rsr.m > 0 ? MODEL_RSR : MODEL_ICAR; }
+static StateDims state_dims(const occ_sampler *s)
+{
+    const Ctx &c = s->ctx;
+    const PbArgs &A = s->pb;
+    if (s->probit) return {(size_t)A.n, (size_t)A.S, (size_t)A.R, (size_t)A.p, (size_t)A.q, (size_t)A.m};
+    return {(size_t)c.n, (size_t)c.S, (size_t)c.R, (size_t)c.p, (size_t)c.q, (size_t)s->rsr.m};
+}
+// One chain's part of the device array behind an AT_ARRAY row; `it`: the chain's completed iterations (omega_b, logit)
+static double *state_array(const occ_sampler *s, int row, size_t chain, const StateDims &d, uint32_t it)
+{
+    const Ctx &c = s->ctx;
+    const PbArgs &A = s->pb;
+    switch (row) {
+    case ST_ETA: return (s->probit ? A.eta : c.eta) + chain * d.n;
+    case ST_OMEGA_A: return (s->probit ? A.omega_a : c.omega_a) + chain * d.R;
+    case ST_OMEGA_B: return (s->probit ? A.omega_b : c.omega_b[(it + 1) & 1]) + chain * d.n;  // of the last completed iteration
+    case ST_RHS: return c.rhs + chain * d.n;
+    case ST_EPS: return A.eps + chain * d.n;
+    case ST_C: return A.c + chain * d.m;
+    // tests only, m x m row-major, of the last theta update.  m <= RSR_MAX_DIM: K' diag(omega_b) K (upper 16 x 16 tiles).
+    // m > RSR_MAX_DIM: k_rsrb_assemble adds tau Qr in place and k_rsrb_step overwrites each 32-row panel's rows right of
+    // its diagonal block with the factor U (Lam = U'U); the diagonal blocks hold trailing-update values, their factors
+    // are in big_dfac.  Entries below the diagonal are undefined.
+    case ST_RSR_GRAM: return s->rsr.gram + chain * d.m * d.m;
+    default: return nullptr;
+    }
+}
+
+static int get_plain_state(occ_sampler *s, int chain, int row, std::vector<double> &v)
+{
+    const StateDims d = state_dims(s);
+    const size_t n = d.n, m = d.m, count = state_length(row, d);
+    // the chain's scalars: read only for a name that lives in them or needs the iteration number
+    std::vector<ChainScalars> h;
+    std::vector<PbChain> hp;
+    uint32_t it = 0;
+    if (STATE[row].at == AT_SCALARS || (row == ST_OMEGA_B && !s->probit)) {
+        const int rc = s->probit ? pb_read_chains(s, hp) : read_scalars(s, h);
+        if (rc) return rc;
+        it = s->probit ? hp[chain].it : h[chain].ctl[s->parity].it;  // iterations completed
+    }
+    switch (STATE[row].at) {
+    case AT_ARRAY: return pull(s, state_array(s, row, (size_t)chain, d, it), count, v);
+    case AT_Z: return pull_z_view(s, STATE[row].name, (s->probit ? s->pb.z : s->ctx.z) + chain * n, n, (int)d.S, v);
+    case AT_SCALARS:
+        if (row == ST_ITER) v.assign(1, (double)it);
+        else if (row == ST_MINRES_ITN) v.assign(1, (double)h[chain].minres_itn_last);
+        else {
+            const double *p = s->probit ? chain_field(hp[chain], row) : chain_field(h[chain], row);
+            v.assign(p, p + count);
+        }
+        return OCC_OK;
+    default: break;
+    }
+    if (row == ST_LINK) {
+        v.assign(1, 1.0);
+    } else if (row == ST_XZ) {
+        std::vector<double2> x(n);
+        HIP_TRY(copy_on(s, x.data(), s->ctx.Xv + chain * n, sizeof(double2) * n, hipMemcpyDeviceToHost));
+        v.resize(2 * n);
+        for (size_t i = 0; i < n; ++i) { v[i] = x[i].x; v[n + i] = x[i].y; }
+    } else if (!s->probit) {  // theta, reduced rank: as stored
+        return pull(s, s->rsr.theta + chain * m, m, v);
+    } else {  // theta, probit: G c
+        std::vector<double> cc;
+        const int rc = pull(s, s->pb.c + chain * m, m, cc);
+        if (rc) return rc;
+        v.assign(m, 0.0);
+        for (size_t i = 0; i < m; ++i) {
+            double t = 0.0;
+            for (size_t j = 0; j < m; ++j) t = std::fma(s->pb_G[i * m + j], cc[j], t);
+            v[i] = t;
+        }
+    }
+    return OCC_OK;
+}
+
+// tests of the MINRES-did-not-converge exit (logit.py:91-92): the iteration limit of every chain's solve; 0 restores
+// scipy's default 5 * (2n).  The limit travels by value in the kernels' argument blocks: the graphs are re-captured.
+static int set_debug_maxiter(occ_sampler *s, double limit)
+{
+    if (limit < 0.0) return set_error(s, OCC_E_STATE, "wrong length");
+    WAIT_TRY(s->stream);
+    WAIT_TRY(s->side);
+    destroy_graph(s);
+    s->ctx.maxiter = limit > 0.0 ? (long long)limit : 10LL * s->ctx.n;
+    s->kry.maxiter = s->ctx.maxiter;
+    s->iter.a.maxiter = s->ctx.maxiter;
+    HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
+    return OCC_OK;
+}
+
+// `row`: -1 for a name that is none
+static int set_plain_state(occ_sampler *s, int chain, int row, const double *in, int64_t len)
+{
+    const StateDims d = state_dims(s);
+    if (const char *why = state_refusal(row, state_model(s), true, len, d)) return set_error(s, OCC_E_STATE, why);
+    const size_t n = d.n;
+    int rc = OCC_OK;
+    switch (STATE[row].at) {
+    case AT_ARRAY: rc = push(s, state_array(s, row, (size_t)chain, d, 0), in, (size_t)len); break;
+    case AT_Z: rc = push_z(s, (s->probit ? s->pb.z : s->ctx.z) + chain * n, n, in, len); break;
+    case AT_COMPUTED:
+        if (row == ST_THETA) {
+            rc = s->probit ? pb_set_theta(s, chain, in) : set_theta(s, chain, in);
+        } else {  // xz
+            std::vector<double2> x(n);
+            for (size_t i = 0; i < n; ++i) x[i] = make_double2(in[i], in[n + i]);
+            HIP_TRY(copy_on(s, s->ctx.Xv + chain * n, x.data(), sizeof(double2) * n, hipMemcpyHostToDevice));
+        }
+        break;
+    case AT_SCALARS:
+        if (s->probit) {
+            std::vector<PbChain> hp;
+            if ((rc = pb_read_chains(s, hp))) return rc;
+            if (row == ST_ITER) hp[chain].it = (uint32_t)in[0];
+            else std::copy(in, in + len, chain_field(hp[chain], row));
+            rc = pb_write_chains(s, hp);
+        } else {
+            std::vector<ChainScalars> h;
+            if ((rc = read_scalars(s, h))) return rc;
+            ChainScalars &sc = h[chain];
+            if (row == ST_ITER) {
+                const Ctl fresh = {(uint32_t)in[0], 0u};
+                sc.ctl[0] = sc.ctl[1] = sc.mid[0] = sc.mid[1] = fresh;
+            } else std::copy(in, in + len, chain_field(sc, row));
+            rc = write_scalars(s, h);
+        }
+        break;
+    default:  // a word of the handle
+        // debug_close_window: tests of the no-progress exit of occ_run, the next call's window reaches the device with zero iterations
+        if (row == ST_DEBUG_CLOSE_WINDOW) s->debug_close_window = in[0] != 0.0;
+        else rc = set_debug_maxiter(s, in[0]);
+    }
+    if (rc) return rc;
+    if (STATE[row].prologue && !s->probit) s->need_prologue = true;  // omega_b of the coming iteration must be redrawn from the new state
+    return OCC_OK;
+}
+
+// the handle's labels as they were set
+static int get_component_id(occ_sampler *s, std::vector<double> &v)
+{
+    if (const char *why = component_refusal(s)) return set_error(s, OCC_E_STATE, why);
+    if (s->comp.id.empty()) return set_error(s, OCC_E_STATE, "component_id has not been set for this handle");
+    v.assign(s->comp.id.begin(), s->comp.id.end());
+    return OCC_OK;
+}
+
 int occ_get_state(occ_sampler *s, int32_t chain, const char *name, double *out, int64_t cap, int64_t *len)
 {
     if (!s || !name || !len) return OCC_E_BADARG;
-    const Ctx &c = s->ctx;
-    if (chain < 0 || chain >= c.C) return set_error(s, OCC_E_BADARG, "bad chain index");
+    if (chain < 0 || chain >= s->ctx.C) return set_error(s, OCC_E_BADARG, "bad chain index");
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
     WAIT_TRY(s->stream);
-    const std::string nm(name);
-    const size_t n = (size_t)c.n, R = (size_t)c.R;
+    const NameRoute r = name_route(name);
     std::vector<double> v;
-    if (nm == "component_id") {  // the handle's labels as they were set
-        if (const char *why = component_refusal(s)) return set_error(s, OCC_E_STATE, why);
-        if (s->comp.id.empty()) return set_error(s, OCC_E_STATE, "component_id has not been set for this handle");
-        v.assign(s->comp.id.begin(), s->comp.id.end());
-        return give_state(s, v, out, cap, len);
+    int rc;
+    switch (r.family) {
+    case FAM_COMPONENT: rc = get_component_id(s, v); break;
+    case FAM_DRAWS: rc = get_draws_state(s, chain, r.kind, r.field, v); break;
+    case FAM_ACCUM: rc = get_accum_state(s, chain, r.kind, r.field, v); break;
+    case FAM_SUMS: rc = get_site_state(s, chain, r.kind, r.field, v); break;
+    default:  // a plain name, or none
+        if (const char *why = state_refusal(r.kind, state_model(s), false, 0, state_dims(s))) return set_error(s, OCC_E_STATE, why);
+        if (!out) {  // a length query: a function of the problem's sizes, nothing is copied off the device
+            *len = (int64_t)state_length(r.kind, state_dims(s));
+            return OCC_OK;
+        }
+        rc = get_plain_state(s, chain, r.kind, v);
     }
-    int drw_field = DRW_NONE;
-    const int drw_kind = draws_lookup(name, &drw_field);
-    if (drw_kind >= 0) {
-        const int drc = get_draws_state(s, chain, drw_kind, drw_field, v);
-        return drc ? drc : give_state(s, v, out, cap, len);
-    }
-    int acc_field = ACC_NONE;
-    const int acc_kind = accum_lookup(name, &acc_field);
-    if (acc_kind >= 0) {
-        const int arc = get_accum_state(s, chain, acc_kind, acc_field, v);
-        return arc ? arc : give_state(s, v, out, cap, len);
-    }
-    int sums_kind = SUMS_SITE;
-    const int site_q = site_field(nm, &sums_kind);
-    const SumsKind &sk = SUMS[sums_kind];
-    if (site_q != SITE_NONE) {
-        if (s->probit) return sums_refused(s, sk);
-        if (!(c.*sk.acc))
-            return set_error(s, OCC_E_STATE, (std::string(sk.what) + " have not been switched on for this handle (set " + sk.sw + " to 1 first)").c_str());
-    }
-    if (s->probit) {
-        const int prc = pb_get_state(s, chain, nm, v);
-        return prc ? prc : give_state(s, v, out, cap, len);
-    }
-    auto pull = [&](const double *src, size_t count) -> int {
-        v.resize(count);
-        if (count) HIP_TRY(copy_on(s, v.data(), src, sizeof(double) * count, hipMemcpyDeviceToHost));
-        return OCC_OK;
-    };
-    int rc = OCC_OK;
-    std::vector<ChainScalars> h;
-    if ((rc = read_scalars(s, h))) return rc;
-    const ChainScalars &sc = h[chain];
-    const uint32_t it = sc.ctl[s->parity].it;  // iterations completed
-    if (nm == "eta") rc = pull(c.eta + chain * n, n);
-    else if (nm == "omega_b") rc = pull(c.omega_b[(it + 1) & 1] + chain * n, n);  // of the last completed iteration
-    else if (nm == "omega_a") rc = pull(c.omega_a + chain * R, R);
-    else if (nm == "rhs") rc = pull(c.rhs + chain * n, n);
-    else if (nm == "z" || nm == "k" || nm == "exists") rc = pull_z_view(s, nm, c.z + chain * n, n, c.S, v);
-    else if (nm == "xz") {
-        std::vector<double2> x(n);
-        HIP_TRY(copy_on(s, x.data(), c.Xv + chain * n, sizeof(double2) * n, hipMemcpyDeviceToHost));
-        v.resize(2 * n);
-        for (size_t i = 0; i < n; ++i) { v[i] = x[i].x; v[n + i] = x[i].y; }
-    } else if (nm == "alpha") v.assign(sc.alpha, sc.alpha + c.q);
-    else if (nm == "beta") v.assign(sc.beta, sc.beta + c.p);
-    else if (nm == "tau") v.assign(1, sc.tau);
-    else if (nm == "minres_itn") v.assign(1, (double)sc.minres_itn_last);
-    else if (nm == "iter") v.assign(1, (double)it);
-    else if (site_q == SITE_SWITCH) v.assign(1, (sc.site_on & sk.bit) ? 1.0 : 0.0);
-    else if (site_q == SITE_COUNT) rc = pull(c.*sk.count + chain, 1);
-    else if (site_q >= 0) rc = pull(c.*sk.acc + (size_t)site_q * c.C * n + chain * n, n);
-    else if (nm == "rsr_gram" && s->rsr.m > 0) {
-        // tests only, m x m row-major, of the last theta update.  m <= RSR_MAX_DIM: K' diag(omega_b) K (upper 16 x 16 tiles).
-        // m > RSR_MAX_DIM: k_rsrb_assemble adds tau Qr in place and k_rsrb_step overwrites each 32-row panel's rows right of
-        // its diagonal block with the factor U (Lam = U'U); the diagonal blocks hold trailing-update values, their factors
-        // are in big_dfac.  Entries below the diagonal are undefined.
-        v.resize((size_t)s->rsr.m * s->rsr.m);
-        HIP_TRY(copy_on(s, v.data(), s->rsr.gram + (size_t)chain * v.size(), sizeof(double) * v.size(), hipMemcpyDeviceToHost));
-    }
-    else if (nm == "theta" && s->rsr.m > 0) {
-        v.resize((size_t)s->rsr.m);
-        HIP_TRY(copy_on(s, v.data(), s->rsr.theta + (size_t)chain * s->rsr.m, sizeof(double) * v.size(), hipMemcpyDeviceToHost));
-    }
-    else return set_error(s, OCC_E_STATE, "unknown state name");
     return rc ? rc : give_state(s, v, out, cap, len);
 }
 
 int occ_set_state(occ_sampler *s, int32_t chain, const char *name, const double *in, int64_t len)
 {
     if (!s || !name || !in) return OCC_E_BADARG;
-    const Ctx &c = s->ctx;
-    if (chain < 0 || chain >= c.C) return set_error(s, OCC_E_BADARG, "bad chain index");
+    if (chain < 0 || chain >= s->ctx.C) return set_error(s, OCC_E_BADARG, "bad chain index");
     DeviceLease lease = lease_device(s->device);
     HIP_TRY(hipSetDevice(s->device));
     WAIT_TRY(s->stream);
-    const std::string nm(name);
-    if (nm == "component_id") return set_component_id(s, in, len);
-    int drw_field = DRW_NONE;
-    const int drw_kind = draws_lookup(name, &drw_field);
-    if (drw_kind >= 0) return set_draws_state(s, chain, drw_kind, drw_field, in, len);
-    int acc_field = ACC_NONE;
-    const int acc_kind = accum_lookup(name, &acc_field);
-    if (acc_kind >= 0) return set_accum_state(s, chain, acc_kind, acc_field, in, len);
-    int sums_kind = SUMS_SITE;
-    const int sums_q = site_field(nm, &sums_kind);
-    if (sums_q != SITE_NONE) return set_site_state(s, chain, sums_kind, sums_q, in, len);
-    if (s->probit) return pb_set_state(s, chain, nm, in, len);
-    const size_t n = (size_t)c.n, R = (size_t)c.R;
-    auto need = [&](size_t want) { return (size_t)len == want; };
-    if (nm == "eta") {
-        if (!need(n)) return set_error(s, OCC_E_STATE, "wrong length");
-        HIP_TRY(copy_on(s, c.eta + chain * n, in, sizeof(double) * n, hipMemcpyHostToDevice));
-    } else if (nm == "omega_a") {
-        if (!need(R)) return set_error(s, OCC_E_STATE, "wrong length");
-        HIP_TRY(copy_on(s, c.omega_a + chain * R, in, sizeof(double) * R, hipMemcpyHostToDevice));
-    } else if (nm == "z") {
-        int rc = push_z(s, c.z + chain * n, n, in, len);
-        if (rc) return rc;
-    } else if (nm == "theta" && s->rsr.m > 0) {
-        if (!need((size_t)s->rsr.m)) return set_error(s, OCC_E_STATE, "wrong length");
-        int rc = set_theta(s, chain, in);
-        if (rc) return rc;
-    } else if (nm == "xz") {
-        if (!need(2 * n)) return set_error(s, OCC_E_STATE, "wrong length");
-        std::vector<double2> x(n);
-        for (size_t i = 0; i < n; ++i) x[i] = make_double2(in[i], in[n + i]);
-        HIP_TRY(copy_on(s, c.Xv + chain * n, x.data(), sizeof(double2) * n, hipMemcpyHostToDevice));
-    } else if (nm == "debug_close_window") {
-        // tests of the no-progress exit of occ_run: the next call's window reaches the device with zero iterations
-        if (!need(1)) return set_error(s, OCC_E_STATE, "wrong length");
-        s->debug_close_window = in[0] != 0.0;
-        return OCC_OK;
-    } else if (nm == "debug_maxiter") {
-        // tests of the MINRES-did-not-converge exit (logit.py:91-92): the iteration limit of every chain's solve; 0 restores
-        // scipy's default 5 * (2n).  The limit travels by value in the kernels' argument blocks: the graphs are re-captured.
-        if (!need(1) || in[0] < 0.0) return set_error(s, OCC_E_STATE, "wrong length");
-        WAIT_TRY(s->stream);
-        WAIT_TRY(s->side);
-        destroy_graph(s);
-        s->ctx.maxiter = in[0] > 0.0 ? (long long)in[0] : 10LL * c.n;
-        s->kry.maxiter = s->ctx.maxiter;
-        s->iter.a.maxiter = s->ctx.maxiter;
-        HIP_TRY(copy_on(s, s->ctx_dev, &s->ctx, sizeof(Ctx), hipMemcpyHostToDevice));
-    } else {
-        std::vector<ChainScalars> h;
-        int rc = read_scalars(s, h);
-        if (rc) return rc;
-        ChainScalars &sc = h[chain];
-        if (nm == "alpha" && need((size_t)c.q)) std::copy(in, in + c.q, sc.alpha);
-        else if (nm == "beta" && need((size_t)c.p)) std::copy(in, in + c.p, sc.beta);
-        else if (nm == "tau" && need(1)) sc.tau = in[0];
-        else if (nm == "iter" && need(1)) {
-            const Ctl fresh = {(uint32_t)in[0], 0u};
-            sc.ctl[0] = sc.ctl[1] = sc.mid[0] = sc.mid[1] = fresh;
-        } else return set_error(s, OCC_E_STATE, "unknown state name or wrong length");
-        if ((rc = write_scalars(s, h))) return rc;
+    const NameRoute r = name_route(name);
+    switch (r.family) {
+    case FAM_COMPONENT: return set_component_id(s, in, len);
+    case FAM_DRAWS: return set_draws_state(s, chain, r.kind, r.field, in, len);
+    case FAM_ACCUM: return set_accum_state(s, chain, r.kind, r.field, in, len);
+    case FAM_SUMS: return set_site_state(s, chain, r.kind, r.field, in, len);
+    default: return set_plain_state(s, chain, r.kind, in, len);  // a plain name, or none
     }
-    s->need_prologue = true;  // omega_b of the coming iteration must be redrawn from the new state
-    return OCC_OK;
 }
 
 int occ_get_stats(occ_sampler *s, occ_stats *out)

@@ -1,7 +1,8 @@
 // occ_plan_capi.cpp -- the planner, the launch order and the z update's outputs (occ_plan.hpp), the accumulators behind the z
-// update (occ_accum.hpp), the draws of a call (occ_draws.hpp), a call's host decisions (occ_call.hpp) and the problem layout
-// (occ_layout.hpp) behind C entry points for tests/test_plan_cpu.py, tests/test_order_cpu.py, tests/test_outputs_cpu.py,
-// tests/test_accum_cpu.py, tests/test_draws_cpu.py, tests/test_call_cpu.py and tests/test_layout_cpu.py (ctypes).  Test infrastructure: `make plan` builds it with g++ into build/; it is never linked
+// update (occ_accum.hpp), the draws of a call (occ_draws.hpp), the state names (occ_names.hpp), a call's host decisions
+// (occ_call.hpp) and the problem layout (occ_layout.hpp) behind C entry points for tests/test_plan_cpu.py,
+// tests/test_order_cpu.py, tests/test_outputs_cpu.py, tests/test_accum_cpu.py, tests/test_draws_cpu.py, tests/test_names_cpu.py,
+// tests/test_call_cpu.py and tests/test_layout_cpu.py (ctypes).  Test infrastructure: `make plan` builds it with g++ into build/; it is never linked
 // into libocc_gibbs.so.
 #include <cstdio>
 #include <cstring>
@@ -10,6 +11,7 @@
 #include "occ_call.hpp"
 #include "occ_draws.hpp"
 #include "occ_layout.hpp"
+#include "occ_names.hpp"
 
 using namespace occ;
 
@@ -137,6 +139,38 @@ void occ_draws_row(int32_t k, const char *name[3], const char *refusal[5], int32
 int32_t occ_draws_lookup(const char *name, int32_t *field) { return draws_lookup(name, field); }
 double occ_draws_value(int32_t k, uint64_t raw, int64_t col) { return draws_value(DRAWS[k], &raw, (size_t)col); }
 int64_t occ_draws_length(int32_t field, int64_t n, int64_t keep, int64_t width) { return (int64_t)draws_length(field, (size_t)n, (size_t)keep, (size_t)width); }
+
+// The state names (occ_names.hpp).  The plain state of a chain (STATE): how many; row k's name and numbers {unit, read, write,
+// at, prologue, ckpt}; its length for dims = {n, S, R, p, q, m}; what a read or a write of `len` elements earns (row -1: a
+// name that is none).  The kinds of per-site sums (SUMS): how many; row k's words -- what, switch, count, the sums (null: none)
+// -- and numbers {bit, nacc}.  The router: out = {family, kind, field}.
+static StateDims state_dims(const int64_t d[6]) { return {(size_t)d[0], (size_t)d[1], (size_t)d[2], (size_t)d[3], (size_t)d[4], (size_t)d[5]}; }
+int32_t occ_state_count(void) { return N_STATE; }
+const char *occ_state_row(int32_t k, int32_t num[6])
+{
+    const StateName &st = STATE[k];
+    num[0] = st.unit; num[1] = (int32_t)st.read; num[2] = (int32_t)st.write; num[3] = st.at; num[4] = st.prologue; num[5] = (int32_t)st.ckpt;
+    return st.name;
+}
+int32_t occ_state_lookup(const char *name) { return state_lookup(name); }
+int64_t occ_state_length(int32_t row, const int64_t dims[6]) { return (int64_t)state_length(row, state_dims(dims)); }
+const char *occ_state_refusal(int32_t row, uint32_t model, int32_t write, int64_t len, const int64_t dims[6])
+{
+    return state_refusal(row, model, write != 0, len, state_dims(dims));
+}
+int32_t occ_sums_count(void) { return N_SUMS; }
+void occ_sums_row(int32_t k, const char *word[3], const char *sum[5], int32_t num[2])
+{
+    const SumsKind &s = SUMS[k];
+    word[0] = s.what; word[1] = s.sw; word[2] = s.cnt;
+    for (int q = 0; q < 5; ++q) sum[q] = q < s.nacc ? s.sum[q] : nullptr;
+    num[0] = (int32_t)s.bit; num[1] = s.nacc;
+}
+void occ_name_route(const char *name, int32_t out[3])
+{
+    const NameRoute r = name_route(name);
+    out[0] = r.family; out[1] = r.kind; out[2] = r.field;
+}
 
 // What a call decides on the host (occ_call.hpp), as it is.  occ_call_head: the steps as {kind, n, from_calib, long_pair} rows,
 // -> how many.  occ_call_progress: at = [C]{it, koff, it_base}, seen = [C]{it, koff} (updated) -> the stuck chain or -1.
